@@ -7,6 +7,10 @@
 
 One step = host mask draws + forward + masked loss + backward + (N>1: RCCL gradient all-reduce) + fused AdamW on
 a resident synthetic batch of B=32 tiles per GPU (weak scaling).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the measurements that take runs of
+their own: the roofline leg (per-kernel HIP-event times of K extra eager steps, HBM sub-stages) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy (see ``dump_outputs``).
 """
 
 from __future__ import annotations
@@ -222,6 +226,47 @@ def cpu_baseline(workload: str, seconds: float, phase: str = "pretrain") -> dict
                 "sample": f"CPU leg exceeded its {cap:.0f} s cap on this host"}
 
 
+DUMP_SAMPLE = 1 << 20     # elements kept of each large output (fixed, seeded positions); the whole set stays far below 64 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample(t: torch.Tensor, seed: int) -> torch.Tensor:
+    """``t`` flattened; above DUMP_SAMPLE elements, the elements at DUMP_SAMPLE fixed positions (seeded, sorted)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(loop, loss: torch.Tensor, out_dir: str) -> None:
+    """What a caller of the timed step holds after its last step, as float32 / float64 ``.npy`` files in ``out_dir``:
+    ``loss`` (float64), ``params`` / ``grads`` (the fp32 master weights after the AdamW update and the step's gradients),
+    pretrain: ``rec_<modality>`` (reconstructions, ``MAEEngine.reconstructions``) and ``mask_<group>`` (token masks, 0 / 1);
+    probe / finetune: ``logits_<target>``.  Outputs above DUMP_SAMPLE elements are sampled at fixed seeded positions."""
+    import numpy as np
+
+    eng = loop.engine
+    st = eng.store
+    arrays = {"loss": loss.detach().double().reshape(1), "params": _sample(st.flat, 1), "grads": _sample(st.grad, 2)}
+    if hasattr(eng, "reconstructions"):
+        pixels, _ = eng.reconstructions()
+        for i, (m, img) in enumerate(sorted(pixels.items())):
+            arrays[f"rec_{m}"] = _sample(img, 100 + i)
+        for i, (g, mask) in enumerate(sorted(eng.token_masks().items())):
+            arrays[f"mask_{g}"] = _sample(mask.float(), 200 + i)
+    if hasattr(eng, "logits"):
+        for i, (t, lg) in enumerate(sorted(eng.logits().items())):
+            arrays[f"logits_{t}"] = _sample(lg.float(), 300 + i)
+    out = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total / 2**20:.1f} MB exceeds the {DUMP_LIMIT_BYTES >> 20} MB limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -234,8 +279,12 @@ def main() -> None:
                     help="GEMM operand type: bf16 (BASELINE metric), fp8 = e4m3 forward GEMMs (BASELINE configs[4]: --config c5)")
     ap.add_argument("--phase", default="pretrain", choices=["pretrain", "probe", "finetune"],
                     help="pretrain = the BASELINE metric; probe / finetune = the supervised branch (configs c3, c4)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure: roofline leg (per-kernel times, HBM sub-stages) and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, weights, gradients, reconstructions / logits) to DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline sample of --full (0 = skip)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the roofline leg")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--single-stream", action="store_true", help="profiling aid: no group-parallel streams (clean per-kernel times)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
@@ -253,7 +302,8 @@ def main() -> None:
                     help="gradient exchange at N > 1: all-reduce per bucket (default) or reduce-scatter -> sharded AdamW -> all-gather")
     ap.add_argument("--log-losses", action="store_true",
                     help="diagnostic: add the loss of every timed step to the JSON line (one tiny device copy per step)")
-    ap.add_argument("--shapes", action="store_true", help="print per-shape kernel times to stderr (diagnostic)")
+    ap.add_argument("--shapes", action="store_true",
+                    help="print per-shape kernel times to stderr (diagnostic; runs the roofline leg as --full does)")
     args = ap.parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_worker(args.config, args.cpu_seconds, args.phase)), flush=True)
@@ -372,9 +422,11 @@ def main() -> None:
     step_seq = [a.elapsed_time(b) for a, b in zip(marks, marks[1:])]
     step_ms = sorted(step_seq)
     loss_val = float(loss.item())   # the engine's loss buffer is static: read it before the roofline leg runs more steps
+    if args.dump_outputs and rank == 0:   # before the roofline leg: it runs more steps on the same buffers
+        dump_outputs(loop, loss, args.dump_outputs)
     # Roofline leg: the same steps once more with HIP events around every MFMA-kernel launch on its stream (event
     # pairs cannot be recorded inside a captured graph, so these steps are launched eagerly; kernels are identical).
-    timer = None if args.no_kernel_timing else hip.KernelTimer()
+    timer = hip.KernelTimer() if (args.full or args.shapes) and not args.no_kernel_timing else None
     comm = None
     if gsync is not None:
         # Self-diagnosis of the data-parallel run (no scaling claim is made from it): which backend and how many ranks the process
@@ -477,7 +529,7 @@ def main() -> None:
         if timer is not None and args.shapes:
             for ms, kind, shape, n, tf in timer.by_shape(args.steps)[:80]:
                 print(f"{ms:8.3f} ms/step {kind:18s} {str(shape):26s} x{n:3d}/step {tf:7.1f} TFLOP/s", file=sys.stderr)
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds, args.phase)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -33,6 +33,7 @@ import torch  # noqa: E402
 
 REPO = Path(__file__).resolve().parent.parent
 REFERENCE = Path("/root/reference")
+import json  # noqa: E402
 import os  # noqa: E402
 
 GOLDEN = Path(os.environ.get("MAESTRO_GOLDEN_DIR", REPO / "tests" / "golden"))   # (tests redirect it to a temp directory)
@@ -653,6 +654,7 @@ def run_ckpt(ref, ours) -> None:
     # (3) the one-line swap of maestro/run_experiment.py:39-40: OUR SSLModule built from the REFERENCE's own config objects
     #     (DatasetsConfig / MaskConfig / ModelConfig instances, exactly what run_experiment passes) -- duck-typed, no conversion
     from maestro.conf.model import ModelConfig as RefModelConfig
+    shapes = {}
     for fusion, inter in (("group", 3), ("mod", 1), ("shared", 0), ("monotemp", 0)):
         cfg = RefModelConfig(model_size="tiny", fusion_mode=fusion, inter_depth=inter, use_ema=False)
         theirs = ref.model.SSLModule(datasets=ds_ref, mask=mask_ref, **vars(cfg))
@@ -662,6 +664,9 @@ def run_ckpt(ref, ours) -> None:
         assert a == b, (fusion, sorted(set(a) ^ set(b))[:5])
         assert swapped.norm_bands == theirs.norm_bands and swapped.model.mask_ratio == theirs.model.mask_ratio
         assert swapped.model.grid_size == theirs.model.grid_size and swapped.model.len_bands == theirs.model.len_bands
+        shapes[fusion] = {k: list(v) for k, v in a.items()}
+    # the reference module's state-dict keys and shapes per fusion mode, for the test that runs without the reference
+    (GOLDEN / "ref_ckpt_shapes.json").write_text(json.dumps(shapes, sort_keys=True) + "\n")
     print(f"[ckpt] maestro_amd SSLModule built from the reference's config objects: state-dict keys and shapes equal the "
           f"reference module's for all four fusion modes ({len(a)} tensors)")
 

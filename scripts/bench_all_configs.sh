@@ -6,7 +6,7 @@ tag=${1:-r03}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/cfg
 mkdir -p $out
-common="--steps 20 --warmup 5 --cpu-seconds 0"
+common="--full --steps 20 --warmup 5 --cpu-seconds 0"
 for cfg in c2 c3p c4 c5; do
   timeout -k 10 240 python $R/bench.py --config $cfg $common > $out/${tag}_bench_${cfg}.json 2>> $out/err.log || exit 1
   python -c "import json;d=json.load(open('$out/${tag}_bench_${cfg}.json'));print('$cfg',d['value'],d['ms_per_step'],d['whole_step']['mfma_frac'],d['roofline']['kernel'],d['roofline']['achieved'])"

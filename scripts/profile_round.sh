@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/prof
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $out/${tag}_bench_c3_n1.json 2> $out/${tag}_bench.err || exit 1
+python $R/bench.py --full > $out/${tag}_bench_c3_n1.json 2> $out/${tag}_bench.err || exit 1
 tail -c 600 $out/${tag}_bench_c3_n1.json; echo
 common="--cpu-seconds 0 --no-kernel-timing"
 # the traces are normalised per step (13 = 3 warm-up + 10 timed; counters: 5): no start-up passes of the first step in them

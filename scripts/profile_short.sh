@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/prof
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $out/${tag}_bench_c3_n1.json 2> $out/${tag}_bench.err || exit 1
+python $R/bench.py --full > $out/${tag}_bench_c3_n1.json 2> $out/${tag}_bench.err || exit 1
 tail -c 300 $out/${tag}_bench_c3_n1.json; echo
 common="--cpu-seconds 0 --no-kernel-timing"
 export MAESTRO_WARM_PASSES=0
