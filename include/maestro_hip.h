@@ -158,6 +158,41 @@ typedef struct MhQuantJob {
 int mh_quant_batched(const MhQuantJob* jobs_device, const unsigned long* items_device, int n_items, const float* scale,
                      float* amax, int mode, void* stream);
 int mh_fp8_update_scales(float* amax, float* scale, float* descale, int n, float format_max, int margin_log2, void* stream);
+/* ---------------------------------------------------------------------------------------------- MX block scaling
+ * The second fp8 scaling mode (maestro_amd/fp8.py, `mx`): OCP MX (MXFP8, e4m3 elements) with one E8M0 scale byte per BLOCK of
+ * 32 consecutive elements along the GEMM's K dimension (a row of the K-minor byte tensor).  The rule, for every producer below:
+ *   scale  e = the smallest integer with amax <= 448 * 2^e (amax = the block's max |value|); stored byte = clamp(127 + e, 0, 254).
+ *          An all-zero block gets 127.  A block that holds a NaN or an inf gets 0xFF (E8M0 NaN): every product of the block
+ *          is NaN, so the poison reaches the GEMM output -- the MX form of the per-tensor rule (a non-finite amax poisons the
+ *          tensor's scale and descale, mh_fp8_update_scales).  Rounding the scale UP means no element ever saturates: the OCP
+ *          spec's floor(log2 amax) - 8 puts amax in [256, 512) and clips the top of that binade to 448 (up to 1.75x of the
+ *          largest values lost); ceil(log2(amax / 448)) keeps amax in (224, 448], at the cost of at most one binade of e4m3's
+ *          17 for the block's smallest values.
+ *   elements  e4m3fn(v * 2^-e), round to nearest even (the conversion of the per-tensor quantisers).
+ *   source    every MX copy is the MX quantisation of a BF16 tensor (the bf16 operand the bf16 path would use): the producers
+ *          that fuse the cast (the LayerNorm, the GEMM's c8 copy) quantise their own bf16-ROUNDED output, so each is bit-equal
+ *          to mh_quant_mx_batched applied to that bf16 output.
+ *   layout    scales are a row-major byte matrix [rows, K/32] with leading dimension ld (ld %% 4 == 0: one K step of 128 of a row
+ *          is one aligned u32).  Weights: one flat byte buffer, a weight [N, K] at parameter offset o has its scales as a
+ *          [N, K/32] view at byte o / 32 rounded up to a multiple of 4 (parameters are only 64-element aligned). */
+/* C[M, N] = sum_k (A8[m, k] 2^ea(m, k/32)) (B8[n, k] 2^eb(n, k/32)) with the epilogues of mh_gemm_fp8 (same flags, tiles, size
+ * rule and MH_GEMM_FP8_TILE_* hints): A8 [M, K] and B8 [N, K] OCP e4m3 bytes (K %% 128 == 0, lda / ldb %% 16 == 0, 16-B bases),
+ * sa [M, K/32] / sb [N, K/32] their E8M0 scales (ldsa / ldsb %% 4 == 0, >= K/32, 4-B bases).  No descale factors.  Optional c8
+ * (bf16-output epilogues, N %% 32 == 0): the MX copy of the bf16 output C, c8_scales [M, N/32] (ldc8s %% 4 == 0, >= N/32) --
+ * the next GEMM's A operand (fc1 -> fc2).  No e5m2 operands. */
+int mh_gemm_mx(int M, int N, int K, const void* A8, int lda, const void* sa, int ldsa, const void* B8, int ldb, const void* sb,
+               int ldsb, void* C, int ldc, int flags, const float* bias, const float* res, int ldr, const void* aux_in,
+               void* aux_out, int ldaux, float* colsum, void* c8, int ldc8, void* c8_scales, int ldc8s, void* stream);
+/* MX quantisation, batched (all weight shadows of a step in ONE launch): job = a bf16 source [rows, cols] (row pitch ld_src
+ * elements, %% 4, 8-B base) -> dst e4m3 [rows, cols] (pitch ld_dst bytes, %% 4) + scales [rows, cols/32] (pitch ld_s);
+ * cols %% 32 == 0.  jobs_host: a host copy of the n_jobs jobs, checked before the launch (the kernel reads jobs_device);
+ * items: DEVICE array of job << 32 | chunk (chunks of 128 blocks = 4096 elements, row-major over the job's blocks). */
+typedef struct MhQuantMxJob {
+    const void* src; void* dst; void* scales;
+    int rows, cols, ld_src, ld_dst, ld_s, reserved;
+} MhQuantMxJob;
+int mh_quant_mx_batched(const MhQuantMxJob* jobs_host, int n_jobs, const MhQuantMxJob* jobs_device, const unsigned long* items_device,
+                        int n_items, void* stream);
 /* Byte transposes, batched: dst [cols, rows] = src [rows, cols]^T for every job (rows, cols %% 64 == 0, 16-byte aligned) -- the
  * fp8 dgrad C = dY W needs W^T K-minor ([in, out] for an nn.Linear weight [out, in]): the e4m3 weight shadows are transposed
  * once per optimizer step.  items: DEVICE array of job << 32 | tile (64 x 64-byte tiles, row-major over the source). */
@@ -178,6 +213,12 @@ int mh_layernorm_fwd(const float* x, int x_L, int x_off, const float* gamma, con
 int mh_layernorm_fwd_fp8(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y, int y_L,
                          int y_off, float* mean, float* rstd, int B, int n, int dim, float eps, void* y8,
                          const float* y8_scale, float* y8_amax, void* stream);
+/* The same with the MX copy (see "MX block scaling"): y8 = e4m3 of the BF16 output y in y's row map, y8_scales [rows, dim/32]
+ * in that row map too (row(b, j) * ld_y8s, ld_y8s %% 4 == 0, >= dim/32).  dim %% 32 == 0; y bit-identical to
+ * mh_layernorm_fwd's. */
+int mh_layernorm_fwd_mx(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y, int y_L, int y_off,
+                        float* mean, float* rstd, int B, int n, int dim, float eps, void* y8, void* y8_scales, int ld_y8s,
+                        void* stream);
 /* dx (f32, x's row map) = (dres ? dres : 0) + LN-backward(dy); optional bf16 copy dx_bf16 (operand of the next
  * dgrad/wgrad GEMM).  dgamma/dbeta f32 [dim] are accumulated (+=) through `workspace` (f32,
  * mh_layernorm_bwd_workspace(B*n, dim) floats; per-block partial rows, then a short atomic reduce); dcol f32 [dim]

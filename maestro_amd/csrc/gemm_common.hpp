@@ -17,6 +17,10 @@ struct GemmParams {
     // e4m3 copy of the output scaled by *c8_scale, the operand of the next fp8 GEMM, with max |value| folded into *c8_amax
     const float* descale_a = nullptr; const float* descale_b = nullptr;
     uint8_t* c8 = nullptr; const float* c8_scale = nullptr; float* c8_amax = nullptr; int ldc8 = 0;
+    // MX block scaling (mh_gemm_mx): E8M0 scale matrices of A [M, K/32] and B [N, K/32] (byte extents for the buffer descriptors),
+    // and the [M, N/32] scale matrix of the c8 copy
+    const uint8_t* sa = nullptr; const uint8_t* sb = nullptr; int ldsa = 0, ldsb = 0; unsigned sa_bytes = 0, sb_bytes = 0;
+    uint8_t* c8_scales = nullptr; int ldc8s = 0;
 };
 
 // Output-tile coordinates of raster id `id` (ids already XCD-remapped: every XCD owns a contiguous run).  Ids walk GROUP_M m-tiles
@@ -71,6 +75,34 @@ __device__ __forceinline__ uint32_t pack_e4m3x4(f32x4 v, float s) {   // 4 float
     a = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], a, true);
     return (uint32_t)a;
 }
+// OCP MX block scaling (MXFP8 e4m3; the rule is stated once in include/maestro_hip.h, "MX block scaling"): the E8M0 byte of a
+// 32-element block whose max |value| is `a` (amax_fold order: inf / NaN above every finite value) is 127 + e, e the smallest
+// integer with a <= 448 * 2^e, clamped to [0, 254]; 127 for an all-zero block, 0xFF (NaN) for a non-finite one.  a = m 2^E with
+// m in [1, 2): e = E - 8, plus one when m > 1.75 (448 = 1.75 * 2^8).
+__device__ __forceinline__ uint32_t mx_scale_byte(float a) {
+    const uint32_t u = __float_as_uint(a);
+    if (u >= 0x7f800000u) return 0xffu;
+    if (u == 0u) return 127u;
+    const int eb = (int)(u >> 23);               // biased exponent; 0 (an fp32 subnormal amax) -> byte 0
+    const int b = eb - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return eb == 0 ? 0u : (uint32_t)max(b, 0);
+}
+// the elements' multiplier 2^-e = 2^(127 - byte) (exact: a normal fp32 power of two for every finite block's byte <= 247); 1 for a
+// non-finite block, whose NaN scale byte poisons every product of the block anyway
+__device__ __forceinline__ float mx_inv_scale(uint32_t byte) { return byte == 0xffu ? 1.f : __uint_as_float((254u - byte) << 23); }
+// max |.| over the 2^k lanes of an aligned lane group (xor shuffles 1 .. 2^(k-1)), NaN on top
+template <int LANES>
+__device__ __forceinline__ float group_amax(float v) {
+    uint32_t u = __float_as_uint(v);
+#pragma unroll
+    for (int o = 1; o < LANES; o <<= 1) u = max(u, (uint32_t)__shfl_xor((int)u, o, 64));
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ f32x4 bf2x2_to_f32x4(uint32_t a, uint32_t b) {   // 4 bf16 (two packed words) -> 4 floats
+    return (f32x4){__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u), __uint_as_float(b << 16),
+                   __uint_as_float(b & 0xffff0000u)};
+}
+
 // Fold an absmax (v >= 0 or NaN: the int order of the bits is the float order, NaN on top: see amax_fold) into a slot's amax ROW (MH_FP8_AMAX_PITCH floats).
 // Atomics on one cache line retire at ~10 ns apiece whatever the address inside it (scripts/micro_amax.hip; a look-before-
 // you-add needs an agent-scope load to see other CUs' maxima at all -- plain and nontemporal loads are served stale -- and
@@ -113,7 +145,10 @@ __device__ __forceinline__ f32x4 unpack_dgelu_u8x4(unsigned w) {
 // GELU' / aux): each wave transposes its tile through a private LDS region (passes of 32 rows, 68-float row pitch:
 // conflict-free ds_write_b128 / ds_read_b128) so that the aux reads and the C / aux writes are done in ROW-MAJOR lane
 // order: 8 lanes cover one 128-byte row segment with 16-byte accesses.
-template <int MT, int RP = 32>   // RP = rows per staging pass (32: 32 x 68 floats per wave; 16: half of that)
+// MX (mh_gemm_mx): no descale multiplies (p.descale_a is null), and the c8 copy is block-scaled: the four lanes that hold one
+// 32-column block of a row (l ^ 1, l ^ 2) fold their maxima of the BF16-ROUNDED outputs, so c8 and its scales are exactly the
+// MX quantisation of C (mh_quant_mx_batched applied to C gives the same bytes); lane (l & 3) == 0 writes the scale byte.
+template <int MT, int RP = 32, bool MX = false>   // RP = rows per staging pass (32: 32 x 68 floats per wave; 16: half of that)
 __device__ __forceinline__ void gemm_epilogue_store(const GemmParams& p, const f32x4 (&acc)[4][MT], float* st, int m_base,
                                                     int n_base) {
     constexpr int TPP = RP / 16, NPASS = MT / TPP, SUB = RP / 8;   // m-tiles per pass, passes, 8-row groups per pass
@@ -165,7 +200,8 @@ __device__ __forceinline__ void gemm_epilogue_store(const GemmParams& p, const f
         return;
     }
     f32x4 cs_lo = {0, 0, 0, 0}, cs_hi = {0, 0, 0, 0};   // MH_GEMM_COLSUM: this lane's 8 columns summed over its rows
-    const float s8 = p.c8 ? *p.c8_scale : 0.f;
+    float s8 = 0.f;
+    if constexpr (!MX) s8 = p.c8 ? *p.c8_scale : 0.f;
     float amax8 = 0.f;
     // The saved GELU' bytes (or pre-activations) of ALL passes are requested before the first store (round 5: behind the stores of
     // pass p the compiler could not move the loads of pass p + 1 -- aux_in / C may overlap for all it knows -- and every pass waited
@@ -257,9 +293,20 @@ __device__ __forceinline__ void gemm_epilogue_store(const GemmParams& p, const f
                     u32x4 pk = {pack_bf2(lo[0], lo[1]), pack_bf2(lo[2], lo[3]), pack_bf2(hi[0], hi[1]), pack_bf2(hi[2], hi[3])};
                     *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n) = pk;
                     if (p.c8) {
-                        *reinterpret_cast<u32x2*>(p.c8 + (size_t)m * p.ldc8 + n) = pack_fp8x8(lo, hi, s8, p.flags & MH_GEMM_C8_E5M2);
+                        if constexpr (MX) {
+                            const f32x4 qlo = bf2x2_to_f32x4(pk[0], pk[1]), qhi = bf2x2_to_f32x4(pk[2], pk[3]);
+                            float a = 0.f;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) amax8 = amax_fold(amax_fold(amax8, lo[e]), hi[e]);
+                            for (int e = 0; e < 4; ++e) a = amax_fold(amax_fold(a, qlo[e]), qhi[e]);
+                            const uint32_t sbyte = mx_scale_byte(group_amax<4>(a));   // (all four lanes pass m < M, n < N together)
+                            const float inv = mx_inv_scale(sbyte);
+                            *reinterpret_cast<u32x2*>(p.c8 + (size_t)m * p.ldc8 + n) = (u32x2){pack_e4m3x4(qlo, inv), pack_e4m3x4(qhi, inv)};
+                            if ((l & 3) == 0) p.c8_scales[(size_t)m * p.ldc8s + (n >> 5)] = (uint8_t)sbyte;
+                        } else {
+                            *reinterpret_cast<u32x2*>(p.c8 + (size_t)m * p.ldc8 + n) = pack_fp8x8(lo, hi, s8, p.flags & MH_GEMM_C8_E5M2);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) amax8 = amax_fold(amax_fold(amax8, lo[e]), hi[e]);
+                        }
                     }
                 }
             }
@@ -284,7 +331,7 @@ __device__ __forceinline__ void gemm_epilogue_store(const GemmParams& p, const f
             }
         }
     }
-    if (p.c8 && p.c8_amax) {
+    if (!MX && p.c8 && p.c8_amax) {
         amax8 = wave_amax(amax8);
         if (l == 0 && amax_nonzero(amax8)) atomic_max_pos(p.c8_amax, amax8);
     }

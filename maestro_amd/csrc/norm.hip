@@ -16,7 +16,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                                                      const float* __restrict__ beta, void* __restrict__ y, RowMap ym,
                                                      int y_is_f32, float* __restrict__ mean, float* __restrict__ rstd,
                                                      int B, int n, int dim, float eps, uint8_t* __restrict__ y8,
-                                                     const float* __restrict__ y8_scale, float* __restrict__ y8_amax) {
+                                                     const float* __restrict__ y8_scale, float* __restrict__ y8_amax,
+                                                     uint8_t* __restrict__ y8s, int ld_y8s) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B * n) return;
@@ -44,11 +45,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     const float rs = rsqrtf(wave_sum(q) / dim + eps);
     if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
     const size_t yrow = map_row(ym, b, j) * dim;
-    const float s8 = y8 ? *y8_scale : 0.f;     // fp8 path: an e4m3 copy of the output (the next GEMM's A operand) + its absmax
+    const bool t8 = y8 && !y8s;                // per-tensor e4m3 copy; y8s: the MX copy of the bf16 output (dim %% 32 == 0)
+    const float s8 = t8 ? *y8_scale : 0.f;     // fp8 path: an e4m3 copy of the output (the next GEMM's A operand) + its absmax
     float amax8 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
+        u32x2 pk16 = {0u, 0u};
         if (c < nv) {
             const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
             const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + 4 * c);
@@ -60,15 +63,27 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
             } else {
                 u32x2 pk = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
                 *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(y) + yrow + 4 * c) = pk;
+                pk16 = pk;
             }
-            if (y8) {
+            if (t8) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) amax8 = amax_fold(amax8, o[e]);
                 *reinterpret_cast<uint32_t*>(y8 + yrow + 4 * c) = pack_e4m3x4(o, s8);
             }
         }
+        if (y8s) {      // (every lane: the 8 lanes of a 32-element block are all inside the row or all beyond it)
+            const f32x4 q = bf2x2_to_f32x4(pk16[0], pk16[1]);
+            float a = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a = amax_fold(a, q[e]);
+            const uint32_t sbyte = mx_scale_byte(group_amax<8>(a));
+            if (c < nv) {
+                *reinterpret_cast<uint32_t*>(y8 + yrow + 4 * c) = pack_e4m3x4(q, mx_inv_scale(sbyte));
+                if ((lane & 7) == 0) y8s[map_row(ym, b, j) * ld_y8s + (c >> 3)] = (uint8_t)sbyte;
+            }
+        }
     }
-    if (y8 && y8_amax) {
+    if (t8 && y8_amax) {
         amax8 = wave_amax(amax8);
         if (lane == 0 && amax_nonzero(amax8)) atomic_max_pos(y8_amax, amax8);
     }
@@ -105,15 +120,21 @@ __device__ __forceinline__ float ln_wave_sum(float v) {
     return wave_sum(v);
 #endif
 }
-// FP8 = true (mh_layernorm_fwd_fp8): the same kernel also writes the e4m3 copy of the output (the next GEMM's A operand) and
-// folds |y| into the tensor's amax row; the bf16 output is the SAME instruction sequence, hence bit-identical to FP8 = false.
-template <int NV, bool FP8>
-__global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
+// Y8 = LN_Y8_TENSOR (mh_layernorm_fwd_fp8): the same kernel also writes the e4m3 copy of the output (the next GEMM's A operand)
+// and folds |y| into the tensor's amax row; Y8 = LN_Y8_MX (mh_layernorm_fwd_mx): the MX copy of the BF16 output -- a lane holds
+// 4 consecutive values per i, so 8 lanes hold one 32-element block (3 xor shuffles for its max), lane (l & 7) == 0 writes the
+// scale byte.  The bf16 output is the SAME instruction sequence in all three, hence bit-identical to Y8 = LN_Y8_NONE.  (Other
+// widths with dim %% 32 == 0 -- the small models' 384 -- take the generic ln_fwd_kernel, which writes the MX copy the same way.)
+// (One __device__ body, three kernels: ln_fwd_fast_kernel<NV, FP8> keeps its two instantiations, ln_fwd_fast_mx_kernel<NV> is the third.)
+enum { LN_Y8_NONE = 0, LN_Y8_TENSOR = 1, LN_Y8_MX = 2 };
+template <int NV, int Y8>
+__device__ __forceinline__ void ln_fwd_fast_body(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, bf16_t* __restrict__ y, RowMap ym,
                                                           float* __restrict__ mean, float* __restrict__ rstd, int B, int n,
                                                           float eps, uint8_t* __restrict__ y8, const float* __restrict__ y8_scale,
-                                                          float* __restrict__ y8_amax) {
+                                                          float* __restrict__ y8_amax, uint8_t* __restrict__ y8s, int ld_y8s) {
     constexpr int dim = 256 * NV;
+    constexpr bool FP8 = Y8 == LN_Y8_TENSOR;
     const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B * n) return;
@@ -150,6 +171,15 @@ __global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const float* __restric
         for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mu) * rs * g[i][e] + bt[i][e];
         const u32x2 pk = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
         *reinterpret_cast<u32x2*>(yr + 4 * (lane + 64 * i)) = pk;
+        if constexpr (Y8 == LN_Y8_MX) {
+            const f32x4 q = bf2x2_to_f32x4(pk[0], pk[1]);
+            float a = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a = amax_fold(a, q[e]);
+            const uint32_t sbyte = mx_scale_byte(group_amax<8>(a));
+            *reinterpret_cast<uint32_t*>(y8 + yrow + 4 * (lane + 64 * i)) = pack_e4m3x4(q, mx_inv_scale(sbyte));
+            if ((lane & 7) == 0) y8s[map_row(ym, b, j) * ld_y8s + ((lane + 64 * i) >> 3)] = (uint8_t)sbyte;
+        }
         if constexpr (FP8) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) amax8 = amax_fold(amax8, o[e]);
@@ -163,6 +193,23 @@ __global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const float* __restric
             if (lane == 0 && amax_nonzero(amax8)) atomic_max_pos(y8_amax, amax8);
         }
     }
+}
+template <int NV, bool FP8>
+__global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, bf16_t* __restrict__ y, RowMap ym,
+                                                          float* __restrict__ mean, float* __restrict__ rstd, int B, int n,
+                                                          float eps, uint8_t* __restrict__ y8, const float* __restrict__ y8_scale,
+                                                          float* __restrict__ y8_amax) {
+    ln_fwd_fast_body<NV, FP8 ? LN_Y8_TENSOR : LN_Y8_NONE>(x, xm, gamma, beta, y, ym, mean, rstd, B, n, eps, y8, y8_scale, y8_amax,
+                                                          nullptr, 0);
+}
+template <int NV>
+__global__ __launch_bounds__(256) void ln_fwd_fast_mx_kernel(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, bf16_t* __restrict__ y, RowMap ym,
+                                                             float* __restrict__ mean, float* __restrict__ rstd, int B, int n,
+                                                             float eps, uint8_t* __restrict__ y8, uint8_t* __restrict__ y8s,
+                                                             int ld_y8s) {
+    ln_fwd_fast_body<NV, LN_Y8_MX>(x, xm, gamma, beta, y, ym, mean, rstd, B, n, eps, y8, nullptr, nullptr, y8s, ld_y8s);
 }
 
 // Backward. Each wave walks ROWS_PER_WAVE rows keeping per-column partials of dgamma, dbeta and colsum(dx) in
@@ -435,25 +482,36 @@ static int ln_nv(int dim) { const int v = (dim / 4 + 63) / 64; return v <= 4 ? v
 
 static int layernorm_fwd_impl(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y, int y_L,
                               int y_off, int y_is_f32, float* mean, float* rstd, int B, int n, int dim, float eps, void* y8,
-                              const float* y8_scale, float* y8_amax, void* stream);
+                              const float* y8_scale, float* y8_amax, void* stream, void* y8s, int ld_y8s);
 
 extern "C" int mh_layernorm_fwd(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y,
                                 int y_L, int y_off, int y_is_f32, float* mean, float* rstd, int B, int n, int dim,
                                 float eps, void* stream) {
     return layernorm_fwd_impl(x, x_L, x_off, gamma, beta, y, y_L, y_off, y_is_f32, mean, rstd, B, n, dim, eps, nullptr, nullptr,
-                              nullptr, stream);
+                              nullptr, stream, nullptr, 0);
 }
 
 extern "C" int mh_layernorm_fwd_fp8(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y,
                                     int y_L, int y_off, float* mean, float* rstd, int B, int n, int dim, float eps, void* y8,
                                     const float* y8_scale, float* y8_amax, void* stream) {
     MH_CHECK_ARG(y8 && y8_scale && ((uintptr_t)y8 % 4) == 0, "mh_layernorm_fwd_fp8: y8 (4-byte aligned) and its scale are required");
-    return layernorm_fwd_impl(x, x_L, x_off, gamma, beta, y, y_L, y_off, 0, mean, rstd, B, n, dim, eps, y8, y8_scale, y8_amax, stream);
+    return layernorm_fwd_impl(x, x_L, x_off, gamma, beta, y, y_L, y_off, 0, mean, rstd, B, n, dim, eps, y8, y8_scale, y8_amax, stream,
+                              nullptr, 0);
+}
+
+extern "C" int mh_layernorm_fwd_mx(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y, int y_L,
+                                   int y_off, float* mean, float* rstd, int B, int n, int dim, float eps, void* y8, void* y8_scales,
+                                   int ld_y8s, void* stream) {
+    MH_CHECK_ARG(y8 && ((uintptr_t)y8 % 4) == 0, "mh_layernorm_fwd_mx: y8 (4-byte aligned) is required");
+    MH_CHECK_ARG(y8_scales, "mh_layernorm_fwd_mx: null scale pointer (y8_scales)");
+    MH_CHECK_ARG(ld_y8s % 4 == 0 && ld_y8s >= dim / 32, "mh_layernorm_fwd_mx: ld_y8s must be a multiple of 4 and >= dim / 32 (%d)", ld_y8s);
+    return layernorm_fwd_impl(x, x_L, x_off, gamma, beta, y, y_L, y_off, 0, mean, rstd, B, n, dim, eps, y8, nullptr, nullptr, stream,
+                              y8_scales, ld_y8s);
 }
 
 static int layernorm_fwd_impl(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y, int y_L,
                               int y_off, int y_is_f32, float* mean, float* rstd, int B, int n, int dim, float eps, void* y8,
-                              const float* y8_scale, float* y8_amax, void* stream) {
+                              const float* y8_scale, float* y8_amax, void* stream, void* y8s, int ld_y8s) {
     MH_CHECK_ARG(x && gamma && beta && y && mean && rstd, "mh_layernorm_fwd: null pointer");
     MH_CHECK_ARG(dim % 4 == 0 && dim >= 4 && dim <= 2048, "mh_layernorm_fwd: dim %d unsupported", dim);
     MH_CHECK_ARG(B > 0 && n > 0 && x_off + n <= x_L && y_off + n <= y_L, "mh_layernorm_fwd: bad row map");
@@ -461,11 +519,15 @@ static int layernorm_fwd_impl(const float* x, int x_L, int x_off, const float* g
     dim3 grid(ceil_div(rows, 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
 #define LN_FWD(NV) hipLaunchKernelGGL(ln_fwd_kernel<NV>, grid, block, 0, s, x, RowMap{x_L, x_off}, gamma, beta, y, \
-                                      RowMap{y_L, y_off}, y_is_f32, mean, rstd, B, n, dim, eps, (uint8_t*)y8, y8_scale, y8_amax)
+                                      RowMap{y_L, y_off}, y_is_f32, mean, rstd, B, n, dim, eps, (uint8_t*)y8, y8_scale, y8_amax, \
+                                      (uint8_t*)y8s, ld_y8s)
 #define LN_FWD_FAST_(NV, FP8) hipLaunchKernelGGL((ln_fwd_fast_kernel<NV, FP8>), grid, block, 0, s, x, RowMap{x_L, x_off}, gamma, beta, \
                                                  (bf16_t*)y, RowMap{y_L, y_off}, mean, rstd, B, n, eps, (uint8_t*)y8, y8_scale, y8_amax)
-#define LN_FWD_FAST(NV) do { if (y8) LN_FWD_FAST_(NV, true); else LN_FWD_FAST_(NV, false); } while (0)
+#define LN_FWD_FAST_MX(NV) hipLaunchKernelGGL((ln_fwd_fast_mx_kernel<NV>), grid, block, 0, s, x, RowMap{x_L, x_off}, gamma, beta, \
+                                              (bf16_t*)y, RowMap{y_L, y_off}, mean, rstd, B, n, eps, (uint8_t*)y8, (uint8_t*)y8s, ld_y8s)
+#define LN_FWD_FAST(NV) do { if (y8s) LN_FWD_FAST_MX(NV); else if (y8) LN_FWD_FAST_(NV, true); else LN_FWD_FAST_(NV, false); } while (0)
     const int nvs = ln_nv(dim);
+    MH_CHECK_ARG(!y8s || (dim % 32 == 0 && !y_is_f32), "mh_layernorm_fwd_mx: dim %% 32 == 0 required, got %d", dim);
     if (MH_LN_FAST && nvs <= 4 && dim == 256 * nvs && !y_is_f32) {     // the step's own case: straight-line kernel (with or without the e4m3 copy)
         switch (nvs) { case 1: LN_FWD_FAST(1); break; case 2: LN_FWD_FAST(2); break; case 3: LN_FWD_FAST(3); break;
                        default: LN_FWD_FAST(4); }
@@ -474,6 +536,7 @@ static int layernorm_fwd_impl(const float* x, int x_L, int x_off, const float* g
                        case 4: LN_FWD(4); break; default: LN_FWD(8); }
     }
 #undef LN_FWD_FAST
+#undef LN_FWD_FAST_MX
 #undef LN_FWD_FAST_
 #undef LN_FWD
     MH_LAUNCH_CHECK();

@@ -115,7 +115,58 @@ __global__ __launch_bounds__(256) void transpose_u8_kernel(const MhTransposeJob*
     *reinterpret_cast<u32x4*>(dst + (size_t)(tc * 64 + r) * jb.rows + tr * 64 + 16 * q) = w;
 }
 
+// MX quantisation (mh_quant_mx_batched): a bf16 [rows, cols] source -> e4m3 bytes + one E8M0 scale per 32-element block along a
+// row (the rule: mx_scale_byte, gemm_common.hpp).  Eight lanes per block, four elements per lane (8-byte loads, a wave covers 256
+// consecutive elements of a row), block max by 3 xor shuffles; lane (l & 7) == 0 writes the scale byte.
+constexpr int MX_CHUNK_BLOCKS = 128;   // blocks per work item (4096 elements; 4 passes of 32 blocks per 256-thread workgroup)
+
+__global__ __launch_bounds__(256) void quant_mx_kernel(const MhQuantMxJob* __restrict__ jobs, const uint64_t* __restrict__ items) {
+    const uint64_t it = items[blockIdx.x];
+    const MhQuantMxJob jb = jobs[it >> 32];
+    const int nb = jb.cols >> 5;
+    const long nblk = (long)jb.rows * nb;
+    const int q = threadIdx.x & 7;
+#pragma unroll
+    for (int pass = 0; pass < MX_CHUNK_BLOCKS / 32; ++pass) {
+        const long blk = (long)(uint32_t)it * MX_CHUNK_BLOCKS + pass * 32 + (threadIdx.x >> 3);
+        const bool ok = blk < nblk;     // (eight lanes of one block agree; the shuffles below run on every lane)
+        const int r = ok ? (int)(blk / nb) : 0, cb = ok ? (int)(blk - (long)r * nb) : 0;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (ok) {
+            const u32x2 pk = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(jb.src) + (size_t)r * jb.ld_src + 32 * cb + 4 * q);
+            v = bf2x2_to_f32x4(pk[0], pk[1]);
+        }
+        float a = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a = amax_fold(a, v[e]);
+        const uint32_t sbyte = mx_scale_byte(group_amax<8>(a));
+        if (ok) {
+            *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(jb.dst) + (size_t)r * jb.ld_dst + 32 * cb + 4 * q) =
+                pack_e4m3x4(v, mx_inv_scale(sbyte));
+            if (q == 0) reinterpret_cast<uint8_t*>(jb.scales)[(size_t)r * jb.ld_s + cb] = (uint8_t)sbyte;
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int mh_quant_mx_batched(const MhQuantMxJob* jobs_host, int n_jobs, const MhQuantMxJob* jobs_device,
+                                   const unsigned long* items_device, int n_items, void* stream) {
+    MH_CHECK_ARG(jobs_host && n_jobs > 0, "mh_quant_mx_batched: the host copy of the job table is required");
+    for (int i = 0; i < n_jobs; ++i) {
+        const MhQuantMxJob& j = jobs_host[i];
+        MH_CHECK_ARG(j.src && j.dst && j.scales, "mh_quant_mx_batched: job %d: null src / dst / scales", i);
+        MH_CHECK_ARG(j.rows > 0 && j.cols > 0 && j.cols % 32 == 0, "mh_quant_mx_batched: job %d: cols %% 32 == 0 required (%d)", i, j.cols);
+        MH_CHECK_ARG(j.ld_src >= j.cols && j.ld_src % 4 == 0 && j.ld_dst >= j.cols && j.ld_dst % 4 == 0 && j.ld_s >= j.cols / 32,
+                     "mh_quant_mx_batched: job %d: ld_src / ld_dst must be >= cols and multiples of 4, ld_s >= cols / 32", i);
+        MH_CHECK_ARG((uintptr_t)j.src % 8 == 0 && (uintptr_t)j.dst % 4 == 0, "mh_quant_mx_batched: job %d: src 8-B, dst 4-B aligned", i);
+    }
+    MH_CHECK_ARG(jobs_device && items_device && n_items > 0, "mh_quant_mx_batched: bad arguments");
+    hipLaunchKernelGGL(quant_mx_kernel, dim3(n_items), dim3(256), 0, (hipStream_t)stream, jobs_device,
+                       reinterpret_cast<const uint64_t*>(items_device));
+    MH_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int mh_transpose_u8_batched(const MhTransposeJob* jobs_device, const unsigned long* items_device, int n_items, void* stream) {
     MH_CHECK_ARG(jobs_device && items_device && n_items > 0, "mh_transpose_u8_batched: bad arguments");

@@ -27,6 +27,7 @@ import torch
 from torch import nn
 
 from maestro_amd import hip
+from maestro_amd.fp8 import mx_scale_cols, resolve_scaling
 from maestro_amd.layers.utils import draw_struct_masks
 
 F32, BF16, I32, U8 = torch.float32, torch.bfloat16, torch.int32, torch.uint8
@@ -175,11 +176,14 @@ class Stack:
                 d = dict(h1=e(M, dim, dt=U8), o=e(M, self.inner, dt=U8), h2=e(M, dim, dt=U8), act=e(M, mlp, dt=U8),
                          s_h1=plan.add_activation(), s_o=plan.add_activation(), s_h2=plan.add_activation(),
                          s_act=plan.add_activation())
+                if plan.scaling == "mx":     # E8M0 scales [M, cols / 32] of the four copies (row pitch a multiple of 4 bytes)
+                    for key, cols in (("h1", dim), ("o", self.inner), ("h2", dim), ("act", mlp)):
+                        d["mx_" + key] = e(M, mx_scale_cols(cols), dt=U8)[:, : cols // 32]
                 for key, lin in (("qkv", attn.to_qkv), ("proj", attn.to_out[0]), ("fc1", ff.net[1]), ("fc2", ff.net[4])):
                     cache = eng._fp8_weights.get(id(lin.weight))
                     if cache is None:        # a holder shared by several groups registers its weights once
                         off = eng.store.offset[id(lin.weight)]
-                        w8, slot = plan.add_weight(lin.weight.data, off)
+                        w8, slot = plan.add_weight(lin.weight.data, off, half=eng.store.h(lin.weight))
                         cache = eng._fp8_weights[id(lin.weight)] = (w8, slot, plan.add_transposed(w8, off))
                     d["w_" + key], d["sw_" + key], d["wt_" + key] = cache
                 # fp8 dgrad: e5m2 copies of the four gradient operands (d layer output, d attention residual, d fc1-out, d qkv)
@@ -234,10 +238,32 @@ class Stack:
 
     def _forward_layer_fp8(self, l, attn, ff, s, x_in, x_mid, x_out) -> None:
         """The layer's forward with e4m3 GEMM operands (bf16 copies of the activations are still written: the backward reads
-        them).  Same kernels otherwise; the GELU output's e4m3 copy comes straight out of the fc1 epilogue."""
+        them).  Same kernels otherwise; the GELU output's e4m3 copy comes straight out of the fc1 epilogue.  ``plan.scaling``
+        "mx": the same seven launches with block-scaled copies (E8M0 scales next to each e4m3 copy, no descales, no amax)."""
         eng, M, dim, mlp, inner = self.eng, self.M, self.dim, self.mlp, self.inner  # noqa: N806
         plan, f = eng.fp8, self.f8[l]
         proj, ln2, fc1, fc2 = attn.to_out[0], ff.net[0], ff.net[1], ff.net[4]
+        fc1_flags = hip.BIAS | hip.GELU | hip.AUX_DGELU | eng.aux_flag
+        res_flags = hip.OUT_F32 | hip.BIAS | hip.RESIDUAL
+        if plan.scaling == "mx":
+            ws = plan.w_scales
+            ld = lambda t: t.stride(0)  # noqa: E731
+            hip.layernorm_fwd_mx(x_in, M, 0, attn.norm.weight, attn.norm.bias, s["h1"], M, 0, s["mean1"], s["rstd1"], 1, M, dim,
+                                 f["h1"], f["mx_h1"], ld(f["mx_h1"]))
+            hip.gemm_mx(M, 3 * inner, dim, f["h1"], dim, f["mx_h1"], ld(f["mx_h1"]), f["w_qkv"], dim, ws(f["sw_qkv"]), dim // 32,
+                        s["qkv"], 3 * inner)
+            hip.attn_fwd(s["qkv"], s["o"], s["lse"], self.Bn, self.N, self.H, self.Dh, attn.scale)
+            plan.quantize_mx(s["o"], f["o"], f["mx_o"])
+            hip.gemm_mx(M, dim, inner, f["o"], inner, f["mx_o"], ld(f["mx_o"]), f["w_proj"], inner, ws(f["sw_proj"]), inner // 32,
+                        x_mid, dim, flags=res_flags, bias=proj.bias, res=x_in, ldr=dim)
+            hip.layernorm_fwd_mx(x_mid, M, 0, ln2.weight, ln2.bias, s["h2"], M, 0, s["mean2"], s["rstd2"], 1, M, dim, f["h2"],
+                                 f["mx_h2"], ld(f["mx_h2"]))
+            hip.gemm_mx(M, mlp, dim, f["h2"], dim, f["mx_h2"], ld(f["mx_h2"]), f["w_fc1"], dim, ws(f["sw_fc1"]), dim // 32,
+                        s["act"], mlp, flags=fc1_flags, bias=fc1.bias, aux_out=s["hpre"], ldaux=mlp, c8=f["act"], ldc8=mlp,
+                        c8_scales=f["mx_act"], ldc8s=ld(f["mx_act"]))
+            hip.gemm_mx(M, dim, mlp, f["act"], mlp, f["mx_act"], ld(f["mx_act"]), f["w_fc2"], mlp, ws(f["sw_fc2"]), mlp // 32,
+                        x_out, dim, flags=res_flags, bias=fc2.bias, res=x_mid, ldr=dim)
+            return
         hip.layernorm_fwd_fp8(x_in, M, 0, attn.norm.weight, attn.norm.bias, s["h1"], M, 0, s["mean1"], s["rstd1"], 1, M, dim,
                               f["h1"], plan.a_scale(f["s_h1"]), plan.a_amax(f["s_h1"]))
         hip.gemm_fp8(M, 3 * inner, dim, f["h1"], dim, f["w_qkv"], dim, s["qkv"], 3 * inner, plan.a_descale(f["s_h1"]),
@@ -247,14 +273,14 @@ class Stack:
         # cost that VALU-bound kernel +50 % -- 0.91 -> 1.36 ms per C5 step -- against ~0.1 ms for the separate passes)
         plan.quantize(s["o"], f["o"], f["s_o"])
         hip.gemm_fp8(M, dim, inner, f["o"], inner, f["w_proj"], inner, x_mid, dim, plan.a_descale(f["s_o"]),
-                     plan.w_descale(f["sw_proj"]), flags=hip.OUT_F32 | hip.BIAS | hip.RESIDUAL, bias=proj.bias, res=x_in, ldr=dim)
+                     plan.w_descale(f["sw_proj"]), flags=res_flags, bias=proj.bias, res=x_in, ldr=dim)
         hip.layernorm_fwd_fp8(x_mid, M, 0, ln2.weight, ln2.bias, s["h2"], M, 0, s["mean2"], s["rstd2"], 1, M, dim, f["h2"],
                               plan.a_scale(f["s_h2"]), plan.a_amax(f["s_h2"]))
         hip.gemm_fp8(M, mlp, dim, f["h2"], dim, f["w_fc1"], dim, s["act"], mlp, plan.a_descale(f["s_h2"]),
-                     plan.w_descale(f["sw_fc1"]), flags=hip.BIAS | hip.GELU | hip.AUX_DGELU | eng.aux_flag, bias=fc1.bias, aux_out=s["hpre"],
+                     plan.w_descale(f["sw_fc1"]), flags=fc1_flags, bias=fc1.bias, aux_out=s["hpre"],
                      ldaux=mlp, c8=f["act"], ldc8=mlp, c8_scale=plan.a_scale(f["s_act"]), c8_amax=plan.a_amax(f["s_act"]))
         hip.gemm_fp8(M, dim, mlp, f["act"], mlp, f["w_fc2"], mlp, x_out, dim, plan.a_descale(f["s_act"]),
-                     plan.w_descale(f["sw_fc2"]), flags=hip.OUT_F32 | hip.BIAS | hip.RESIDUAL, bias=fc2.bias, res=x_mid, ldr=dim)
+                     plan.w_descale(f["sw_fc2"]), flags=res_flags, bias=fc2.bias, res=x_mid, ldr=dim)
 
     def reduce_jobs(self, lo: int = 0, hi: int | None = None) -> list:
         """``hip.ColsumBatch`` jobs of layers ``lo .. hi-1`` after a ``backward(defer=True)``: the LayerNorm partial rows
@@ -654,11 +680,16 @@ class EngineBase:
 
 # ======================================================================================= the engine
 class MAEEngine(EngineBase):
-    def __init__(self, model, batch_size: int, device, loss: str = "l2_norm", dtype: str = "bf16") -> None:
+    def __init__(self, model, batch_size: int, device, loss: str = "l2_norm", dtype: str = "bf16",
+                 fp8_scaling: str | None = None) -> None:
+        """``fp8_scaling`` (dtype "fp8" only): "tensor" (per-tensor delayed scaling) or "mx" (OCP MX block scales); None reads
+        ``MAESTRO_FP8_SCALING`` (default "tensor").  A numeric-format choice like ``dtype`` (maestro_amd/fp8.py)."""
         if loss not in ("l1", "l2", "l1_norm", "l2_norm"):
             raise ValueError(f"Invalid loss {loss}.")
         if dtype not in ("bf16", "fp8"):
             raise ValueError(f"Invalid compute dtype {dtype!r} (bf16, fp8)")
+        scaling = resolve_scaling(fp8_scaling)         # (before the device check: a bad value is a ValueError on any machine)
+        self.fp8_scaling = scaling if dtype == "fp8" else None
         device = torch.device(device)
         if device.type != "cuda":
             raise hip.HipExtensionError("MAEEngine needs a GPU device; the MAE hot path has no CPU fallback")
@@ -712,7 +743,7 @@ class MAEEngine(EngineBase):
             setattr(m, bname, getattr(m, bname).to(device))
         if dtype == "fp8":
             from maestro_amd.fp8 import Fp8Plan
-            self.fp8 = Fp8Plan(device, self.store.total)
+            self.fp8 = Fp8Plan(device, self.store.total, scaling=self.fp8_scaling)
         self._alloc()
         self._alloc_mask_upload()
         if self.fp8 is not None:

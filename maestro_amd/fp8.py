@@ -20,6 +20,19 @@ Scaling (all state on the device, nothing is read by the host, capturable in the
                  e4m3 copy itself); the first step runs with scale 1;
   * gradients:   delayed scaling as well, but a gradient's magnitude is not O(1): the FIRST backward runs its dgrads in bf16 and
                  only records the absmax of every gradient tensor (calibration), fp8 dgrads start with the second step.
+
+Two scaling modes (``MAEEngine(..., dtype="fp8", fp8_scaling=...)``, default from ``MAESTRO_FP8_SCALING``):
+  * ``tensor`` (default): the per-tensor delayed scaling above;
+  * ``mx``: OCP MX block scaling (MXFP8) -- one E8M0 scale per 32 consecutive elements along K, applied by the scaled MFMA itself
+    (``mh_gemm_mx``; the rule is written once in include/maestro_hip.h, "MX block scaling").  Every MX copy is the MX
+    quantisation of the bf16 tensor the bf16 path uses: the LayerNorm's bf16 output (``mh_layernorm_fwd_mx``), the fc1
+    epilogue's bf16 GELU output (its c8 copy), the attention output (``mh_quant_mx_batched``) and the weights' bf16 shadows
+    (ONE ``mh_quant_mx_batched`` launch over all weights after every change of the shadows).  No scale state: step t's numerics
+    depend on step t's tensors only -- no amax tables, no calibration step, no warm-up of scales.  The optimizer runs the plain
+    ``mh_adamw`` (no fused MX AdamW) and the weight shadows are re-quantised from the bf16 shadows behind it.  The e5m2 dgrads
+    (``MAESTRO_FP8_DGRAD``) do not exist in this mode.  Weight scales live in one flat byte buffer, a weight [N, K] at offset
+    ``o`` of the parameter buffer has its [N, K/32] scales at byte ``ceil4(o / 32)`` (parameters are 64-element aligned; the GEMM
+    reads one aligned u32 per row and K step).
 """
 
 from __future__ import annotations
@@ -31,12 +44,30 @@ import torch
 from maestro_amd import hip
 
 U8 = torch.uint8
+SCALINGS = ("tensor", "mx")
+
+
+def resolve_scaling(fp8_scaling: str | None) -> str:
+    """``fp8_scaling`` or, when None, ``MAESTRO_FP8_SCALING`` (default "tensor"); ValueError for anything but tensor / mx."""
+    val = os.environ.get("MAESTRO_FP8_SCALING", "tensor") if fp8_scaling is None else fp8_scaling
+    if val not in SCALINGS:
+        raise ValueError(f"Invalid fp8 scaling {val!r} (fp8_scaling / MAESTRO_FP8_SCALING: tensor, mx)")
+    return val
+
+
+def mx_scale_cols(cols: int) -> int:
+    """Row pitch (bytes) of an MX scale matrix for ``cols`` elements per row: cols / 32 rounded up to a multiple of 4."""
+    return -(-(cols // 32) // 4) * 4
 
 
 class Fp8Plan:
-    def __init__(self, device, total: int = 0) -> None:
+    def __init__(self, device, total: int = 0, scaling: str = "tensor") -> None:
         """``total``: element count of the engine's flat parameter buffer -- the e4m3 weight shadows live in ONE flat uint8
-        buffer with the same offsets, so that the fused AdamW (``mh_adamw_fp8``) can refresh them in its own pass."""
+        buffer with the same offsets, so that the fused AdamW (``mh_adamw_fp8``) can refresh them in its own pass.
+        ``scaling``: "tensor" (per-tensor delayed scaling) or "mx" (OCP MX block scales, see the module docstring)."""
+        if scaling not in SCALINGS:
+            raise ValueError(f"Invalid fp8 scaling {scaling!r} (tensor, mx)")
+        self.scaling = scaling
         self.device = device
         self.w8_flat = torch.zeros(max(total, 4), dtype=U8, device=device)
         self._slot_map = torch.full(((max(total, 64) + 63) // 64,), -1, dtype=torch.int16)
@@ -48,6 +79,12 @@ class Fp8Plan:
         self._abatch: dict = {}
         # fp8 dgrad: transposed weight shadows (same offsets in a second flat buffer) and e5m2 gradient slots
         self.dgrad = os.environ.get("MAESTRO_FP8_DGRAD", "0") == "1"
+        if self.dgrad and scaling == "mx":
+            raise ValueError("MAESTRO_FP8_DGRAD=1 is not available with fp8_scaling='mx' (an MX dgrad needs transposed weight "
+                             "shadows with scales along `out`); unset MAESTRO_FP8_DGRAD or use fp8_scaling='tensor'")
+        # mx: E8M0 weight scales, one flat byte buffer (weight at parameter offset o -> byte ceil4(o / 32)), one batched quantiser
+        self.ws_flat = torch.zeros(max(total, 64) // 32 + 8 if scaling == "mx" else 4, dtype=U8, device=device)
+        self._w_scales, self._mxbatch, self._mx_act = {}, None, {}
         self.w8t_flat = torch.zeros(max(total, 4) if self.dgrad else 4, dtype=U8, device=device)
         self._t_pairs, self._tbatch = [], None
         self.grad_ready = False          # True once a backward has left the absmax of every gradient slot behind
@@ -57,17 +94,28 @@ class Fp8Plan:
     def eligible(K: int) -> bool:  # noqa: N803
         return K % 128 == 0 and K >= 128
 
-    def add_weight(self, master: torch.Tensor, offset: int):
+    def add_weight(self, master: torch.Tensor, offset: int, half: torch.Tensor | None = None):
         """``master``: the fp32 parameter view [N, K] at ``offset`` of the flat buffer -> (e4m3 shadow uint8 [N, K], a view of
-        ``w8_flat`` at the same offset; scale slot)."""
+        ``w8_flat`` at the same offset; scale slot).  ``half``: its bf16 shadow (the source of the MX copy; mx mode only), whose
+        E8M0 scales are then ``w_scales(slot)``."""
         n = master.numel()
         w8 = self.w8_flat[offset: offset + n].view(master.shape)
         slot = len(self._w_jobs)
         if slot > 32767 or offset % 64:
             raise hip.HipExtensionError("Fp8Plan: too many weights for the int16 slot map / parameter not 64-element aligned")
         self._slot_map[offset // 64: (offset + n + 63) // 64] = slot
-        self._w_jobs.append(dict(src=master, dst=w8, slot=slot, format=hip.FP8_E4M3))
+        if self.scaling == "mx":
+            rows, cols = master.shape
+            so = -(-(offset // 32) // 4) * 4     # (the regions stay disjoint: n / 32 is a multiple of 4 for K % 128 == 0)
+            self._w_scales[slot] = self.ws_flat[so: so + n // 32].view(rows, cols // 32)
+            self._w_jobs.append(dict(src=half, dst=w8, scales=self._w_scales[slot], slot=slot))
+        else:
+            self._w_jobs.append(dict(src=master, dst=w8, slot=slot, format=hip.FP8_E4M3))
         return w8, slot
+
+    def w_scales(self, slot: int) -> torch.Tensor:
+        """mx: the E8M0 scales [N, K/32] of weight ``slot``."""
+        return self._w_scales[slot]
 
     def add_transposed(self, w8: torch.Tensor, offset: int):
         """``w8`` [out, in] (a shadow returned by ``add_weight``) -> its transposed shadow [in, out] (the K-minor B operand of the
@@ -94,7 +142,9 @@ class Fp8Plan:
         if self._t_pairs:
             self._tbatch = hip.TransposeBatch(self._t_pairs, self.device)
         self.slot_map = self._slot_map.to(self.device)
-        if self._w_jobs:
+        if self._w_jobs and self.scaling == "mx":
+            self._mxbatch = hip.QuantMxBatch(self._w_jobs, self.device)
+        elif self._w_jobs:
             self._wbatch = hip.QuantBatch(self._w_jobs, self.wsc, self.device)
 
     # ---- per step
@@ -102,7 +152,12 @@ class Fp8Plan:
         """e4m3 shadows of every registered weight (call after the fp32 masters changed).  The first call (and ``exact``:
         parameters replaced wholesale, e.g. a checkpoint load) runs ``absmax -> scales -> cast`` (three passes); afterwards
         weights move by a learning-rate step at a time, so ONE pass casts with the scales derived from the previous call's
-        absmax and records the new absmax (delayed scaling with one binade of head-room; 5 instead of 9 bytes per weight)."""
+        absmax and records the new absmax (delayed scaling with one binade of head-room; 5 instead of 9 bytes per weight).
+        mx: ONE launch re-quantises every shadow from the bf16 shadows (no state: ``exact`` changes nothing)."""
+        if self._mxbatch is not None:
+            self._mxbatch.launch()
+            self._w_ready = True
+            return
         if self._wbatch is None:
             return
         if exact or not self._w_ready:
@@ -125,7 +180,7 @@ class Fp8Plan:
         """The fused AdamW (``mh_adamw_fp8``) refreshes the shadows in its own pass (5 -> 0 extra bytes per weight): derive this
         step's scales from the previous absmax first.  False while the scales are not initialised (the caller then falls back
         to ``refresh_weights`` after a plain update)."""
-        if self._wbatch is None or not self._w_ready:
+        if self._wbatch is None or not self._w_ready:     # (mx: never -- plain AdamW, then refresh_weights)
             return False
         self.wsc.update(fmt=hip.FP8_E4M3, margin=1)
         return True
@@ -138,6 +193,14 @@ class Fp8Plan:
             qb = self._abatch[key] = hip.QuantBatch([dict(src=src, dst=dst, slot=slot, format=hip.FP8_E4M3)], self.asc, self.device)
         qb.launch(2)
 
+    def quantize_mx(self, src: torch.Tensor, dst: torch.Tensor, scales: torch.Tensor) -> None:
+        """mx: activation cast of a bf16 [rows, cols] tensor to e4m3 + E8M0 block scales (no state)."""
+        key = (src.data_ptr(), dst.data_ptr(), scales.data_ptr())
+        qb = self._mx_act.get(key)
+        if qb is None:
+            qb = self._mx_act[key] = hip.QuantMxBatch([dict(src=src, dst=dst, scales=scales)], self.device)
+        qb.launch()
+
     def quantize_grad(self, src: torch.Tensor, dst: torch.Tensor, slot: int) -> None:
         """Gradient cast to e5m2 with the current scale of gradient ``slot`` + absmax for the next step; while the scales are
         not calibrated (``grad_ready`` False) only the absmax is recorded."""
@@ -149,13 +212,13 @@ class Fp8Plan:
 
     def end_of_backward(self) -> None:
         """Derive the next step's gradient scales from this backward's absmax values (e5m2: 57344 / amax, one binade of margin)."""
-        if self._n_grad and self.dgrad:
+        if self._n_grad and self.dgrad and self.scaling == "tensor":
             self.gsc.update(fmt=hip.FP8_E5M2, margin=1)
             self.grad_ready = True
 
     def end_of_forward(self) -> None:
-        """Derive the next step's activation scales from this step's absmax values."""
-        if self._n_act:
+        """Derive the next step's activation scales from this step's absmax values (mx: nothing, no scale state)."""
+        if self._n_act and self.scaling == "tensor":
             self.asc.update(fmt=hip.FP8_E4M3, margin=1)
 
     def a_scale(self, slot):

@@ -361,6 +361,12 @@ def layernorm_fwd_fp8(x, x_L, x_off, gamma, beta, y, y_L, y_off, mean, rstd, B, 
          _F(eps), y8, y8_scale, y8_amax)
 
 
+def layernorm_fwd_mx(x, x_L, x_off, gamma, beta, y, y_L, y_off, mean, rstd, B, n, dim, y8, y8_scales, ld_y8s, eps=1e-5):
+    """LayerNorm forward writing the bf16 output AND its MX copy (e4m3 ``y8`` + E8M0 ``y8_scales`` [rows, dim/32], pitch ``ld_y8s``)."""
+    call("mh_layernorm_fwd_mx", x, _I(x_L), _I(x_off), gamma, beta, y, _I(y_L), _I(y_off), mean, rstd, _I(B), _I(n), _I(dim),
+         _F(eps), y8, y8_scales, _I(ld_y8s))
+
+
 def layernorm_bwd_workspace(rows, dim) -> int:
     f = lib().mh_layernorm_bwd_workspace
     f.restype = ctypes.c_long
@@ -946,3 +952,70 @@ class QuantBatch:
 
     def launch(self, mode: int) -> None:
         call("mh_quant_batched", self.table, self.items, _I(self.n_items), self.scales.scale, self.scales.amax, _I(mode))
+
+
+# ------------------------------------------------------------------------------------------------ MX block scaling (fp8 `mx`)
+MX_BLOCK = 32          # elements per E8M0 scale along K
+MX_CHUNK = 4096        # elements per work item of mh_quant_mx_batched (csrc/quant.hip)
+
+
+def gemm_mx(M, N, K, A8, lda, sa, ldsa, B8, ldb, sb, ldsb, C, ldc, flags=0, bias=None, res=None, ldr=0,  # noqa: N803
+            aux_in=None, aux_out=None, ldaux=0, colsum=None, c8=None, ldc8=0, c8_scales=None, ldc8s=0) -> None:
+    """``C = (A8 x 2^sa) @ (B8 x 2^sb)^T`` (+ epilogue): e4m3 A8 ``[M, K]`` / B8 ``[N, K]`` uint8 with E8M0 scales ``[M, K/32]`` /
+    ``[N, K/32]``; ``c8`` / ``c8_scales``: the MX copy of the bf16 output.  Timed as ``gemm_fp8_kernel`` (same kernel body)."""
+    ev = None
+    if _timer is not None:
+        ev = _timer.record("gemm_fp8_kernel", 2.0 * M * N * K, (M, N, K))
+        ev[0].record()
+    flags |= _FP8_TILE_HINT.get(os.environ.get("MH_FP8_TILE", ""), 0)      # (experiments / tests; the library reads no environment)
+    _check(lib().mh_gemm_mx(_I(M), _I(N), _I(K), ptr(A8), _I(lda), ptr(sa), _I(ldsa), ptr(B8), _I(ldb), ptr(sb), _I(ldsb), ptr(C),
+                            _I(ldc), _I(flags), ptr(bias), ptr(res), _I(ldr), ptr(aux_in), ptr(aux_out), _I(ldaux), ptr(colsum),
+                            ptr(c8), _I(ldc8), ptr(c8_scales), _I(ldc8s), stream()), "mh_gemm_mx")
+    if ev is not None:
+        ev[1].record()
+
+
+class _MhQuantMxJob(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("scales", ctypes.c_void_p), ("rows", ctypes.c_int),
+                ("cols", ctypes.c_int), ("ld_src", ctypes.c_int), ("ld_dst", ctypes.c_int), ("ld_s", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
+class QuantMxBatch:
+    """Job table for ``mh_quant_mx_batched``: ``jobs`` = dicts(src bf16 [rows, cols], dst uint8 [rows, cols], scales uint8
+    [rows, cols/32]); 2-D views with unit column stride (row pitches are taken from the views).  ``launch()``: one launch for all."""
+
+    def __init__(self, jobs, device) -> None:
+        arr = (_MhQuantMxJob * len(jobs))()
+        items, self.keep = [], []
+        for i, jb in enumerate(jobs):
+            src, dst, sc = jb["src"], jb["dst"], jb["scales"]
+            if src.dim() != 2 or src.dtype != torch.bfloat16 or dst.dtype != torch.uint8 or sc.dtype != torch.uint8:
+                raise HipExtensionError("QuantMxBatch: bf16 [rows, cols] source, uint8 destination and scales expected")
+            rows, cols = src.shape
+            if tuple(dst.shape) != (rows, cols) or tuple(sc.shape) != (rows, cols // MX_BLOCK) or \
+                    1 not in (src.stride(1), cols) or 1 not in (dst.stride(1), cols) or 1 not in (sc.stride(1), cols // MX_BLOCK):
+                raise HipExtensionError("QuantMxBatch: dst [rows, cols] and scales [rows, cols / 32] with unit column stride")
+            arr[i] = _MhQuantMxJob(src.data_ptr(), dst.data_ptr(), sc.data_ptr(), rows, cols, src.stride(0), dst.stride(0),
+                                   sc.stride(0), 0)
+            items += [(i << 32) | c for c in range(-(-(rows * cols) // MX_CHUNK))]
+            self.keep += [src, dst, sc]
+        self.host = arr
+        self.n_jobs = len(jobs)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+        self.items = torch.tensor(items, dtype=torch.int64).to(device)
+        self.n_items = len(items)
+
+    def launch(self) -> None:
+        _check(lib().mh_quant_mx_batched(ctypes.byref(self.host), _I(self.n_jobs), ptr(self.table), ptr(self.items),
+                                         _I(self.n_items), stream()), "mh_quant_mx_batched")
+
+
+def quant_mx(src: torch.Tensor, dst: torch.Tensor | None = None, scales: torch.Tensor | None = None):
+    """MX quantisation of one bf16 [rows, cols] tensor (cols % 32 == 0) -> (e4m3 uint8 [rows, cols], E8M0 uint8 [rows, cols/32])."""
+    rows, cols = src.shape
+    dst = torch.empty(rows, cols, dtype=torch.uint8, device=src.device) if dst is None else dst
+    if scales is None:
+        scales = torch.empty(rows, -(-(cols // MX_BLOCK) // 4) * 4, dtype=torch.uint8, device=src.device)[:, : cols // MX_BLOCK]
+    QuantMxBatch([dict(src=src, dst=dst, scales=scales)], src.device).launch()
+    return dst, scales

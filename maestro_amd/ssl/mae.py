@@ -233,20 +233,27 @@ class MAE(nn.Module):
             self.src_specs.setdefault(s.src, []).append(s)
 
     # ------------------------------------------------------------------------------------------ engine plumbing
-    def engine(self, batch_size: int, device=None, loss: str = "l2_norm", dtype: str | None = None):
+    def engine(self, batch_size: int, device=None, loss: str = "l2_norm", dtype: str | None = None,
+               fp8_scaling: str | None = None):
         """Return (building on first use / batch-size change) the HIP step engine bound to these parameters.  ``dtype``:
-        "bf16" (default) or "fp8" (e4m3 forward GEMMs, maestro_amd/fp8.py); None keeps the current engine's / MAESTRO_DTYPE."""
+        "bf16" (default) or "fp8" (e4m3 forward GEMMs, maestro_amd/fp8.py); None keeps the current engine's / MAESTRO_DTYPE.
+        ``fp8_scaling`` (fp8 only): "tensor" or "mx"; None keeps the current fp8 engine's / MAESTRO_FP8_SCALING."""
         import os
 
         from maestro_amd.engine import MAEEngine
+        from maestro_amd.fp8 import resolve_scaling
 
         device = torch.device(device) if device is not None else next(self.parameters()).device
         if dtype is None:
             dtype = self._engine.dtype if self._engine is not None else os.environ.get("MAESTRO_DTYPE", "bf16")
+        scaling = None
+        if dtype == "fp8":
+            keep = self._engine is not None and self._engine.fp8_scaling is not None and fp8_scaling is None
+            scaling = self._engine.fp8_scaling if keep else resolve_scaling(fp8_scaling)
         if self._engine is None or self._engine.B != batch_size or self._engine.loss != loss \
-                or self._engine.device != device or self._engine.dtype != dtype:
+                or self._engine.device != device or self._engine.dtype != dtype or self._engine.fp8_scaling != scaling:
             self._sup_engine = None
-            self._engine = MAEEngine(self, batch_size, device, loss=loss, dtype=dtype)
+            self._engine = MAEEngine(self, batch_size, device, loss=loss, dtype=dtype, fp8_scaling=scaling)
         return self._engine
 
     def sup_engine(self, batch_size: int, device=None, phase: str = "finetune"):
