@@ -90,3 +90,37 @@ def test_retired_experiment_switches_are_refused(monkeypatch):
     monkeypatch.delenv("MH_GEMM_SPLITK")
     monkeypatch.setattr(hip, "_lib", None)
     assert hip.lib() is not None
+
+
+def test_every_entry_point_has_a_guard_band_test_or_a_reason():
+    """The ledger of tests/guards.py: every ``mh_*`` name of the header is in exactly one of ``GUARDED`` (called by a guard-band
+    test) and ``EXEMPT`` (with a reason); a guarded name really occurs -- by name, through the hip.py wrapper of the same name, or
+    through the wrapper listed in ``VIA`` -- in one of the guard-test files; besides the six calls that touch no device buffer at
+    most ``MAX_OTHER_EXEMPT`` names are exempt."""
+    from tests import guards
+    header = (ROOT / "include" / "maestro_hip.h").read_text()
+    names = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", header))
+    both = guards.GUARDED & set(guards.EXEMPT)
+    assert not both, f"in GUARDED and in EXEMPT: {sorted(both)}"
+    neither = names - guards.GUARDED - set(guards.EXEMPT)
+    assert not neither, f"entry points without a guard-band test or an exemption: {sorted(neither)}"
+    unknown = (guards.GUARDED | set(guards.EXEMPT)) - names
+    assert not unknown, f"not declared in include/maestro_hip.h: {sorted(unknown)}"
+    no_buffer = {"mh_version", "mh_last_error", "mh_gemm_sk_workspace", "mh_groupnorm_partial_size", "mh_layernorm_bwd_workspace",
+                 "mh_attn_reduce_partial_rows"}
+    other = {n: r for n, r in guards.EXEMPT.items() if n not in no_buffer}
+    assert guards.MAX_OTHER_EXEMPT == 6 and len(other) <= 6, f"{len(other)} exemptions besides the six size / version calls: {sorted(other)}"
+    for n, reason in guards.EXEMPT.items():
+        assert isinstance(reason, str) and reason.strip() and "\n" not in reason, f"{n}: a one-line reason is required"
+    # the guard sections of the fp8 / MX files start at their "guard bands" banner: only calls below it count there
+    parts = []
+    for f in guards.GUARD_TEST_FILES:
+        body = (ROOT / "tests" / f).read_text()
+        parts.append(body if f == "test_guard_bands_gpu.py" else body.partition("guard bands (tests/guards.py)")[2])
+    text = re.sub(r"#[^\n]*", "", re.sub(r'"""[\s\S]*?"""', "", "\n".join(parts)))      # code only: no docstrings, no comments
+    absent = []
+    for n in sorted(guards.GUARDED):
+        forms = [rf"\b{n}\b", rf"\bhip\.{n[3:]}\(", re.escape(guards.VIA[n])] if n in guards.VIA else [rf"\b{n}\b", rf"\bhip\.{n[3:]}\("]
+        if not any(re.search(form, text) for form in forms):
+            absent.append(n)
+    assert not absent, f"in GUARDED but called by no guard test: {absent}"

@@ -429,3 +429,143 @@ def test_fp8_on_the_lightning_surface(dev, monkeypatch):
     assert scale == 2.0 ** (math.floor(math.log2(448.0 / amax)) - 1)
     want = (w.float() * scale).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
     assert torch.equal(f0["w_qkv"], want), "e4m3 weight shadow is stale after a torch optimizer step"
+
+
+# ---------------------------------------------------------------------------------------------------- guard bands (tests/guards.py)
+# The fp8 entry points on operands inside poisoned storage: 0x7F (e4m3 NaN) bands and pad columns around fp8 bytes, NaN around
+# floats, pitches above the dense ones, ragged M and N.  See tests/test_guard_bands_gpu.py for the bf16 path.
+@pytest.mark.parametrize("tile", ["128", "128d", "256"])
+@pytest.mark.parametrize("M,N,K", [(300, 520, 384), (130, 264, 1152)])
+def test_gemm_fp8_guarded(dev, M, N, K, tile, monkeypatch):  # noqa: N803
+    """``mh_gemm_fp8`` with lda, ldb > K, ldc > N and the fp8 copy with ldc8 > N.  Exact data: test_gemm_fp8_integer_exact; the c8
+    copy and its absmax: the bounds of test_gemm_fp8_epilogues_match_bf16_kernel."""
+    from maestro_amd import hip
+    from tests.guards import GuardSet
+    monkeypatch.setenv("MH_FP8_TILE", tile)
+    g = torch.Generator().manual_seed(M + N + K)
+    a = torch.randint(-4, 5, (M, K), generator=g).float()
+    b = torch.randint(-4, 5, (N, K), generator=g).float()
+    a[:, ::7] += 1.0
+    for a_fmt in (0, 1):
+        gs = GuardSet(dev)
+        A8 = gs.inp(_q(a, a_fmt).view(torch.uint8), ld=K + 16, fill="fp8", name="A8")  # noqa: N806
+        B8 = gs.inp(_q(b, 0).view(torch.uint8), ld=K + 48, fill="fp8", name="B8")  # noqa: N806
+        da, db = gs.inp(torch.tensor([0.5]), name="descale_a"), gs.inp(torch.tensor([4.0]), name="descale_b")
+        C = gs.out((M, N), torch.float32, ld=N + 8, name="C")  # noqa: N806
+        hip.gemm_fp8(M, N, K, A8, K + 16, B8, K + 48, C, N + 8, da, db, flags=hip.OUT_F32, a_format=a_fmt)
+        gs.check()
+        assert torch.equal(C.cpu(), 2.0 * (a @ b.t()))
+        Cb = gs.out((M, N), torch.bfloat16, ld=N + 16, name="C (bf16)")  # noqa: N806
+        c8 = gs.out((M, N), torch.uint8, ld=N + 24, fill="fp8", align=8, name="c8")
+        s8, amax = gs.inp(torch.tensor([2.0 ** -6]), name="c8_scale"), gs.out((hip.AMAX_PITCH,), init=0.0, name="c8_amax")
+        hip.gemm_fp8(M, N, K, A8, K + 16, B8, K + 48, Cb, N + 16, da, db, a_format=a_fmt, c8=c8, ldc8=N + 24, c8_scale=s8, c8_amax=amax)
+        gs.check()
+        want = (2.0 * (a @ b.t())).bfloat16()
+        assert torch.equal(Cb.cpu(), want)
+        want8 = _q((want.float() * 2.0 ** -6).clamp(-448, 448), 0).view(torch.uint8).int()
+        diff = (c8.cpu().int() - want8).abs()
+        assert int(diff.max()) <= 1 and float((diff != 0).float().mean()) < 0.05
+        assert abs(float(amax.max()) - float(want.float().abs().max())) <= 2 ** -7 * float(amax.max())
+
+
+def test_quantisers_and_scale_update_guarded(dev):
+    """``mh_quant_batched`` (cast + transposed copy + absmax), ``mh_fp8_update_scales`` on a slice of the tables and
+    ``mh_transpose_u8_batched``: references of test_quantiser_matches_torch_float8 / test_transpose_u8_batched."""
+    import math
+
+    from maestro_amd import hip
+    from tests.guards import GuardSet, bits_equal
+    g = torch.Generator().manual_seed(3)
+    gs = GuardSet(dev)
+    x_h = torch.randn(257, 64, generator=g) * torch.exp(3 * torch.randn(257, 1, generator=g))
+    n_slots = 4
+    scale = gs.out((n_slots,), init=1.0, name="scale")
+    descale = gs.out((n_slots,), init=1.0, name="descale")
+    amax = gs.out((n_slots, hip.AMAX_PITCH), init=0.0, name="amax")
+    scale[2] = 0.25
+
+    class Tables:                                            # what QuantBatch reads of hip.Fp8Scales
+        pass
+    sc = Tables()
+    sc.scale, sc.amax = scale, amax
+    jobs, wants = [], []
+    for dtype, fmt, slot in ((torch.float32, 0, 2), (torch.bfloat16, 1, 1)):
+        x = x_h.to(dtype)
+        src = gs.inp(x, name="src")
+        dst = gs.out(x.shape, torch.uint8, fill="fp8", name="dst")
+        dst_t = gs.out((64, 257), torch.uint8, fill="fp8", name="dst_t")
+        jobs.append(dict(src=src, dst=dst, dst_t=dst_t, slot=slot, format=fmt))
+        s = 0.25 if slot == 2 else 1.0
+        lim = hip.FP8_MAX[fmt]
+        wants.append((dst, dst_t, _q((x.float() * s).clamp(-lim, lim), fmt).view(torch.uint8), slot, float(x.float().abs().max())))
+    hip.QuantBatch(jobs, sc, dev).launch(2)
+    gs.check()
+    for dst, dst_t, want, slot, mx in wants:
+        assert torch.equal(dst.cpu(), want) and torch.equal(dst_t.cpu(), want.t().contiguous())
+        assert float(amax[slot].max()) == mx
+    assert float(amax[0].max()) == 0.0 and float(amax[3].max()) == 0.0
+    # scale update of slots [1, 3): slots 0 and 3 keep their bits
+    keep = [t.clone() for t in (scale[0:1], scale[3:], descale[0:1], descale[3:], amax[0], amax[3])]
+    mx1, mx2 = wants[1][4], wants[0][4]
+    hip.call("mh_fp8_update_scales", amax[1:3], scale[1:3], descale[1:3], hip._I(2), hip._F(448.0), hip._I(1))
+    gs.check()
+    for t, t0 in zip((scale[0:1], scale[3:], descale[0:1], descale[3:], amax[0], amax[3]), keep):
+        assert bits_equal(t, t0)
+    for slot, mx in ((1, mx1), (2, mx2)):
+        assert float(scale[slot]) == 2.0 ** (math.floor(math.log2(448.0 / mx)) - 1) and float(amax[slot].max()) == 0.0
+        assert float(descale[slot]) == 1.0 / float(scale[slot])
+    shapes = [(64, 64), (768, 1024), (512, 128)]
+    pairs = []
+    for s in shapes:
+        src = gs.inp(torch.randint(0, 256, s, generator=g, dtype=torch.uint8), fill="fp8", name="transpose src")
+        pairs.append((src, gs.out((s[1], s[0]), torch.uint8, fill="fp8", name="transpose dst")))
+    hip.TransposeBatch(pairs, dev).launch()
+    gs.check()
+    for s, d in pairs:
+        assert torch.equal(d.cpu(), s.cpu().t().contiguous())
+
+
+def test_adamw_fp8_on_a_slice_of_the_flat_store(dev):
+    """``mh_adamw_fp8`` on elements [lo, hi) of the flat p, g, m, v, bf16 and fp8 buffers, lo a multiple of 64 (the slot map's
+    granule) and not of 1024, with the slot map offset that goes with it: parameters bit-identical to ``mh_adamw``'s, shadows and
+    absmax as in test_adamw_fp8_refreshes_the_shadows_in_its_own_pass; everything outside the slice, NaN / 0x7F, keeps its bits."""
+    from maestro_amd import hip
+    from tests.guards import GuardSet, bits_equal
+    total, lo, n = 64 * 70, 64 * 17, 64 * 40 + 128
+    hi = lo + n
+    g = torch.Generator().manual_seed(9)
+    p0, grad = torch.randn(n, generator=g) * 0.05, torch.randn(n, generator=g) * 1e-3
+    smap_h = torch.full((total // 64,), 2, dtype=torch.int16)             # outside the slice: the trap slot (NaN scale)
+    smap_h[lo // 64: hi // 64] = -1
+    smap_h[lo // 64 + 4: lo // 64 + 20], smap_h[lo // 64 + 24: lo // 64 + 40] = 0, 1
+    outs = []
+    for fused in (False, True):
+        gs = GuardSet(dev)
+        p, gr, m, v = (gs.out((total,), name=nm) for nm in "pgmv")
+        half = gs.out((total,), torch.bfloat16, name="p_bf16")
+        p8 = gs.out((total,), torch.uint8, fill="fp8", align=4, name="p_fp8")
+        p[lo:hi], gr[lo:hi], m[lo:hi], v[lo:hi] = p0.to(dev), grad.to(dev), 0.0, 0.0
+        p8[lo:hi] = 7
+        smap = gs.idx(smap_h, 2, name="slot_map")
+        scale = gs.inp(torch.tensor([64.0, 128.0, float("nan")]), name="scale")
+        amax = gs.out((3, hip.AMAX_PITCH), init=0.0, name="amax")
+        before = [torch.cat([t[:lo], t[hi:]]).clone() for t in (p, gr, m, v, half, p8)]
+        if fused:
+            hip.adamw_fp8(p[lo:hi], gr[lo:hi], m[lo:hi], v[lo:hi], half[lo:hi], p8[lo:hi], smap[lo // 64:], scale, amax, n, 1e-3, 0.9, 0.99,
+                          1e-8, 0.01, 1, 0.5)
+        else:
+            hip.adamw(p[lo:hi], gr[lo:hi], m[lo:hi], v[lo:hi], half[lo:hi], n, 1e-3, 0.9, 0.99, 1e-8, 0.01, 1, 0.5)
+        gs.check()
+        for t, t0 in zip((p, gr, m, v, half, p8), before):
+            assert bits_equal(torch.cat([t[:lo], t[hi:]]), t0), "an element outside the slice changed"
+        outs.append([t[lo:hi].cpu() for t in (p, m, v, half, p8)] + [amax.cpu()])
+    for a, b in zip(outs[0][:4], outs[1][:4]):
+        assert bits_equal(a, b)
+    p_new, p8, amax = outs[1][0], outs[1][4], outs[1][5]
+    assert torch.isfinite(p_new).all()
+    for slot, (s0, s1), sc in ((0, (4 * 64, 20 * 64), 64.0), (1, (24 * 64, 40 * 64), 128.0)):
+        want = _q((p_new[s0:s1] * sc).clamp(-448, 448), 0).view(torch.uint8)
+        assert torch.equal(p8[s0:s1], want) and float(amax[slot].max()) == float(p_new[s0:s1].abs().max())
+    assert bool((p8[: 4 * 64] == 7).all()) and bool((p8[20 * 64: 24 * 64] == 7).all()) and bool((p8[40 * 64:] == 7).all())
+    assert float(amax[2].abs().max()) == 0.0                              # the trap slot saw nothing
+

@@ -425,3 +425,89 @@ def test_mx_refuses_the_fp8_dgrad(dev, monkeypatch):
     monkeypatch.setenv("MAESTRO_FP8_DGRAD", "1")
     with pytest.raises(ValueError, match="MAESTRO_FP8_DGRAD.*mx|mx.*MAESTRO_FP8_DGRAD"):
         model().engine(2, dev, loss="l2_norm", dtype="fp8", fp8_scaling="mx")
+
+
+# ---------------------------------------------------------------------------------------------------- guard bands (tests/guards.py)
+# The MX entry points on operands inside poisoned storage: 0x7F (e4m3 NaN) around element bytes, 0xFF (E8M0 NaN) around scale
+# bytes, NaN around floats; operand AND scale pitches above the dense ones, ragged M and N.
+@pytest.mark.parametrize("tile", ["128", "128d", "256"])
+@pytest.mark.parametrize("M,N,K", [(300, 520, 384), (130, 264, 1152)])
+def test_gemm_mx_guarded(dev, M, N, K, tile, monkeypatch):  # noqa: N803
+    """``mh_gemm_mx`` on the exact data of test_gemm_mx_exact_data with lda, ldb > K, ldsa, ldsb > K / 32, ldc > N."""
+    from maestro_amd import hip
+    from tests.guards import GuardSet
+    monkeypatch.setenv("MH_FP8_TILE", tile)
+    g = torch.Generator().manual_seed(M + 3 * N + K)
+    a = torch.randint(-3, 4, (M, K), generator=g).float()
+    b = torch.randint(-3, 4, (N, K), generator=g).float()
+    a[:, ::7] += 1.0
+    b[::5, :] -= 0.5
+    ea = torch.randint(-2, 3, (M, K // 32), generator=g)
+    eb = torch.randint(-2, 3, (N, K // 32), generator=g)
+    gs = GuardSet(dev)
+    A8 = gs.inp(a.to(torch.float8_e4m3fn).view(torch.uint8), ld=K + 16, fill="fp8", name="A8")  # noqa: N806
+    B8 = gs.inp(b.to(torch.float8_e4m3fn).view(torch.uint8), ld=K + 48, fill="fp8", name="B8")  # noqa: N806
+    ldsa, ldsb = (K // 32 + 3) // 4 * 4 + 4, (K // 32 + 3) // 4 * 4 + 12
+    sa = gs.inp((ea + 127).to(torch.uint8), ld=ldsa, fill="e8m0", align=4, name="sa")
+    sb = gs.inp((eb + 127).to(torch.uint8), ld=ldsb, fill="e8m0", align=4, name="sb")
+    C = gs.out((M, N), torch.float32, ld=N + 8, name="C")  # noqa: N806
+    hip.gemm_mx(M, N, K, A8, K + 16, sa, ldsa, B8, K + 48, sb, ldsb, C, N + 8, flags=hip.OUT_F32)
+    gs.check()
+    ad = a.double() * torch.exp2(ea.double()).repeat_interleave(32, dim=1)
+    bd = b.double() * torch.exp2(eb.double()).repeat_interleave(32, dim=1)
+    assert torch.equal(C.cpu(), (ad @ bd.t()).float())
+
+
+@pytest.mark.parametrize("M,N,K", [(300, 544, 256), (130, 288, 384)])
+def test_gemm_mx_c8_copy_guarded(dev, M, N, K):  # noqa: N803
+    """The MX copy of the bf16 output with ldc8 > N and ldc8s > N / 32, ragged M: exact operands, so the bf16 output is exact
+    and c8 / c8_scales are the MX rule (mx_ref) applied to it, as in test_gemm_mx_epilogues_and_c8_copy."""
+    from maestro_amd import hip
+    from tests.guards import GuardSet
+    g = torch.Generator().manual_seed(M + N)
+    a = torch.randint(-3, 4, (M, K), generator=g).float()
+    b = torch.randint(-3, 4, (N, K), generator=g).float()
+    ea = torch.randint(-2, 3, (M, K // 32), generator=g)
+    eb = torch.randint(-2, 3, (N, K // 32), generator=g)
+    gs = GuardSet(dev)
+    A8 = gs.inp(a.to(torch.float8_e4m3fn).view(torch.uint8), ld=K + 32, fill="fp8", name="A8")  # noqa: N806
+    B8 = gs.inp(b.to(torch.float8_e4m3fn).view(torch.uint8), ld=K + 16, fill="fp8", name="B8")  # noqa: N806
+    lds = K // 32 + 4
+    sa = gs.inp((ea + 127).to(torch.uint8), ld=lds, fill="e8m0", align=4, name="sa")
+    sb = gs.inp((eb + 127).to(torch.uint8), ld=lds, fill="e8m0", align=4, name="sb")
+    C = gs.out((M, N), torch.bfloat16, ld=N + 8, name="C")  # noqa: N806
+    c8 = gs.out((M, N), torch.uint8, ld=N + 24, fill="fp8", align=8, name="c8")
+    ldc8s = N // 32 + 7
+    ldc8s += -ldc8s % 4
+    c8s = gs.out((M, N // 32), torch.uint8, ld=ldc8s, fill="e8m0", align=4, name="c8_scales")
+    hip.gemm_mx(M, N, K, A8, K + 32, sa, lds, B8, K + 16, sb, lds, C, N + 8, c8=c8, ldc8=N + 24, c8_scales=c8s, ldc8s=ldc8s)
+    gs.check()
+    ad = a.double() * torch.exp2(ea.double()).repeat_interleave(32, dim=1)
+    bd = b.double() * torch.exp2(eb.double()).repeat_interleave(32, dim=1)
+    want = (ad @ bd.t()).float().bfloat16()
+    assert torch.equal(C.cpu(), want)
+    q, s, finite = mx_ref(want)
+    assert bool(finite.all()) and torch.equal(c8.cpu(), q) and torch.equal(c8s.cpu(), s)
+
+
+def test_quant_mx_guarded(dev):
+    """``mh_quant_mx_batched`` with source, destination and scale pitches above the dense ones: bit for bit the rule."""
+    from maestro_amd import hip
+    from tests.guards import GuardSet
+    g = torch.Generator().manual_seed(5)
+    gs = GuardSet(dev)
+    jobs, want = [], []
+    for rows, cols, pad_s, pad_d, pad_sc in ((37, 768, 8, 16, 3), (130, 96, 4, 4, 1), (5, 3072, 4, 32, 1)):
+        x = torch.randn(rows, cols // 32, 32, generator=g) * torch.exp(3 * torch.randn(rows, cols // 32, 1, generator=g))
+        xb = x.reshape(rows, cols).bfloat16()
+        xb[0, :32] = 0.0
+        src = gs.inp(xb, ld=cols + pad_s, align=8, name="src")
+        dst = gs.out((rows, cols), torch.uint8, ld=cols + pad_d, fill="fp8", align=4, name="dst")
+        sc = gs.out((rows, cols // 32), torch.uint8, ld=cols // 32 + pad_sc, fill="e8m0", align=4, name="scales")
+        jobs.append(dict(src=src, dst=dst, scales=sc))
+        want.append(xb)
+    hip.QuantMxBatch(jobs, dev).launch()
+    gs.check()
+    for jb, xb in zip(jobs, want):
+        q, s, finite = mx_ref(xb)
+        assert bool(finite.all()) and torch.equal(jb["dst"].cpu(), q) and torch.equal(jb["scales"].cpu(), s)
