@@ -42,7 +42,11 @@ int mh_version(void);
 #define MH_GEMM_DGELU 16
 #define MH_GEMM_ATOMIC 32
 #define MH_GEMM_COLSUM 64   /* bf16 output only: colsum[(m / 64), n] = sum over the 64-row block of C[m, n] (f32 values before
-                             * rounding); colsum is a [ceil(M / 64), N] workspace, plain stores; reduce it with mh_colsum */
+                             * rounding); colsum is a [ceil(M / 64), N] workspace, plain stores; reduce it with mh_colsum.
+                             * Numerics: the summand is the epilogue's fp32 value (accumulator + bias, times the GELU' / MULAUX
+                             * factor), NOT its bf16 rounding that C receives; the 64 terms are added in fp32 (a lane's rows in
+                             * order, then a three-step butterfly), so |colsum - exact| <= 64 2^-23 sum |terms| + the terms' own
+                             * errors (tests/test_numerics_gpu.py).  Rows at or beyond M contribute nothing. */
 #define MH_GEMM_AUX_DGELU 128 /* with MH_GEMM_GELU: aux_out receives GELU'(pre-activation) (bf16) instead of the pre-activation: the
                                * CDF / PDF are already at hand in the forward epilogue, so the backward only multiplies */
 #define MH_GEMM_MULAUX 256    /* bf16 output only: C *= aux_in[M, N] (bf16) -- the backward of GELU with the saved derivative */
@@ -275,8 +279,12 @@ int mh_patchify(const float* img, void* cols, float* target, int BD, int Ctot, i
 int mh_patchify_bands(const float* img, void* cols, float* target, int BD, int Csrc, int c0, int Ctot, int S, int P, int Kpad,
                       const int* norm_bands, int n_norm_groups, int normalise, int rescale_elev, void* stream);
 
-/* GroupNorm(1, E) over the whole (tokens x E) image per (b, d) (embed.py:55,59-61): chunked partial sums ->
- * stats f32 [BD, 2] = (mean, rstd).  partial: f32 workspace of mh_groupnorm_partial_size() floats. */
+/* GroupNorm(1, E) over the whole (tokens x E) image per (b, d) (embed.py:55,59-61): chunked partials ->
+ * stats f32 [BD, 2] = (mean, rstd).  partial: f32 workspace of mh_groupnorm_partial_size() floats.
+ * Numerics: every chunk of 8192 values is reduced in two passes (its fp32 sum, then the fp32 sum of (x - chunk mean)^2) and
+ * the chunks are merged in fp64, so mean and rstd keep fp32 two-pass accuracy however far the image lies from zero (an image
+ * whose mean is 1000 sigma: rstd to ~1e-7 relative; sums of x and x^2 would lose all but two digits there).  A constant image gives
+ * variance 0 exactly when its chunk sums are exact in fp32.  tests/test_numerics_gpu.py holds the bounds. */
 int mh_groupnorm_stats(const float* y, float* partial, float* stats, int BD, int L, int E, float eps, void* stream);
 int mh_groupnorm_partial_size(int BD, int L, int E);
 /* normalise + per-channel affine + positional + date encodings (mim.py:232-252, utils.py:103-173), written straight

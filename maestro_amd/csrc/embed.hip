@@ -168,22 +168,42 @@ __global__ __launch_bounds__(256) void patchify_wave16_kernel(const float* __res
     for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4*>(out + 4 * i) = (f32x4){t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]};
 }
 
-// ---- GroupNorm(1, E) statistics over a whole (L x E) image: chunked partial sums, then a finalize.
+// ---- GroupNorm(1, E) statistics over a whole (L x E) image: per-chunk (sum, centred sum of squares), then a finalize.
+// A chunk is 32 values per thread and stays in registers, so it is reduced in two passes: its fp32 sum s first, then the sum q of
+// (x - m)^2 around m = s / n_c.  The finalize merges the chunks in fp64 with the exact expansion
+//   sum (x - mu)^2 = sum_c [ q_c + 2 (m_c - mu) (s_c - n_c m_c) + n_c (m_c - mu)^2 ],   mu = sum_c s_c / n,
+// recomputing m_c = s_c / n_c with the same fp32 division, so the centre it assumes is bit for bit the one the chunk used.
+// The earlier form kept fp32 sums of x and x^2 per chunk: E[x^2] - E[x]^2 cancels, and the variance of an image whose mean is
+// 100 sigma was off by 3e-4 relative, at 1000 sigma by 5e-2.  (Sums shifted by a per-image pivot cure that too, but their mean is
+// only as good as the pivot is close to it: on zero-mean images they are worse than plain sums.  A chunk centred on its own mean
+// has no such case, and the mean itself is the same sum of chunk sums as before.)
 constexpr int GN_CHUNK = 8192;
 
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ y, float* __restrict__ partial,
                                                          long per_image, int nchunk) {
     __shared__ float red[8];
+    constexpr int NV = GN_CHUNK / (256 * 4);
     const int bd = blockIdx.y, ch = blockIdx.x;
     const float* p = y + (size_t)bd * per_image;
     const long lo = (long)ch * GN_CHUNK, hi = min(per_image, lo + GN_CHUNK);
-    float s = 0.f, q = 0.f;
-    for (long i = lo + threadIdx.x * 4; i < hi; i += 256 * 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + i);
-        s += (v[0] + v[1]) + (v[2] + v[3]);
-        q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    f32x4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const long i = lo + (long)(j * 256 + threadIdx.x) * 4;
+        v[j] = i < hi ? *reinterpret_cast<const f32x4*>(p + i) : (f32x4){0, 0, 0, 0};
+        s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
     }
     s = block_sum<4>(s, red);
+    const float m = s / (float)(hi - lo);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        if (lo + (long)(j * 256 + threadIdx.x) * 4 < hi) {
+            const f32x4 d = v[j] - m;
+            q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+        }
+    }
     q = block_sum<4>(q, red + 4);
     if (threadIdx.x == 0) {
         partial[((size_t)bd * nchunk + ch) * 2] = s;
@@ -194,15 +214,21 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
 __global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict__ partial, float* __restrict__ stats,
                                                          long per_image, int nchunk, float eps) {
     const int bd = blockIdx.x;
-    double s = 0.0, q = 0.0;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nchunk; i += 64) s += partial[((size_t)bd * nchunk + i) * 2];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const double mu = s / per_image;                       // (the butterfly leaves the same sum in every lane)
+    double q = 0.0;
     for (int i = threadIdx.x; i < nchunk; i += 64) {
-        s += partial[((size_t)bd * nchunk + i) * 2];
-        q += partial[((size_t)bd * nchunk + i) * 2 + 1];
+        const float sc = partial[((size_t)bd * nchunk + i) * 2];
+        const float nc = (float)min((long)GN_CHUNK, per_image - (long)i * GN_CHUNK);
+        const float mc = sc / nc;                          // the centre gn_partial_kernel used for this chunk
+        const double dm = (double)mc - mu;
+        q += partial[((size_t)bd * nchunk + i) * 2 + 1] + dm * (2.0 * ((double)sc - (double)nc * mc) + (double)nc * dm);
     }
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
     if (threadIdx.x == 0) {
-        const double mu = s / per_image;
-        const double var = fmax(q / per_image - mu * mu, 0.0);
+        const double var = fmax(q / per_image, 0.0);
         stats[bd * 2] = (float)mu;
         stats[bd * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
