@@ -93,6 +93,23 @@ int mh_gemm_bf16_tile(int tile, int layout, int M, int N, int K, const void* A, 
                       int ldc, int flags, const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out,
                       int ldaux, float* colsum, void* stream);
 
+/* Which tile mh_gemm_bf16_tile(tile, ...) runs for a problem: the library's one dispatch rule as a query.  Like the size queries
+ * it takes no device buffer and no stream and launches nothing; it reads shapes, strides and flags only.  Returns
+ *   >= 0  the concrete MH_TILE_* that runs: for MH_TILE_AUTO the rule's choice (REG_128, REG_192, PP_128 or DMA_256); an explicit
+ *         tile stands for itself, except MH_TILE_REG_64 / _192 on a TN or MH_GEMM_COLSUM problem, which run as MH_TILE_REG_128;
+ *   -2    the explicit DMA / ping-pong tile does not serve the problem (mh_gemm_bf16_tile answers -2 too; error string untouched);
+ *   -1    invalid layout / flags / strides / tile (the stream-K ids included: they belong to mh_gemm_bf16_sk), by the same checks
+ *         as the GEMM call minus those on its pointers; see mh_last_error.
+ * `families`: the kernel families MH_TILE_AUTO may choose besides the 128 x 128 register tile.  MH_GEMM_FAMILY_ALL is the rule
+ * mh_gemm_bf16 applies; a subset states an A/B rule without copying it (MH_GEMM_FAMILY_DMA alone: the rule before the ping-pong
+ * and 192-row tiles existed).  A family that is left out is never chosen; explicit tiles ignore the mask. */
+#define MH_GEMM_FAMILY_DMA 1
+#define MH_GEMM_FAMILY_PP 2
+#define MH_GEMM_FAMILY_192 4
+#define MH_GEMM_FAMILY_ALL 7
+int mh_gemm_bf16_resolve_tile(int tile, int families, int layout, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
+                              int ldaux, int flags);
+
 /* Stream-K GEMM (gemm_sk.hip): C[M, N] = A[M, K] B^T (layout 0, B [N, K]) or A B (layout 1, B [K, N]) with the long-K, narrow-N
  * problems of the transformer blocks in mind (fc2, out-proj, fc1 / qkv / out-proj dgrads: the nn.Linear call sites of
  * vit_pytorch's Attention / FeedForward built at maestro/ssl/mae.py:135-174).  `grid` persistent four-wave workgroups (one per

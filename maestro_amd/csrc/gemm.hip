@@ -21,7 +21,7 @@ namespace {
 // MT = 16-row blocks per wave: the tile is (32 MT) x 128 -- 4: 128 x 128 (two workgroups per CU); 2: 64 x 128 (48 KiB of LDS,
 // three workgroups per CU); 6: 192 x 128 (80 KiB, two per CU).  The other two shapes exist for the N = 512 / 768 outputs of the
 // transformer blocks (out-proj, fc2 and three of the four dgrads), whose 128 x 128 tilings fill the 512 workgroup slots badly
-// (M = 8192: 384 tiles; M = 3200: 150; M = 11392: 534): see the dispatch rule in mh_gemm_bf16_tile.
+// (M = 8192: 384 tiles; M = 3200: 150; M = 11392: 534): see the dispatch rule in gemm_resolve.
 template <bool A_KMAJOR, bool B_KMAJOR, int MT = 4>
 __global__ __launch_bounds__(NT, MT == 2 ? 3 : 2) void gemm_kernel(GemmParams p) {
     static_assert(!A_KMAJOR || MT == 4, "the K-major A image is 128 columns wide");
@@ -195,110 +195,14 @@ __global__ __launch_bounds__(NT, MT == 2 ? 3 : 2) void gemm_kernel(GemmParams p)
 
 }  // namespace
 
-// Dispatch rule for the large-tile LDS-DMA kernel (gemm_dma.hip), from scripts/bench_tiles.py on MI355X: it wins (x1.05 to
-// x1.2, x1.8 on the K = 512 dgrad) for NT and NN problems whose 256x256 tiles fill the 256 CUs in whole waves (>= 90 % wave
-// efficiency: the M = 32768 decoder shapes); it loses when the tile count quantises badly (M = 8192 encoder shapes) and for
-// split-K wgrads (more splits -> more fp32 atomic passes).  The library reads no environment: a caller that wants another
-// kernel passes an explicit tile to mh_gemm_bf16_tile (maestro_amd/hip.py maps MH_GEMM_DMA / MH_GEMM_TILE onto that).
-static bool prefer_dma(int layout, int M, int N, int K, int flags) {
-    if (layout == 2 || (flags & MH_GEMM_ATOMIC) || K % 32 != 0 || K < 256) return false;
-    const long tiles = (long)ceil_div(M, 256) * ceil_div(N, 256);
-    if (tiles < 256) return false;
-    const long waves = (tiles + 255) / 256;
-    return 10 * tiles >= 9 * 256 * waves;
-}
-
-static int gemm_dispatch(int tile, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                         void* C, int ldc, int flags, const float* bias, const float* res, int ldr,
-                         const void* aux_in, void* aux_out, int ldaux, float* colsum, void* stream);
-
-extern "C" int mh_gemm_bf16_tile(int tile, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                                 void* C, int ldc, int flags, const float* bias, const float* res, int ldr,
-                                 const void* aux_in, void* aux_out, int ldaux, float* colsum, void* stream) {
-    return gemm_dispatch(tile, layout, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, aux_in, aux_out, ldaux, colsum, stream);
-}
-
-static int gemm_dispatch(int tile, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                         void* C, int ldc, int flags, const float* bias, const float* res, int ldr,
-                         const void* aux_in, void* aux_out, int ldaux, float* colsum, void* stream) {
-    MH_CHECK_ARG(tile >= MH_TILE_AUTO && tile <= MH_TILE_REG_192, "mh_gemm_bf16: tile %d", tile);
-    MH_CHECK_ARG(layout >= 0 && layout <= 2, "mh_gemm_bf16: layout %d", layout);
-    MH_CHECK_ARG(!(flags & ~0x7ff), "mh_gemm_bf16: unknown flag bits 0x%x", flags & ~0x7ff);
-    MH_CHECK_ARG(M > 0 && N > 0 && K > 0, "mh_gemm_bf16: empty problem %d %d %d", M, N, K);
-    MH_CHECK_ARG(A && B && C, "mh_gemm_bf16: null operand");
-    MH_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0, "mh_gemm_bf16: lda/ldb must be multiples of 8 (%d, %d)", lda, ldb);
-    MH_CHECK_ARG(N % 4 == 0 && ldc % 4 == 0, "mh_gemm_bf16: N and ldc must be multiples of 4 (%d, %d)", N, ldc);
-    MH_CHECK_ARG((flags & MH_GEMM_OUT_F32) || (N % 8 == 0 && ldc % 8 == 0), "mh_gemm_bf16: bf16 output needs N, ldc %% 8 == 0");
-    MH_CHECK_ARG((flags & MH_GEMM_OUT_F32) || !(flags & MH_GEMM_RESIDUAL), "mh_gemm_bf16: residual epilogue needs f32 output");
-    MH_CHECK_ARG(!(flags & MH_GEMM_OUT_F32) || !(flags & (MH_GEMM_GELU | MH_GEMM_DGELU | MH_GEMM_MULAUX)), "mh_gemm_bf16: GELU / aux epilogues need bf16 output");
-    MH_CHECK_ARG(((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) % 16 == 0, "mh_gemm_bf16: bases must be 16-B aligned");
-    if (layout == 2) {
-        MH_CHECK_ARG(M % 8 == 0 && N % 8 == 0, "mh_gemm_bf16: TN needs M, N multiples of 8 (%d, %d)", M, N);
-    } else {
-        MH_CHECK_ARG(K % 8 == 0, "mh_gemm_bf16: K must be a multiple of 8 (%d)", K);
-        if (layout == 1) MH_CHECK_ARG(N % 8 == 0, "mh_gemm_bf16: NN needs N multiple of 8 (%d)", N);
-    }
-    MH_CHECK_ARG(!(flags & MH_GEMM_BIAS) || bias, "mh_gemm_bf16: bias flag without pointer");
-    MH_CHECK_ARG(!(flags & MH_GEMM_RESIDUAL) || (res && ldr % 4 == 0), "mh_gemm_bf16: residual needs pointer, ldr%%4==0");
-    MH_CHECK_ARG(!(flags & (MH_GEMM_DGELU | MH_GEMM_MULAUX)) || (aux_in && ldaux % 8 == 0), "mh_gemm_bf16: dgelu / mulaux need aux_in, ldaux %% 8 == 0");
-    MH_CHECK_ARG(!(flags & MH_GEMM_AUX_DGELU) || ((flags & MH_GEMM_GELU) && aux_out), "mh_gemm_bf16: aux_dgelu needs the GELU epilogue and aux_out");
-    MH_CHECK_ARG(!((flags & MH_GEMM_DGELU) && (flags & MH_GEMM_MULAUX)), "mh_gemm_bf16: dgelu and mulaux exclude each other");
-    MH_CHECK_ARG(!(flags & MH_GEMM_AUX_U8) || ((flags & (MH_GEMM_AUX_DGELU | MH_GEMM_MULAUX)) && !(flags & MH_GEMM_DGELU)),
-                 "mh_gemm_bf16: MH_GEMM_AUX_U8 applies to the saved GELU derivative only (AUX_DGELU / MULAUX)");
-    MH_CHECK_ARG(!(flags & MH_GEMM_GELU) || !aux_out || ldaux % 8 == 0, "mh_gemm_bf16: ldaux %% 8");
-    MH_CHECK_ARG(!(flags & MH_GEMM_ATOMIC) || (flags & MH_GEMM_OUT_F32), "mh_gemm_bf16: atomic needs f32 output");
-    MH_CHECK_ARG(!(flags & MH_GEMM_COLSUM) || (colsum && !(flags & MH_GEMM_OUT_F32)), "mh_gemm_bf16: colsum needs a pointer and bf16 output");
-    MH_CHECK_ARG(!(flags & MH_GEMM_ATOMIC) || !(flags & ~(MH_GEMM_ATOMIC | MH_GEMM_OUT_F32)),
-                 "mh_gemm_bf16: atomic accumulate excludes other epilogues");
-
-    if (tile >= MH_TILE_PP_128 && tile <= MH_TILE_PP_128_DIAG5)
-        return gemm_pp_dispatch(layout, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, aux_in, aux_out, ldaux, colsum, stream,
-                                tile - MH_TILE_PP_128);
-    if (tile > MH_TILE_REG_128 && tile < MH_TILE_PP_128)   // explicit DMA tile: -2 when not eligible (the caller picks another tile)
-        return gemm_dma_dispatch(tile, layout, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, aux_in, aux_out, ldaux, colsum, stream);
-    // Persistent 128x128 tile with the epilogue inside the next tile's main loop (gemm_pp.hip), scripts/bench_pp.py on the C3
-    // step's shapes with their real epilogues: +6...12 % on the plain bf16 NT outputs (qkv), +3...10 % on fp32 + residual
-    // (out-proj, fc2) and on the plain NN dgrads, +3 % on fc1; it LOSES 8-20 % on the fc2 dgrad (MULAUX + column sums: 256
-    // VGPRs, spills) -> never picked there.  Against the 256x256 LDS-DMA tile (M = 32768) it wins the short-K NT problems
-    // (qkv 61.0 vs 68.4 us, out-proj 38.8 vs 43.3, fc1 165 vs 173) and loses the long-K ones (fc2 136 vs 125).
-    const bool dma = tile == MH_TILE_AUTO && prefer_dma(layout, M, N, K, flags);
-    // 192 x 128 tiles where the 128 x 128 tiling overshoots the 512 workgroup slots by a few tiles (M = 11392, N = 768: 534 tiles,
-    // i.e. a second, almost empty round; 360 tiles of 192 x 128 run in one): fc2 78.8 -> 76.5 us, fc1 dgrad 73.6 -> 69.5, qkv dgrad
-    // 56.8 -> 54.1 (scripts/bench_pp.py).  The 64 x 128 form (three workgroups per CU) gains 1-4 % at M = 8192, N = 768 and loses
-    // elsewhere: explicit tile only.
-    if (tile == MH_TILE_AUTO && !dma && layout != 2 && !(flags & (MH_GEMM_COLSUM | MH_GEMM_ATOMIC)) && K >= 1536 && K % BK == 0) {
-        const long t128 = (long)ceil_div(M, 128) * ceil_div(N, 128);
-        if (t128 > 512 && t128 <= 576 && (long)ceil_div(M, 192) * ceil_div(N, 128) <= 512) tile = MH_TILE_REG_192;
-    }
-    // Round 3, second pass -- the rule below follows the kernels' times INSIDE the step (bench.py --shapes on the pretrain, probe and
-    // finetune steps, profiles/README.md), which differ from the isolated loops above (operands are cold, the fp32 residual is
-    // read, two group streams share the chip): the ping-pong tile keeps the NT problems between one round of workgroups and
-    // 8192 tiles (qkv +6 %, out-proj +11 %, fc2 +4 % at M = 32768; +2 ... 5 % at M = 8192), loses the fc1 (GELU) epilogue beyond
-    // ~2300 tiles (M = 32768: -7 % against the LDS-DMA tile, M = 12800: -2 %), loses 27 % on the segmentation head (M = 557056,
-    // 52224 tiles, 1.7 GB of output: the LDS-DMA tile's staged full-line stores), and is a tie or a loss on every NN (dgrad)
-    // problem in the step (M = 3200: -9 %), so those stay with the one-tile-per-workgroup / LDS-DMA kernels.
-    const long t128_all = (long)ceil_div(M, 128) * ceil_div(N, 128);
-    const bool pp_ok = layout == 0 && t128_all >= 256 &&
-                       ((flags & MH_GEMM_GELU) ? t128_all <= 2304 : (!dma || (K < 1024 && t128_all <= 8192)));
-    if (tile == MH_TILE_AUTO && !(flags & MH_GEMM_MULAUX) && pp_ok) {
-        const int rc = gemm_pp_dispatch(layout, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, aux_in, aux_out, ldaux, colsum, stream);
-        if (rc != -2) return rc;   // -2: not eligible -> the kernels below
-    }
-    if (dma) {
-        const int rc = gemm_dma_dispatch(MH_TILE_DMA_256, layout, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, aux_in,
-                                         aux_out, ldaux, colsum, stream);
-        if (rc != -2) return rc;   // -2: not eligible -> general kernel below
-    }
-    GemmParams p;
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
-    p.bias = bias; p.res = res; p.aux_in = (const bf16_t*)aux_in; p.aux_out = (bf16_t*)aux_out; p.colsum = colsum;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldaux = ldaux; p.flags = flags;
-    // tile rows: 128 unless the caller (or the rule above) asked for the 64- / 192-row form (K-minor A, no column sums)
-    const int mt = (layout != 2 && !(flags & MH_GEMM_COLSUM)) ? (tile == MH_TILE_REG_64 ? 2 : tile == MH_TILE_REG_192 ? 6 : 4) : 4;
+// One problem on the register-staged kernel: tile = MH_TILE_REG_128 / _64 / _192 as mh_gemm_bf16_resolve_tile names it
+static int gemm_reg_launch(int tile, int layout, GemmParams& p, hipStream_t s) {
+    const int K = p.K;
+    const int mt = tile == MH_TILE_REG_64 ? 2 : tile == MH_TILE_REG_192 ? 6 : 4;
     const int tbm = 32 * mt;
-    p.tiles_m = ceil_div(M, tbm); p.tiles_n = ceil_div(N, BN);
+    p.tiles_m = ceil_div(p.M, tbm); p.tiles_n = ceil_div(p.N, BN);
     int splits = 1;
-    if (flags & MH_GEMM_ATOMIC) {  // fill the 256 CUs (2 workgroups each) when the output has few tiles
+    if (p.flags & MH_GEMM_ATOMIC) {  // fill the 256 CUs (2 workgroups each) when the output has few tiles
         const int tiles = p.tiles_m * p.tiles_n;
         const int ksteps = ceil_div(K, BK);
         splits = max(1, min(min(512 / max(tiles, 1), ksteps / 4), 32));
@@ -310,15 +214,12 @@ static int gemm_dispatch(int tile, int layout, int M, int N, int K, const void* 
     // instead of reading zero); K-major operands zero-fill beyond K by the descriptor extent.  Split ranges are whole
     // K steps, so the only tail is the global one.
     const bool a_kmajor = layout == 2, b_kmajor = layout != 0;
-    const long a_ext = a_kmajor ? ((long)(K - 1) * lda + M) * 2 : ((long)(M - 1) * lda + K) * 2;
-    const long b_ext = b_kmajor ? ((long)(K - 1) * ldb + N) * 2 : ((long)(N - 1) * ldb + K) * 2;
-    const long a_reach = a_kmajor ? (long)(ceil_div(K, BK) * BK) * lda * 2 : (long)(p.tiles_m * tbm) * lda * 2;
-    const long b_reach = b_kmajor ? (long)(ceil_div(K, BK) * BK) * ldb * 2 : (long)(p.tiles_n * BN) * ldb * 2;
-    const bool tail_ok = (a_kmajor || K % BK == 0) && (b_kmajor || K % BK == 0);
-    p.fast = tail_ok && a_reach + 4096 < (1L << 31) && b_reach + 4096 < (1L << 31);
-    p.a_bytes = (unsigned)a_ext; p.b_bytes = (unsigned)b_ext;
+    const long k_rows = (long)ceil_div(K, BK) * BK;
+    const bool tail_ok = (a_kmajor && b_kmajor) || K % BK == 0;
+    p.fast = tail_ok && gemm_in_reach((a_kmajor ? k_rows : (long)p.tiles_m * tbm) * p.lda * 2, 4096) &&
+             gemm_in_reach((b_kmajor ? k_rows : (long)p.tiles_n * BN) * p.ldb * 2, 4096);
+    gemm_set_extents(p, layout);
     dim3 grid(p.tiles_m * p.tiles_n, splits), block(NT);
-    hipStream_t s = (hipStream_t)stream;
     switch (layout * 8 + mt) {
         case 0 * 8 + 4: hipLaunchKernelGGL((gemm_kernel<false, false, 4>), grid, block, 0, s, p); break;
         case 0 * 8 + 2: hipLaunchKernelGGL((gemm_kernel<false, false, 2>), grid, block, 0, s, p); break;
@@ -330,6 +231,115 @@ static int gemm_dispatch(int tile, int layout, int M, int N, int K, const void* 
     }
     MH_LAUNCH_CHECK();
     return 0;
+}
+
+// The argument checks of mh_gemm_bf16_tile.  buffers = false: the shape / stride / flag half alone, for
+// mh_gemm_bf16_resolve_tile, which has no pointers to offer (they count as given).
+static int gemm_check_args(bool buffers, int tile, int layout, const GemmParams& p) {
+    const int M = p.M, N = p.N, K = p.K, lda = p.lda, ldb = p.ldb, ldc = p.ldc, ldr = p.ldr, ldaux = p.ldaux, flags = p.flags;
+    auto given = [&](const void* q) { return !buffers || q; };
+    MH_CHECK_ARG(tile >= MH_TILE_AUTO && tile <= MH_TILE_REG_192, "mh_gemm_bf16: tile %d", tile);
+    MH_CHECK_ARG(layout >= 0 && layout <= 2, "mh_gemm_bf16: layout %d", layout);
+    MH_CHECK_ARG(!(flags & ~0x7ff), "mh_gemm_bf16: unknown flag bits 0x%x", flags & ~0x7ff);
+    MH_CHECK_ARG(M > 0 && N > 0 && K > 0, "mh_gemm_bf16: empty problem %d %d %d", M, N, K);
+    MH_CHECK_ARG(given(p.A) && given(p.B) && given(p.C), "mh_gemm_bf16: null operand");
+    MH_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0, "mh_gemm_bf16: lda/ldb must be multiples of 8 (%d, %d)", lda, ldb);
+    MH_CHECK_ARG(N % 4 == 0 && ldc % 4 == 0, "mh_gemm_bf16: N and ldc must be multiples of 4 (%d, %d)", N, ldc);
+    MH_CHECK_ARG((flags & MH_GEMM_OUT_F32) || (N % 8 == 0 && ldc % 8 == 0), "mh_gemm_bf16: bf16 output needs N, ldc %% 8 == 0");
+    MH_CHECK_ARG((flags & MH_GEMM_OUT_F32) || !(flags & MH_GEMM_RESIDUAL), "mh_gemm_bf16: residual epilogue needs f32 output");
+    MH_CHECK_ARG(!(flags & MH_GEMM_OUT_F32) || !(flags & (MH_GEMM_GELU | MH_GEMM_DGELU | MH_GEMM_MULAUX)), "mh_gemm_bf16: GELU / aux epilogues need bf16 output");
+    MH_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) % 16 == 0, "mh_gemm_bf16: bases must be 16-B aligned");
+    if (layout == 2) {
+        MH_CHECK_ARG(M % 8 == 0 && N % 8 == 0, "mh_gemm_bf16: TN needs M, N multiples of 8 (%d, %d)", M, N);
+    } else {
+        MH_CHECK_ARG(K % 8 == 0, "mh_gemm_bf16: K must be a multiple of 8 (%d)", K);
+        if (layout == 1) MH_CHECK_ARG(N % 8 == 0, "mh_gemm_bf16: NN needs N multiple of 8 (%d)", N);
+    }
+    MH_CHECK_ARG(!(flags & MH_GEMM_BIAS) || given(p.bias), "mh_gemm_bf16: bias flag without pointer");
+    MH_CHECK_ARG(!(flags & MH_GEMM_RESIDUAL) || (given(p.res) && ldr % 4 == 0), "mh_gemm_bf16: residual needs pointer, ldr%%4==0");
+    MH_CHECK_ARG(!(flags & (MH_GEMM_DGELU | MH_GEMM_MULAUX)) || (given(p.aux_in) && ldaux % 8 == 0), "mh_gemm_bf16: dgelu / mulaux need aux_in, ldaux %% 8 == 0");
+    MH_CHECK_ARG(!(flags & MH_GEMM_AUX_DGELU) || ((flags & MH_GEMM_GELU) && given(p.aux_out)), "mh_gemm_bf16: aux_dgelu needs the GELU epilogue and aux_out");
+    MH_CHECK_ARG(!((flags & MH_GEMM_DGELU) && (flags & MH_GEMM_MULAUX)), "mh_gemm_bf16: dgelu and mulaux exclude each other");
+    MH_CHECK_ARG(!(flags & MH_GEMM_AUX_U8) || ((flags & (MH_GEMM_AUX_DGELU | MH_GEMM_MULAUX)) && !(flags & MH_GEMM_DGELU)),
+                 "mh_gemm_bf16: MH_GEMM_AUX_U8 applies to the saved GELU derivative only (AUX_DGELU / MULAUX)");
+    MH_CHECK_ARG(!(flags & MH_GEMM_GELU) || !p.aux_out || ldaux % 8 == 0, "mh_gemm_bf16: ldaux %% 8");
+    MH_CHECK_ARG(!(flags & MH_GEMM_ATOMIC) || (flags & MH_GEMM_OUT_F32), "mh_gemm_bf16: atomic needs f32 output");
+    MH_CHECK_ARG(!(flags & MH_GEMM_COLSUM) || (given(p.colsum) && !(flags & MH_GEMM_OUT_F32)), "mh_gemm_bf16: colsum needs a pointer and bf16 output");
+    MH_CHECK_ARG(!(flags & MH_GEMM_ATOMIC) || !(flags & ~(MH_GEMM_ATOMIC | MH_GEMM_OUT_F32)),
+                 "mh_gemm_bf16: atomic accumulate excludes other epilogues");
+    return 0;
+}
+
+// Dispatch rule for the large-tile LDS-DMA kernel (gemm_dma.hip), from scripts/bench_tiles.py on MI355X: it wins (x1.05 to
+// x1.2, x1.8 on the K = 512 dgrad) for NT and NN problems whose 256x256 tiles fill the 256 CUs in whole waves (>= 90 % wave
+// efficiency: the M = 32768 decoder shapes); it loses when the tile count quantises badly (M = 8192 encoder shapes) and for
+// split-K wgrads (more splits -> more fp32 atomic passes).  The library reads no environment: a caller that wants another
+// kernel passes an explicit tile to mh_gemm_bf16_tile, or asks mh_gemm_bf16_resolve_tile for the rule over fewer families
+// (maestro_amd/hip.py maps MH_GEMM_DMA / MH_GEMM_TILE onto the former, MH_GEMM_PP=0 / MH_DMA_STAGGER=0 onto the latter).
+static bool prefer_dma(int layout, int M, int N, int K, int flags) {
+    if (layout == 2 || (flags & MH_GEMM_ATOMIC) || K % 32 != 0 || K < 256) return false;
+    const long tiles = (long)ceil_div(M, 256) * ceil_div(N, 256);
+    if (tiles < 256) return false;
+    const long waves = (tiles + 255) / 256;
+    return 10 * tiles >= 9 * 256 * waves;
+}
+
+// The tile that runs `p` when `tile` is asked for, or -2 when an explicit tile does not serve the problem: THE rule, for
+// mh_gemm_bf16_tile and mh_gemm_bf16_resolve_tile alike.  Reads shapes, strides and flags; launches nothing.
+static int gemm_resolve(int tile, int families, int layout, const GemmParams& p) {
+    const int M = p.M, N = p.N, K = p.K, flags = p.flags;
+    if (tile >= MH_TILE_PP_128 && tile <= MH_TILE_PP_128_DIAG5) return gemm_pp_serves(tile, layout, p) ? tile : -2;
+    if (tile > MH_TILE_REG_128 && tile < MH_TILE_PP_128) return gemm_dma_serves(tile, layout, p) ? tile : -2;
+    if (tile != MH_TILE_AUTO)   // the 64- / 192-row forms need a K-minor A and no column sums; otherwise the 128-row tile runs
+        return layout != 2 && !(flags & MH_GEMM_COLSUM) ? tile : MH_TILE_REG_128;
+    const bool dma = (families & MH_GEMM_FAMILY_DMA) && prefer_dma(layout, M, N, K, flags);
+    const long t128 = (long)ceil_div(M, 128) * ceil_div(N, 128);
+    // 192 x 128 tiles where the 128 x 128 tiling overshoots the 512 workgroup slots by a few tiles (M = 11392, N = 768: 534 tiles,
+    // i.e. a second, almost empty round; 360 tiles of 192 x 128 run in one): fc2 78.8 -> 76.5 us, fc1 dgrad 73.6 -> 69.5, qkv dgrad
+    // 56.8 -> 54.1 (scripts/bench_pp.py).  The 64 x 128 form (three workgroups per CU) gains 1-4 % at M = 8192, N = 768 and loses
+    // elsewhere: explicit tile only.
+    if ((families & MH_GEMM_FAMILY_192) && !dma && layout != 2 && !(flags & (MH_GEMM_COLSUM | MH_GEMM_ATOMIC)) && K >= 1536 &&
+        K % BK == 0 && t128 > 512 && t128 <= 576 && (long)ceil_div(M, 192) * ceil_div(N, 128) <= 512)
+        return MH_TILE_REG_192;
+    // Persistent 128x128 tile with the epilogue inside the next tile's main loop (gemm_pp.hip), scripts/bench_pp.py on the C3
+    // step's shapes with their real epilogues: +6...12 % on the plain bf16 NT outputs (qkv), +3...10 % on fp32 + residual
+    // (out-proj, fc2) and on the plain NN dgrads, +3 % on fc1; it LOSES 8-20 % on the fc2 dgrad (MULAUX + column sums: 256
+    // VGPRs, spills) -> never picked there.  Against the 256x256 LDS-DMA tile (M = 32768) it wins the short-K NT problems
+    // (qkv 61.0 vs 68.4 us, out-proj 38.8 vs 43.3, fc1 165 vs 173) and loses the long-K ones (fc2 136 vs 125).
+    // Round 3, second pass -- the rule below follows the kernels' times INSIDE the step (bench.py --shapes on the pretrain, probe and
+    // finetune steps, profiles/README.md), which differ from the isolated loops above (operands are cold, the fp32 residual is
+    // read, two group streams share the chip): the ping-pong tile keeps the NT problems between one round of workgroups and
+    // 8192 tiles (qkv +6 %, out-proj +11 %, fc2 +4 % at M = 32768; +2 ... 5 % at M = 8192), loses the fc1 (GELU) epilogue beyond
+    // ~2300 tiles (M = 32768: -7 % against the LDS-DMA tile, M = 12800: -2 %), loses 27 % on the segmentation head (M = 557056,
+    // 52224 tiles, 1.7 GB of output: the LDS-DMA tile's staged full-line stores), and is a tie or a loss on every NN (dgrad)
+    // problem in the step (M = 3200: -9 %), so those stay with the one-tile-per-workgroup / LDS-DMA kernels.
+    if ((families & MH_GEMM_FAMILY_PP) && !(flags & MH_GEMM_MULAUX) && layout == 0 && t128 >= 256 &&
+        ((flags & MH_GEMM_GELU) ? t128 <= 2304 : (!dma || (K < 1024 && t128 <= 8192))) && gemm_pp_serves(MH_TILE_PP_128, layout, p))
+        return MH_TILE_PP_128;
+    if (dma && gemm_dma_serves(MH_TILE_DMA_256, layout, p)) return MH_TILE_DMA_256;
+    return MH_TILE_REG_128;
+}
+
+extern "C" int mh_gemm_bf16_resolve_tile(int tile, int families, int layout, int M, int N, int K, int lda, int ldb, int ldc,
+                                         int ldr, int ldaux, int flags) {
+    GemmParams p;
+    gemm_fill(p, M, N, K, nullptr, lda, nullptr, ldb, nullptr, ldc, flags, nullptr, nullptr, ldr, nullptr, nullptr, ldaux, nullptr);
+    MH_CHECK_ARG(!(families & ~MH_GEMM_FAMILY_ALL), "mh_gemm_bf16_resolve_tile: unknown family bits 0x%x", families & ~MH_GEMM_FAMILY_ALL);
+    if (const int rc = gemm_check_args(false, tile, layout, p)) return rc;
+    return gemm_resolve(tile, families, layout, p);
+}
+
+extern "C" int mh_gemm_bf16_tile(int tile, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                                 void* C, int ldc, int flags, const float* bias, const float* res, int ldr,
+                                 const void* aux_in, void* aux_out, int ldaux, float* colsum, void* stream) {
+    GemmParams p;
+    gemm_fill(p, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, aux_in, aux_out, ldaux, colsum);
+    if (const int rc = gemm_check_args(true, tile, layout, p)) return rc;
+    const int run = gemm_resolve(tile, MH_GEMM_FAMILY_ALL, layout, p);
+    if (run == -2) return -2;   // an explicit tile that does not serve the problem: nothing launched, error string untouched
+    if (run >= MH_TILE_PP_128 && run <= MH_TILE_PP_128_DIAG5) return gemm_pp_launch(run, layout, p, (hipStream_t)stream);
+    if (run > MH_TILE_REG_128 && run < MH_TILE_PP_128) return gemm_dma_launch(run, layout, p, (hipStream_t)stream);
+    return gemm_reg_launch(run, layout, p, (hipStream_t)stream);
 }
 
 extern "C" int mh_gemm_bf16(int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,

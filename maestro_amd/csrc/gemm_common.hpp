@@ -114,15 +114,39 @@ __device__ __forceinline__ void atomic_max_pos(float* row, float v) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// gemm_dma.hip: the LDS-DMA tile family (tile = MH_TILE_DMA_*); -2 = not eligible, nothing launched
-int gemm_dma_dispatch(int tile, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
-                      int ldc, int flags, const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out,
-                      int ldaux, float* colsum, void* stream);
+// ---- host side, shared by every GEMM entry point (gemm*.hip)
+// The operand / epilogue half of the parameter block.  The family that launches sets tiles_m, tiles_n, k_per_split, fast and the
+// operand extents.
+static inline void gemm_fill(GemmParams& p, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
+                             int flags, const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out, int ldaux,
+                             float* colsum) {
+    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
+    p.bias = bias; p.res = res; p.aux_in = (const bf16_t*)aux_in; p.aux_out = (bf16_t*)aux_out; p.colsum = colsum;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldaux = ldaux; p.flags = flags;
+}
+// Bytes from the base of an operand to the end of its last element (the buffer descriptor's extent: everything beyond reads as
+// zero): `rows` x K with K contiguous (K-minor), or K x `rows` with the rows contiguous (K-major); `esize` bytes per element.
+static inline long gemm_extent(bool kmajor, int rows, int K, int ld, int esize = 2) {
+    return (kmajor ? (long)(K - 1) * ld + rows : (long)(rows - 1) * ld + K) * esize;
+}
+// a_bytes / b_bytes of bf16 operands in `layout` (0 NT, 1 NN, 2 TN)
+static inline void gemm_set_extents(GemmParams& p, int layout) {
+    p.a_bytes = (unsigned)gemm_extent(layout == 2, p.M, p.K, p.lda);
+    p.b_bytes = (unsigned)gemm_extent(layout != 0, p.N, p.K, p.ldb);
+}
+// A buffer descriptor addresses 2 GiB: `bytes` = what the kernel's whole tiles span from the base (tile rows x pitch, past M / N /
+// K), `margin` = room for the offsets it adds inside a tile row.
+static inline bool gemm_in_reach(long bytes, long margin = 65536) { return bytes < (1L << 31) - margin; }
 
-// gemm_pp.hip: the persistent 128x128 tile with a second accumulator set (tile = MH_TILE_PP_128); -2 = not eligible
-int gemm_pp_dispatch(int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int flags,
-                     const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out, int ldaux, float* colsum,
-                     void* stream, int diag = 0);
+// Kernel families other than the register-staged tile: `serves` is the family's FULL eligibility for a problem (shapes, strides and
+// flags of `p` only: no pointer is read, nothing is launched) and is what mh_gemm_bf16_resolve_tile (gemm.hip) asks; `launch` runs
+// a problem that `serves` accepted and cannot decline.
+// gemm_dma.hip: the LDS-DMA tile family (tile = MH_TILE_DMA_*)
+bool gemm_dma_serves(int tile, int layout, const GemmParams& p);
+int gemm_dma_launch(int tile, int layout, GemmParams& p, hipStream_t stream);
+// gemm_pp.hip: the persistent 128x128 tile with a second accumulator set (tile = MH_TILE_PP_128, or one of its DIAG builds)
+bool gemm_pp_serves(int tile, int layout, const GemmParams& p);
+int gemm_pp_launch(int tile, int layout, GemmParams& p, hipStream_t stream);
 
 // MH_GEMM_AUX_U8: the saved GELU derivative as a byte code, value = code / 200 - 0.13 (range [-0.129, 1.129] -> 0.2 .. 251.8)
 __device__ __forceinline__ u32x2 pack_dgelu_u8x8(f32x4 lo, f32x4 hi) {

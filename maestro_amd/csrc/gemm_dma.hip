@@ -212,13 +212,9 @@ __global__ __launch_bounds__(T::NT) void gemm_dma_grouped_tn_kernel(const MhGrou
 }
 
 template <class T>
-int launch_dma(int layout, GemmParams& p, hipStream_t s, bool stagger = true) {
-    const int M = p.M, N = p.N, K = p.K;
-    const bool a_kmajor = layout == 2, b_kmajor = layout != 0;
-    p.tiles_m = ceil_div(M, T::BM); p.tiles_n = ceil_div(N, T::BN);
-    const long a_reach = a_kmajor ? (long)(ceil_div(K, BK) * BK) * p.lda * 2 : (long)(p.tiles_m * T::BM) * p.lda * 2;
-    const long b_reach = b_kmajor ? (long)(ceil_div(K, BK) * BK) * p.ldb * 2 : (long)(p.tiles_n * T::BN) * p.ldb * 2;
-    if (a_reach + 65536 >= (1L << 31) || b_reach + 65536 >= (1L << 31)) return -2;
+void launch_dma(int layout, GemmParams& p, hipStream_t s, bool stagger = true) {
+    const int K = p.K;
+    p.tiles_m = ceil_div(p.M, T::BM); p.tiles_n = ceil_div(p.N, T::BN);
     int splits = 1;
     if (p.flags & MH_GEMM_ATOMIC) {
         const int tiles = p.tiles_m * p.tiles_n, ksteps = ceil_div(K, BK);
@@ -235,14 +231,13 @@ int launch_dma(int layout, GemmParams& p, hipStream_t s, bool stagger = true) {
             case 1: hipLaunchKernelGGL((gemm_dma_kernel<T, false, true, T::NW == 8>), grid, block, 0, s, p); break;
             default: hipLaunchKernelGGL((gemm_dma_kernel<T, true, true, T::NW == 8>), grid, block, 0, s, p); break;
         }
-        return 0;
+        return;
     }
     switch (layout) {
         case 0: hipLaunchKernelGGL((gemm_dma_kernel<T, false, false, false>), grid, block, 0, s, p); break;
         case 1: hipLaunchKernelGGL((gemm_dma_kernel<T, false, true, false>), grid, block, 0, s, p); break;
         default: hipLaunchKernelGGL((gemm_dma_kernel<T, true, true, false>), grid, block, 0, s, p); break;
     }
-    return 0;
 }
 
 }  // namespace
@@ -257,33 +252,36 @@ extern "C" int mh_gemm_grouped_tn(const MhGroupedGemm* table_device, int n_probl
     return 0;
 }
 
-// Called by mh_gemm_bf16 / mh_gemm_bf16_tile (gemm.hip) after argument validation.  Returns -2 (without touching the
-// error string) when the problem does not qualify for the DMA path, so that the caller can use the general kernel.
-int gemm_dma_dispatch(int tile, int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
-                      int ldc, int flags, const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out,
-                      int ldaux, float* colsum, void* stream) {
-    const bool a_kmajor = layout == 2, b_kmajor = layout != 0;
-    if ((!a_kmajor || !b_kmajor) && K % BK != 0) return -2;   // a K tail inside a K-minor row would wrap, not read zero
-    if (lda % 8 || ldb % 8) return -2;
-    GemmParams p;
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
-    p.bias = bias; p.res = res; p.aux_in = (const bf16_t*)aux_in; p.aux_out = (bf16_t*)aux_out; p.colsum = colsum;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldaux = ldaux; p.flags = flags;
-    const long a_ext = a_kmajor ? ((long)(K - 1) * lda + M) * 2 : ((long)(M - 1) * lda + K) * 2;
-    const long b_ext = b_kmajor ? ((long)(K - 1) * ldb + N) * 2 : ((long)(N - 1) * ldb + K) * 2;
-    p.fast = 1; p.a_bytes = (unsigned)a_ext; p.b_bytes = (unsigned)b_ext;
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
+// Everything the ring asks of a problem (mh_gemm_bf16_resolve_tile): whole K steps of 32 inside a K-minor operand (a K tail there
+// would wrap into the next row, not read zero; K-major operands zero-fill beyond K through the descriptor's extent) and both
+// operands' whole tiles inside the 2 GiB buffer-descriptor range.
+bool gemm_dma_serves(int tile, int layout, const GemmParams& p) {
+    int bm, bn;
     switch (tile) {
-        case MH_TILE_DMA_256: rc = launch_dma<T256>(layout, p, s); break;
-        case MH_TILE_DMA_256x128: rc = launch_dma<T256x128>(layout, p, s); break;
-        case MH_TILE_DMA_128x256: rc = launch_dma<T128x256>(layout, p, s); break;
-        case MH_TILE_DMA_128: rc = launch_dma<T128>(layout, p, s); break;
-        case MH_TILE_DMA_128x4: rc = launch_dma<T128q>(layout, p, s); break;
-        case MH_TILE_DMA_256_LOCKSTEP: rc = launch_dma<T256>(layout, p, s, false); break;
-        default: return -2;
+        case MH_TILE_DMA_256: case MH_TILE_DMA_256_LOCKSTEP: bm = T256::BM; bn = T256::BN; break;
+        case MH_TILE_DMA_256x128: bm = T256x128::BM; bn = T256x128::BN; break;
+        case MH_TILE_DMA_128x256: bm = T128x256::BM; bn = T128x256::BN; break;
+        case MH_TILE_DMA_128: case MH_TILE_DMA_128x4: bm = T128::BM; bn = T128::BN; break;
+        default: return false;
     }
-    if (rc) return rc;
+    const bool a_kmajor = layout == 2, b_kmajor = layout != 0;
+    if ((!a_kmajor || !b_kmajor) && p.K % BK != 0) return false;
+    const long k_rows = (long)ceil_div(p.K, BK) * BK;
+    return gemm_in_reach((a_kmajor ? k_rows : (long)ceil_div(p.M, bm) * bm) * p.lda * 2) &&
+           gemm_in_reach((b_kmajor ? k_rows : (long)ceil_div(p.N, bn) * bn) * p.ldb * 2);
+}
+
+int gemm_dma_launch(int tile, int layout, GemmParams& p, hipStream_t s) {
+    p.fast = 1;
+    gemm_set_extents(p, layout);
+    switch (tile) {
+        case MH_TILE_DMA_256: launch_dma<T256>(layout, p, s); break;
+        case MH_TILE_DMA_256x128: launch_dma<T256x128>(layout, p, s); break;
+        case MH_TILE_DMA_128x256: launch_dma<T128x256>(layout, p, s); break;
+        case MH_TILE_DMA_128: launch_dma<T128>(layout, p, s); break;
+        case MH_TILE_DMA_128x4: launch_dma<T128q>(layout, p, s); break;
+        default: launch_dma<T256>(layout, p, s, false); break;   // MH_TILE_DMA_256_LOCKSTEP
+    }
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -248,14 +248,11 @@ static int fp8_gemm_params(const char* fn, int M, int N, int K, const void* A8, 
     MH_CHECK_ARG(!(flags & MH_GEMM_AUX_U8) || ((flags & (MH_GEMM_AUX_DGELU | MH_GEMM_MULAUX)) && !(flags & MH_GEMM_DGELU)),
                  "%s: MH_GEMM_AUX_U8 applies to the saved GELU derivative only (AUX_DGELU / MULAUX)", fn);
     MH_CHECK_ARG(!(flags & MH_GEMM_COLSUM) || colsum, "%s: colsum flag without pointer", fn);
-    MH_CHECK_ARG((long)ceil_div(M, 256) * 256 * lda + 65536 < (1L << 31) && (long)ceil_div(N, 256) * 256 * ldb + 65536 < (1L << 31),
+    MH_CHECK_ARG(gemm_in_reach((long)ceil_div(M, 256) * 256 * lda) && gemm_in_reach((long)ceil_div(N, 256) * 256 * ldb),
                  "%s: operand beyond the 2 GiB buffer-descriptor range", fn);
-    p.A = (const bf16_t*)A8; p.B = (const bf16_t*)B8; p.C = C;
-    p.bias = bias; p.res = res; p.aux_in = (const bf16_t*)aux_in; p.aux_out = (bf16_t*)aux_out; p.colsum = colsum;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldaux = ldaux; p.flags = flags;
+    gemm_fill(p, M, N, K, A8, lda, B8, ldb, C, ldc, flags, bias, res, ldr, aux_in, aux_out, ldaux, colsum);
     p.k_per_split = K; p.fast = 1;
-    const long a_ext = (long)(M - 1) * lda + K, b_ext = (long)(N - 1) * ldb + K;   // bytes: rows beyond M / N read as zero
-    p.a_bytes = (unsigned)a_ext; p.b_bytes = (unsigned)b_ext;
+    p.a_bytes = (unsigned)gemm_extent(false, M, K, lda, 1); p.b_bytes = (unsigned)gemm_extent(false, N, K, ldb, 1);   // one byte per element
     return 0;
 }
 

@@ -388,33 +388,25 @@ static int pp_epilogue(int flags) {
     return -1;
 }
 
-// Called by mh_gemm_bf16_tile (gemm.hip) after argument validation.  -2 (error string untouched): the problem does not qualify
-// (layout TN, K % 64 != 0 or K < 512, N % 128 != 0, another epilogue, operands beyond the 2 GiB buffer-descriptor range).
-int gemm_pp_dispatch(int layout, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int flags,
-                     const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out, int ldaux, float* colsum,
-                     void* stream, int diag) {
-    const int epi = pp_epilogue(flags);
+// Everything the kernel asks of a problem (mh_gemm_bf16_resolve_tile): NT / NN, whole K steps and at least the EPI_STEPS that carry an
+// epilogue, whole tiles along N (the B tile base is not clipped), one of the four epilogue forms, and every buffer descriptor's tiles
+// (A, B, C, residual / aux) inside the 2 GiB range.
+bool gemm_pp_serves(int tile, int layout, const GemmParams& p) {
+    const int epi = pp_epilogue(p.flags), diag = tile - MH_TILE_PP_128;
 #ifndef MH_DIAG_TILES
-    if (diag != 0) return -2;   // MH_TILE_PP_128_DIAG1..5 write wrong outputs on purpose: compiled only under -DMH_DIAG_TILES
+    if (diag != 0) return false;   // MH_TILE_PP_128_DIAG1..5 write wrong outputs on purpose: compiled only under -DMH_DIAG_TILES
 #else
-    if (diag != 0 && (layout != 0 || !(epi == EPI_GELU || (epi == EPI_BF16 && diag == 1)))) return -2;   // no such ablation build
+    if (diag != 0 && (layout != 0 || !(epi == EPI_GELU || (epi == EPI_BF16 && diag == 1)))) return false;   // no such ablation build
 #endif
-    if (epi < 0 || layout == 2 || K % BK != 0 || K < EPI_STEPS * BK || N % BN != 0) return -2;
-    if (epi == EPI_GELU && !aux_out) return -2;
-    const bool b_kmajor = layout == 1;
-    GemmParams p;
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
-    p.bias = bias; p.res = res; p.aux_in = (const bf16_t*)aux_in; p.aux_out = (bf16_t*)aux_out; p.colsum = colsum;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldaux = ldaux; p.flags = flags;
-    p.tiles_m = ceil_div(M, BM); p.tiles_n = N / BN; p.k_per_split = K; p.fast = 1;
-    const long a_ext = ((long)(M - 1) * lda + K) * 2;
-    const long b_ext = b_kmajor ? ((long)(K - 1) * ldb + N) * 2 : ((long)(N - 1) * ldb + K) * 2;
-    const long a_reach = (long)(p.tiles_m * BM) * lda * 2, b_reach = b_kmajor ? (long)K * ldb * 2 : (long)N * ldb * 2;
-    const long c_reach = (long)(p.tiles_m * BM) * ldc * (epi == EPI_F32 ? 4 : 2);
-    const long x_reach = epi == EPI_F32 ? (long)(p.tiles_m * BM) * ldr * 4 : (long)(p.tiles_m * BM) * ldaux;
-    const long lim = (1L << 31) - 65536;
-    if (a_reach >= lim || b_reach >= lim || c_reach >= lim || x_reach >= lim) return -2;
-    p.a_bytes = (unsigned)a_ext; p.b_bytes = (unsigned)b_ext;
+    if (epi < 0 || layout == 2 || p.K % BK != 0 || p.K < EPI_STEPS * BK || p.N % BN != 0) return false;
+    const long rows = (long)ceil_div(p.M, BM) * BM;
+    return gemm_in_reach(rows * p.lda * 2) && gemm_in_reach((long)(layout == 1 ? p.K : p.N) * p.ldb * 2) &&
+           gemm_in_reach(rows * p.ldc * (epi == EPI_F32 ? 4 : 2)) && gemm_in_reach(epi == EPI_F32 ? rows * p.ldr * 4 : rows * p.ldaux);
+}
+
+int gemm_pp_launch(int tile, int layout, GemmParams& p, hipStream_t stream) {
+    p.tiles_m = ceil_div(p.M, BM); p.tiles_n = p.N / BN; p.k_per_split = p.K; p.fast = 1;
+    gemm_set_extents(p, layout);
     const int tiles = p.tiles_m * p.tiles_n;
     // MH_PP_TILES_PER_WG (build time): 0 = fully persistent (512 workgroups walk all tiles); n > 0: a workgroup walks at most n tiles
     // (shorter-lived workgroups let the dispatcher interleave another stream's kernel sooner, at one exposed epilogue per n tiles)
@@ -423,8 +415,8 @@ int gemm_pp_dispatch(int layout, int M, int N, int K, const void* A, int lda, co
 #endif
     int grid = tiles >= 512 ? 512 : (tiles + 7) / 8 * 8;   // two workgroups per CU; a multiple of 8 (XCD runs)
     if (MH_PP_TILES_PER_WG > 0) grid = max(grid, ((tiles + MH_PP_TILES_PER_WG - 1) / MH_PP_TILES_PER_WG + 7) / 8 * 8);
-    if (b_kmajor) launch_pp<true>(epi, grid, p, (hipStream_t)stream);
-    else launch_pp<false>(epi, grid, p, (hipStream_t)stream, diag);
+    if (layout == 1) launch_pp<true>(pp_epilogue(p.flags), grid, p, stream);
+    else launch_pp<false>(pp_epilogue(p.flags), grid, p, stream, tile - MH_TILE_PP_128);
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -250,9 +250,7 @@ extern "C" int mh_gemm_bf16_sk(int tile, int layout, int M, int N, int K, const 
     MH_CHECK_ARG(epi != SK_EPI_BF16 || ldc % 8 == 0, "mh_gemm_bf16_sk: bf16 output needs ldc %% 8 == 0");
     const bool b_kmajor = layout == 1;
     GemmParams p;
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
-    p.bias = bias; p.res = res; p.aux_in = nullptr; p.aux_out = nullptr; p.colsum = nullptr;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.ldaux = 0; p.flags = flags;
+    gemm_fill(p, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, nullptr, nullptr, 0, nullptr);
     if (tile == MH_TILE_SK_DMA_256) {
         const int rc = gemm_sk_dma_launch(layout, epi, p, workspace, grid, stream);
         if (rc) return rc;
@@ -262,14 +260,8 @@ extern "C" int mh_gemm_bf16_sk(int tile, int layout, int M, int N, int K, const 
     if (K % BK != 0 || K < 2 * BK || N % BN != 0) return -2;
     const int tbm = 32 * mt;
     p.tiles_m = ceil_div(M, tbm); p.tiles_n = N / BN; p.k_per_split = K; p.fast = 1;
-    const long a_ext = ((long)(M - 1) * lda + K) * 2;
-    const long b_ext = b_kmajor ? ((long)(K - 1) * ldb + N) * 2 : ((long)(N - 1) * ldb + K) * 2;
-    const long a_reach = (long)(p.tiles_m * tbm) * lda * 2, b_reach = b_kmajor ? (long)K * ldb * 2 : (long)N * ldb * 2;
-    const long c_reach = (long)(p.tiles_m * tbm) * ldc * (epi == SK_EPI_F32 ? 4 : 2);
-    const long r_reach = epi == SK_EPI_F32 ? (long)(p.tiles_m * tbm) * ldr * 4 : 0;
-    const long lim = (1L << 31) - 65536;
-    if (a_reach >= lim || b_reach >= lim || c_reach >= lim || r_reach >= lim) return -2;
-    p.a_bytes = (unsigned)a_ext; p.b_bytes = (unsigned)b_ext;
+    if (!sk_in_reach(layout, epi, p, tbm)) return -2;
+    gemm_set_extents(p, layout);
     SkArgs sk;
     sk.flags = reinterpret_cast<int*>(workspace);
     sk.err = sk.flags + SK_FLAG_BYTES / 4 - 1;

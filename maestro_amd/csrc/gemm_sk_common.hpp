@@ -215,5 +215,12 @@ __device__ __forceinline__ void sk_wait_flags(const SkArgs& sk, int wf, int lw) 
 
 }  // namespace
 
+// A, B, C and the residual of a stream-K problem with `tbm`-row tiles inside the 2 GiB buffer-descriptor range (host; p.tiles_m set)
+static inline bool sk_in_reach(int layout, int epi, const GemmParams& p, int tbm) {
+    const long rows = (long)p.tiles_m * tbm;
+    return gemm_in_reach(rows * p.lda * 2) && gemm_in_reach((long)(layout == 1 ? p.K : p.N) * p.ldb * 2) &&
+           gemm_in_reach(rows * p.ldc * (epi == SK_EPI_F32 ? 4 : 2)) && gemm_in_reach(epi == SK_EPI_F32 ? rows * p.ldr * 4 : 0);
+}
+
 // gemm_sk_dma.hip: the eight-wave 256 x 256 stream-K tile; -2 = not served
 int gemm_sk_dma_launch(int layout, int epi, GemmParams& p, void* workspace, int grid, void* stream);

@@ -202,14 +202,8 @@ int gemm_sk_dma_launch(int layout, int epi, GemmParams& p, void* workspace, int 
     const bool b_kmajor = layout == 1;
     if (p.K % BK != 0 || p.K < 4 * BK || p.N % T::BN != 0 || p.lda % 8 || p.ldb % 8) return -2;
     p.tiles_m = ceil_div(p.M, T::BM); p.tiles_n = p.N / T::BN; p.k_per_split = p.K; p.fast = 1;
-    const long a_ext = ((long)(p.M - 1) * p.lda + p.K) * 2;
-    const long b_ext = b_kmajor ? ((long)(p.K - 1) * p.ldb + p.N) * 2 : ((long)(p.N - 1) * p.ldb + p.K) * 2;
-    const long a_reach = (long)(p.tiles_m * T::BM) * p.lda * 2, b_reach = b_kmajor ? (long)p.K * p.ldb * 2 : (long)p.N * p.ldb * 2;
-    const long c_reach = (long)(p.tiles_m * T::BM) * p.ldc * (epi == SK_EPI_F32 ? 4 : 2);
-    const long r_reach = epi == SK_EPI_F32 ? (long)(p.tiles_m * T::BM) * p.ldr * 4 : 0;
-    const long lim = (1L << 31) - 65536;
-    if (a_reach >= lim || b_reach >= lim || c_reach >= lim || r_reach >= lim) return -2;
-    p.a_bytes = (unsigned)a_ext; p.b_bytes = (unsigned)b_ext;
+    if (!sk_in_reach(layout, epi, p, T::BM)) return -2;
+    gemm_set_extents(p, layout);
     SkArgs sk;
     sk.flags = reinterpret_cast<int*>(workspace);
     sk.err = sk.flags + SK_FLAG_BYTES / 4 - 1;

@@ -198,6 +198,24 @@ def _gemm_tile(tile, layout, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, 
                                    ptr(colsum), stream())
 
 
+FAMILY_DMA, FAMILY_PP, FAMILY_192, FAMILY_ALL = 1, 2, 4, 7   # MH_GEMM_FAMILY_*: what MH_TILE_AUTO may choose besides TILE_REG_128
+
+
+def resolve_tile(tile, layout, M, N, K, lda, ldb, ldc, ldr, ldaux, flags, families=FAMILY_ALL) -> int:  # noqa: N803
+    """mh_gemm_bf16_resolve_tile: the TILE_* that ``mh_gemm_bf16_tile(tile, ...)`` runs for this problem -- the library's own rule, asked
+    instead of copied; nothing is launched.  -2: the explicit DMA / ping-pong ``tile`` does not serve the problem."""
+    rc = lib().mh_gemm_bf16_resolve_tile(_I(tile), _I(families), _I(layout), _I(M), _I(N), _I(K), _I(lda), _I(ldb), _I(ldc), _I(ldr),
+                                         _I(ldaux), _I(flags))
+    if rc == -1:
+        _check(rc, "mh_gemm_bf16_resolve_tile")
+    return rc
+
+
+def _resolve(tile, args, families=FAMILY_ALL) -> int:
+    layout, M, N, K, _, lda, _, ldb, _, ldc, flags, _, _, ldr, _, _, ldaux, _ = args  # noqa: N806
+    return resolve_tile(tile, layout, M, N, K, lda, ldb, ldc, ldr, ldaux, flags, families)
+
+
 def _tune_gemm(key, args) -> int:
     best, best_ms = TILE_REG_128, float("inf")
     for tile in TILES:
@@ -226,7 +244,8 @@ def _pick_tile(layout, M, N, K, flags, args) -> int:  # noqa: N803
     if tile is None:
         # Experiment switches are resolved HERE, on the host side: the C library reads no environment (its header promises no
         # process-global state).  MH_GEMM_TILE=<id> forces one tile; MH_GEMM_DMA=0 keeps everything on the register-staged
-        # kernel, =1 sends every eligible problem to the 256x256 LDS-DMA tile; MH_DMA_STAGGER=0 picks its lockstep form.
+        # kernel, =1 sends every eligible problem to the 256x256 LDS-DMA tile; MH_DMA_STAGGER=0 picks its lockstep form.  Where a
+        # switch needs the library's rule (MH_GEMM_PP=0, MH_DMA_STAGGER=0) it asks mh_gemm_bf16_resolve_tile for it.
         forced = os.environ.get("MH_GEMM_TILE")
         if forced is not None:
             t = int(forced)
@@ -238,11 +257,12 @@ def _pick_tile(layout, M, N, K, flags, args) -> int:  # noqa: N803
             return t
         dma = os.environ.get("MH_GEMM_DMA", "")[:1]
         if os.environ.get("MH_GEMM_PP", "")[:1] == "0" and dma == "":   # A/B: the round-2 rule (no persistent ping-pong tile)
-            return TILE_DMA_256 if _uses_dma(layout, M, N, K, flags) else TILE_REG_128
+            return _resolve(TILE_AUTO, args, FAMILY_DMA)
         if dma == "0":
             return TILE_REG_128
         lockstep = os.environ.get("MH_DMA_STAGGER", "")[:1] == "0"
-        if (dma == "1" and layout != GEMM_TN and not (flags & ATOMIC)) or (lockstep and _uses_dma(layout, M, N, K, flags)):
+        if (dma == "1" and layout != GEMM_TN and not (flags & ATOMIC)) or (
+                lockstep and _resolve(TILE_AUTO, args, FAMILY_DMA) == TILE_DMA_256):
             return TILE_DMA_256_LOCKSTEP if lockstep else TILE_DMA_256
         if _tuning and not (flags & ATOMIC):   # accumulating outputs cannot be re-run for timing: the library's rule decides
             targs = list(args)
@@ -251,37 +271,6 @@ def _pick_tile(layout, M, N, K, flags, args) -> int:  # noqa: N803
         else:
             tile = TILE_AUTO
     return tile
-
-
-def _uses_192(layout, M, N, K, flags) -> bool:  # noqa: N803
-    """Mirror of the 192 x 128 rule in csrc/gemm.hip (labels kernel timings only)."""
-    if layout == GEMM_TN or (flags & (COLSUM | ATOMIC)) or K < 1536 or K % 64 or _uses_dma(layout, M, N, K, flags):
-        return False
-    t128 = -(-M // 128) * -(-N // 128)
-    return 512 < t128 <= 576 and -(-M // 192) * -(-N // 128) <= 512
-
-
-def _uses_pp(layout, M, N, K, flags) -> bool:  # noqa: N803
-    """Mirror of the MH_TILE_AUTO rule in csrc/gemm.hip + gemm_pp_dispatch's eligibility (labels kernel timings only)."""
-    if os.environ.get("MH_GEMM_PP", "")[:1] == "0":
-        return False
-    served = flags in (0, BIAS | GELU | AUX_DGELU | AUX_U8, OUT_F32 | BIAS | RESIDUAL)
-    if not served or layout == GEMM_TN or K % 64 or K < 512 or N % 128 or _uses_192(layout, M, N, K, flags):
-        return False
-    t128 = -(-M // 128) * -(-N // 128)
-    if layout != GEMM_NT or t128 < 256:
-        return False
-    if flags & GELU:
-        return t128 <= 2304
-    return not _uses_dma(layout, M, N, K, flags) or (K < 1024 and t128 <= 8192)
-
-
-def _auto_tile_name(layout, M, N, K, flags) -> int:  # noqa: N803
-    if _uses_192(layout, M, N, K, flags):
-        return TILE_REG_192
-    if _uses_pp(layout, M, N, K, flags):
-        return TILE_PP_128
-    return TILE_DMA_256 if _uses_dma(layout, M, N, K, flags) else TILE_REG_128
 
 
 def gemm(layout: int, M: int, N: int, K: int, A, lda: int, B, ldb: int, C, ldc: int, flags: int = 0, bias=None,  # noqa: N803
@@ -305,9 +294,9 @@ def gemm(layout: int, M: int, N: int, K: int, A, lda: int, B, ldb: int, C, ldc: 
         tile = _pick_tile(layout, M, N, K, flags, args)
     ev = None
     if _timer is not None:
-        named = tile if tile != TILE_AUTO else _auto_tile_name(layout, M, N, K, flags)
-        if named in (TILE_REG_64, TILE_REG_192) and (layout == GEMM_TN or (flags & COLSUM)):
-            named = TILE_REG_128       # (the tile height applies to K-minor A without column sums; the library falls back silently)
+        named = tile if tile in SK_TILES else _resolve(tile, args)   # the kernel the library will run for `tile`
+        if named == -2:                # a forced tile that does not serve the problem: the launch below falls back or raises
+            named = tile
         ev = _timer.record(_TILE_NAME[named].format(_LAYOUT_NAME[layout]), 2.0 * M * N * K, (M, N, K))
         ev[0].record()
     rc = _gemm_tile(tile, *args)
@@ -718,15 +707,6 @@ class KernelTimer:
 
 
 _timer: KernelTimer | None = None
-
-
-def _uses_dma(layout, M, N, K, flags) -> bool:
-    """Mirror of prefer_dma() in csrc/gemm.hip (labels kernel timings; decides where MH_DMA_STAGGER=0 applies)."""
-    if layout == GEMM_TN or (flags & ATOMIC) or K % 32 or K < 256:
-        return False
-    tiles = -(-M // 256) * -(-N // 256)
-    waves = -(-tiles // 256)
-    return tiles >= 256 and 10 * tiles >= 9 * 256 * waves
 
 
 def set_kernel_timer(t: KernelTimer | None) -> None:

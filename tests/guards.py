@@ -249,6 +249,7 @@ EXEMPT = {
     "mh_version": NO_DEVICE_BUFFER,
     "mh_last_error": NO_DEVICE_BUFFER,
     "mh_gemm_sk_workspace": NO_DEVICE_BUFFER,
+    "mh_gemm_bf16_resolve_tile": NO_DEVICE_BUFFER,
     "mh_groupnorm_partial_size": NO_DEVICE_BUFFER,
     "mh_layernorm_bwd_workspace": NO_DEVICE_BUFFER,
     "mh_attn_reduce_partial_rows": NO_DEVICE_BUFFER,

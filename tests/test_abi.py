@@ -72,7 +72,7 @@ def test_product_never_imports_the_oracle():
 
 def test_library_reads_no_environment():
     """include/maestro_hip.h promises "no global mutable state": every tile / ring choice is an argument, the experiment
-    switches (MH_GEMM_TILE, MH_GEMM_DMA, MH_DMA_STAGGER, MH_FP8_TILE) are parsed on the host side (maestro_amd/hip.py)."""
+    switches (MH_GEMM_TILE, MH_GEMM_DMA, MH_GEMM_PP, MH_DMA_STAGGER, MH_FP8_TILE) are parsed on the host side (maestro_amd/hip.py)."""
     for src in list((ROOT / "maestro_amd" / "csrc").glob("*.hip")) + list((ROOT / "maestro_amd" / "csrc").glob("*.hpp")):
         assert "getenv" not in src.read_text(), f"{src.name} reads the environment"
 
@@ -95,7 +95,7 @@ def test_retired_experiment_switches_are_refused(monkeypatch):
 def test_every_entry_point_has_a_guard_band_test_or_a_reason():
     """The ledger of tests/guards.py: every ``mh_*`` name of the header is in exactly one of ``GUARDED`` (called by a guard-band
     test) and ``EXEMPT`` (with a reason); a guarded name really occurs -- by name, through the hip.py wrapper of the same name, or
-    through the wrapper listed in ``VIA`` -- in one of the guard-test files; besides the six calls that touch no device buffer at
+    through the wrapper listed in ``VIA`` -- in one of the guard-test files; besides the seven calls that touch no device buffer at
     most ``MAX_OTHER_EXEMPT`` names are exempt."""
     from tests import guards
     header = (ROOT / "include" / "maestro_hip.h").read_text()
@@ -106,10 +106,10 @@ def test_every_entry_point_has_a_guard_band_test_or_a_reason():
     assert not neither, f"entry points without a guard-band test or an exemption: {sorted(neither)}"
     unknown = (guards.GUARDED | set(guards.EXEMPT)) - names
     assert not unknown, f"not declared in include/maestro_hip.h: {sorted(unknown)}"
-    no_buffer = {"mh_version", "mh_last_error", "mh_gemm_sk_workspace", "mh_groupnorm_partial_size", "mh_layernorm_bwd_workspace",
-                 "mh_attn_reduce_partial_rows"}
+    no_buffer = {"mh_version", "mh_last_error", "mh_gemm_sk_workspace", "mh_gemm_bf16_resolve_tile", "mh_groupnorm_partial_size",
+                 "mh_layernorm_bwd_workspace", "mh_attn_reduce_partial_rows"}
     other = {n: r for n, r in guards.EXEMPT.items() if n not in no_buffer}
-    assert guards.MAX_OTHER_EXEMPT == 6 and len(other) <= 6, f"{len(other)} exemptions besides the six size / version calls: {sorted(other)}"
+    assert guards.MAX_OTHER_EXEMPT == 6 and len(other) <= 6, f"{len(other)} exemptions besides the seven size / rule / version calls: {sorted(other)}"
     for n, reason in guards.EXEMPT.items():
         assert isinstance(reason, str) and reason.strip() and "\n" not in reason, f"{n}: a one-line reason is required"
     # the guard sections of the fp8 / MX files start at their "guard bands" banner: only calls below it count there

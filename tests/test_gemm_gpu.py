@@ -279,3 +279,67 @@ def test_gemm_other_tile_heights(tile_name, layout, shape):
             outs.append(C)
         torch.cuda.synchronize()
         assert torch.equal(outs[0], outs[1]), (flags, (outs[0].float() - outs[1].float()).abs().max().item())
+
+
+# (layout, M, N, K, epilogue) -> the tile the library's rule names: the smallest shape that reaches each outcome
+_RULE_CASES = [
+    (0, 200, 72, 104, "plain", "TILE_REG_128"),         # K tail: the register kernel's general path
+    (0, 2048, 2048, 512, "plain", "TILE_PP_128"),
+    (0, 2048, 2048, 512, "fc1", "TILE_PP_128"),
+    (1, 4096, 4096, 256, "plain", "TILE_DMA_256"),
+    (0, 11392, 768, 1536, "f32res", "TILE_REG_192"),
+    # K % 64 == 32: the ping-pong tile (K steps of 64) declines, the LDS-DMA ring (K steps of 32: csrc/gemm_ring.hpp) serves it
+    (0, 4096, 4096, 288, "plain", "TILE_DMA_256"),
+]
+
+
+@pytest.mark.parametrize("layout,M,N,K,epilogue,tile_name", _RULE_CASES)
+def test_unforced_gemm_runs_the_tile_the_resolver_names(monkeypatch, layout, M, N, K, epilogue, tile_name):  # noqa: N803
+    """``hip.gemm`` without ``tile`` and with ``tile=`` the answer of mh_gemm_bf16_resolve_tile write the same bits, and those
+    meet the fp64 bounds of tests/numerics.py: fp32 accumulation (K 2^-23 |A||B|) plus the epilogue's own terms.  For the GELU
+    output the accumulation and bias-add error of the pre-activation passes through GELU, whose slope lies in [-0.13, 1.13]
+    (include/maestro_hip.h, MH_GEMM_AUX_U8), hence the factor 1.13 on it -- and 1 + 2^-8 for its share of the bf16 rounding -- beside
+    ``gelu_bound``."""
+    from maestro_amd import hip
+    from tests import numerics as nm
+    dev = _dev()
+    for name in ("MH_GEMM_PP", "MH_GEMM_DMA", "MH_DMA_STAGGER", "MH_GEMM_TILE"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(hip, "_tile_choice", {})
+    a, b = nm.gemm_operands("randn", M, N, K)
+    a, b = a.to(dev), b.to(dev)
+    acc64, absprod = nm.gemm_ref64(a, b)
+    A = a.bfloat16().contiguous()                                             # noqa: N806
+    B = (b.t() if layout == 0 else b).bfloat16().contiguous()                 # noqa: N806
+    g = torch.Generator().manual_seed(K)
+    bias = torch.randn(N, generator=g).to(dev)
+    flags, kw, dt = 0, {}, torch.bfloat16
+    want, bound = acc64, nm.bf16_store_bound(acc64, absprod, K)
+    if epilogue == "fc1":
+        flags = hip.BIAS | hip.GELU | hip.AUX_DGELU | hip.AUX_U8
+        kw = dict(bias=bias, ldaux=N)
+        x64 = acc64 + bias.double()
+        want = nm.gelu64(x64)
+        bound = nm.gelu_bound(x64) + 1.13 * (1 + nm.HALF_ULP_BF16) * (nm.gemm_bound(absprod, K) + nm.U_F32 * x64.abs())
+    elif epilogue == "f32res":
+        flags, dt = hip.OUT_F32 | hip.BIAS | hip.RESIDUAL, torch.float32
+        res = torch.randn(M, N, generator=g).to(dev)
+        kw = dict(bias=bias, res=res, ldr=N)
+        b64 = bias.double()[None].expand(M, N)
+        want, bound = acc64 + b64 + res.double(), nm.bias_residual_bound(acc64, absprod, K, b64, res.double())
+    tile = hip.resolve_tile(hip.TILE_AUTO, layout, M, N, K, A.shape[1], B.shape[1], N, kw.get("ldr", 0), kw.get("ldaux", 0), flags)
+    assert tile == getattr(hip, tile_name)
+    outs, auxs = [], []
+    for t in (None, tile):
+        C = torch.full((M, N), float("nan"), device=dev, dtype=dt)           # noqa: N806
+        aux = torch.full((M, N), 77, device=dev, dtype=torch.uint8) if epilogue == "fc1" else None
+        hip.gemm(layout, M, N, K, A, A.shape[1], B, B.shape[1], C, N, flags, aux_out=aux, tile=t, **kw)
+        outs.append(C), auxs.append(aux)
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0].view(torch.int16 if dt == torch.bfloat16 else torch.int32),
+                       outs[1].view(torch.int16 if dt == torch.bfloat16 else torch.int32))
+    assert aux is None or torch.equal(auxs[0], auxs[1])
+    err = (outs[0].double() - want).abs()
+    ratio = nm.worst_ratio(err, bound)
+    print(f"{tile_name} {epilogue} ({M}, {N}, {K}): worst error / bound = {ratio:.3e}")
+    assert ratio <= 1.0, f"{int((err > bound).sum())} of {err.numel()} elements outside the bound"
