@@ -470,6 +470,23 @@ class SupervisedEngine(EngineBase):
                 out[t] = hb["logits"].clone()
         return out
 
+    def update_metric(self, name_target: str, metric, batch: dict | None = None) -> None:
+        """Feed the prediction metric of ``name_target`` (``maestro_amd/train/metric.py``) from the last ``forward``
+        (``base.py:143-146``): the head's confusion kernel on the logits buffer and the staged target, with the arguments
+        ``_forward_launches`` hands to ``hip.ce_loss`` / ``hip.bce_loss``.  One eager launch on the current stream, behind the
+        forward segment and outside the captured graphs (the destination depends on the stage); nothing is read back.  A batch
+        without a valid entry adds nothing (``base.py:126-127``)."""
+        hb = self.hb[name_target]
+        if batch is not None and name_target not in batch:
+            raise KeyError(f"batch has no target {name_target!r}")
+        tgt = self._staged[name_target]
+        if hb["kind"] == "multilabel_classif":
+            metric.update(hb["logits"], tgt, missing_val=hb["missing"])
+        elif hb["kind"] == "segment":
+            metric.update(hb["logits"], tgt, g=self.ref["G"], P=hb["P"], ld=hb["PPCp"], missing_val=hb["missing"])
+        else:
+            metric.update(hb["logits"], tgt, missing_val=hb["missing"])
+
     def logged_class_map(self, t: str) -> torch.Tensor:
         """Arg-max class map ``[S, S]`` of sample 0 of a raster target (the image logs of ``base.py:58-96`` keep only that
         sample): depatchifies that sample's g x g tokens only."""

@@ -38,6 +38,10 @@ def lib() -> ctypes.CDLL:
                                     "would measure the default path (INTEGRATION.md, profiles/r05_experiments.md, r06_experiments.md)")
         _lib = ctypes.CDLL(str(_LIB_PATH))
         _lib.mh_last_error.restype = ctypes.c_char_p
+        vp, ci = ctypes.c_void_p, ctypes.c_int          # include/maestro_hip_metrics.h
+        _lib.mh_confusion_ce.argtypes = [vp, vp, ci, ctypes.c_long, vp, ci, ci, ci, ci, ci, vp]
+        _lib.mh_confusion_bce.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp, ci, ci, vp]
+        _lib.mh_confusion_ce.restype = _lib.mh_confusion_bce.restype = ci
     return _lib
 
 
@@ -581,6 +585,29 @@ def ce_loss(logits, target, missing_val, n_valid, acc, dlogits, B, g, P, C, ld=N
 
 def bce_loss(logits, target, missing_val, acc, dlogits, B, C):  # noqa: N803
     call("mh_bce_loss", logits, target, _F(float(missing_val)), acc, dlogits, _I(B), _I(C))
+
+
+def confusion_ce(logits, target, missing_val, cm, B, g, P, C, ld=None):  # noqa: N803
+    """``cm[t, argmax]`` += 1 over the valid pixels (int64 ``[C, C]``; operands as ``ce_loss``; include/maestro_hip_metrics.h)."""
+    if cm.dtype != torch.int64 or cm.numel() != C * C or not cm.is_contiguous():
+        raise HipExtensionError(f"confusion_ce: cm must be a contiguous int64 [{C}, {C}] tensor")
+    call("mh_confusion_ce", logits, target, _I(target.element_size()), _L(int(missing_val)), cm, _I(B), _I(g), _I(P), _I(C),
+         _I(P * P * C if ld is None else ld))
+
+
+def logit_threshold(threshold: float) -> float:
+    """``sigmoid(x) > threshold``  <=>  ``x > log(threshold / (1 - threshold))`` (0 for the reference's 0.5)."""
+    import math
+    if not 0.0 < threshold < 1.0:
+        raise ValueError(f"detection threshold {threshold} outside (0, 1)")
+    return math.log(threshold / (1.0 - threshold))
+
+
+def confusion_bce(logits, target, missing_val, threshold, cm, B, C):  # noqa: N803
+    """``cm[l, target > 0.5, sigmoid(logit) > threshold]`` += 1 over the used rows (int64 ``[C, 2, 2]``; operands as ``bce_loss``)."""
+    if cm.dtype != torch.int64 or cm.numel() != C * 4 or not cm.is_contiguous():
+        raise HipExtensionError(f"confusion_bce: cm must be a contiguous int64 [{C}, 2, 2] tensor")
+    call("mh_confusion_bce", logits, target, _F(float(missing_val)), _F(logit_threshold(threshold)), cm, _I(B), _I(C))
 
 
 def zero_spans(base, spans, n_spans, max_len):

@@ -19,6 +19,7 @@ from torch import nn
 
 from maestro_amd import hip
 from maestro_amd.ssl.mae import mae_large, mae_medium, mae_small, mae_tiny
+from maestro_amd.train.metric import MonoLabelMetric, MultiLabelMetric
 
 try:  # optional dependency, exactly as in the reference's environment
     from pytorch_lightning import LightningModule as _Base
@@ -194,8 +195,19 @@ class SSLModule(_Base):
                  loss="l2_norm", use_date_enc=True, use_ema=False) -> None:
         super().__init__()
         self.dataset = datasets.dataset
-        self.metrics = nn.ModuleDict({f"{n}_{s}": MeanMetric() for n in ("loss_rec", "loss_pred")
-                                      for s in ("train", "val", "test")})
+        self.metrics = nn.ModuleDict()
+        for name_target, target in datasets.dataset.targets.items():       # base.py:34-50: one prediction metric per target and stage
+            for s in ("train", "val", "test"):
+                if target.type_target in ("classif", "segment"):
+                    metric = MonoLabelMetric(type_target=target.type_target, num_classes=target.num_classes)
+                elif target.type_target == "multilabel_classif":
+                    metric = MultiLabelMetric(num_labels=target.num_classes)
+                else:
+                    continue
+                self.metrics[f"{name_target}_{s}"] = metric
+        for n in ("loss_rec", "loss_pred"):                                 # base.py:52-56
+            for s in ("train", "val", "test"):
+                self.metrics[f"{n}_{s}"] = MeanMetric()
         self.norm_bands = {
             m: tuple(c.norm_bands if c.norm_bands is not None
                      else ([c.bands] if isinstance(c.bands, int) else [len(b) for b in c.bands]))
@@ -347,8 +359,12 @@ class SSLModule(_Base):
                  sync_dist=True)
 
     def compute_loss_pred(self, engine, stage: str) -> torch.Tensor:
-        """``loss_pred`` of the last supervised forward (``base.py:98-151``; computed on the GPU by mh_ce_loss / mh_bce_loss)."""
+        """``loss_pred`` of the last supervised forward (``base.py:98-151``; computed on the GPU by mh_ce_loss / mh_bce_loss), then
+        every target's prediction metric of this stage (``base.py:143-146``): one confusion-matrix launch per target on the
+        engine's logits, no host read.  A target without a valid entry in the batch leaves its metric as it is."""
         loss = _EngineLoss.apply(self._anchor, engine, engine.loss_acc)
+        for name_target in engine.hb:
+            engine.update_metric(name_target, self.metrics[f"{name_target}_{stage}"])
         self.metrics[f"loss_pred_{stage}"].update(loss)
         return loss
 
