@@ -405,6 +405,73 @@ class Stack:
         return cur, cur16
 
 
+# ======================================================================================= patch-embed end
+class PatchEmbedEnd:
+    """Buffers and launch sequence of the patch embedding of one modality spec (one band-group of one raster): patchify ->
+    conv GEMM -> GroupNorm + positional / date encodings into a group sequence, and its backward.  Shared by the step
+    engines; what differs between them arrives as arguments (a loss target or none, the destination sequence, whether the
+    conv-gradient staging buffer still needs clearing)."""
+
+    def __init__(self, eng: "EngineBase", s) -> None:
+        self.eng, self.s = eng, s
+        m, dev, E = eng.model, eng.device, eng.E  # noqa: N806
+        e = lambda *sh, dt=F32: torch.empty(*sh, dtype=dt, device=dev)  # noqa: E731
+        z = lambda *sh, dt=F32: torch.zeros(*sh, dtype=dt, device=dev)  # noqa: E731
+        T, BD = s.Beff * s.n_tok, s.Beff * s.D  # noqa: N806
+        # ``eng.mb[name]`` is this dict; the engines add their own keys (loss target, decoder-side buffers) to it
+        self.buf = dict(
+            cols=e(T, s.Kpad, dt=BF16), yconv=e(T, E), gn_partial=e(hip.groupnorm_partial_size(BD, s.L, E)), gn_stats=e(BD, 2),
+            gn_sums=e(BD, 2), pos_enc=m.pos_enc_rows[s.name].to(dev), norm_bands=torch.tensor(s.norm_bands, dtype=I32, device=dev),
+            w_conv16=z(E, s.Kpad, dt=BF16), dw_conv=z(E, s.Kpad), dyc=e(T, E, dt=BF16),
+            pe=m.patch_embed[s.embed].patchify_bands[s.gi])
+
+    def pack(self) -> None:
+        """The K-padded bf16 copy of the conv weight (wherever the bf16 shadows are refreshed)."""
+        b, s = self.buf, self.s
+        hip.pack_rows_bf16(b["pe"].conv.weight, b["w_conv16"], self.eng.E, s.K, s.Kpad)
+
+    def forward(self, batch: dict, gbuf: dict, xg: torch.Tensor, Lgroup: int, target=None, normalise: bool = False) -> None:  # noqa: N803
+        """Embeds ``batch[s.src]`` into rows ``tok_off ..`` of the group sequence ``xg`` [Beff, Lgroup, E]; ``target``: also
+        writes the (normalised) loss target of the modality."""
+        eng, s, b = self.eng, self.s, self.buf
+        m, B, E = eng.model, eng.B, eng.E  # noqa: N806
+        BD, T = s.Beff * s.D, s.Beff * s.n_tok  # noqa: N806
+        if s.G == 1 and target is not None:
+            hip.patchify(batch[s.src], b["cols"], target, BD, s.C, s.S, s.P, s.Kpad, b["norm_bands"], len(s.norm_bands),
+                         normalise, s.rescale_elev)
+        else:   # one band-group: its channel window for the conv (the whole raster when there is one band-group) ...
+            hip.patchify_bands(batch[s.src], b["cols"], None, BD, s.C_src, s.c0, s.C, s.S, s.P, s.Kpad, None, 0, False,
+                               s.rescale_elev)
+            if target is not None and s.gi == 0:   # ... and the modality's target once, over all channels
+                k_src = s.C_src * s.P * s.P
+                hip.patchify_bands(batch[s.src], None, target, BD, s.C_src, 0, s.C_src, s.S, s.P, (k_src + 7) // 8 * 8,
+                                   b["norm_bands"], len(s.norm_bands), normalise, s.rescale_elev)
+        dates, ref_date = batch[f"{s.src}_dates"], batch["ref_date"]
+        if s.D != s.Dates:   # dates folded into the batch: one date row per sequence
+            hip.date_features(dates, ref_date, gbuf["dates"].view(B, s.Dates, 8), B, s.Dates, s.Dates, 0, m.fac_date_enc)
+        else:
+            hip.date_features(dates, ref_date, gbuf["dates"], B, s.D, gbuf["n_dates"], s.date_off, m.fac_date_enc)
+        pe = b["pe"]
+        hip.gemm(hip.GEMM_NT, T, E, s.Kpad, b["cols"], s.Kpad, b["w_conv16"], s.Kpad, b["yconv"], E, hip.OUT_F32 | hip.BIAS,
+                 bias=pe.conv.bias)
+        hip.groupnorm_stats(b["yconv"], b["gn_partial"], b["gn_stats"], BD, s.L, E)
+        hip.embed_finish(b["yconv"], b["gn_stats"], pe.norm.weight, pe.norm.bias, b["pos_enc"], gbuf["dates"], gbuf["n_dates"],
+                         s.date_off, xg, s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
+
+    def backward(self, dxg: torch.Tensor, Lgroup: int, clear_dw: bool) -> None:  # noqa: N803
+        """``dxg`` [Beff, Lgroup, E]: gradient of the group sequence.  ``clear_dw``: the conv-gradient staging buffer (split-K
+        atomics accumulate into it) was not cleared since the last backward."""
+        eng, s, b = self.eng, self.s, self.buf
+        ps, E, pe, T = eng.store, eng.E, b["pe"], s.Beff * s.n_tok  # noqa: N806
+        hip.embed_finish_bwd(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight), ps.g(pe.norm.bias),
+                             b["gn_sums"], s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
+        if clear_dw:
+            b["dw_conv"].zero_()
+        hip.gemm(hip.GEMM_TN, E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, b["dw_conv"], s.Kpad, hip.OUT_F32 | hip.ATOMIC)
+        hip.unpack_rows_add(b["dw_conv"], ps.g(pe.conv.weight), E, s.K, s.Kpad)
+        hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+
+
 # hipGraphs of engines that have been garbage-collected, kept alive until the next SAFE point.  An engine is a reference cycle, so
 # Python finalises a dropped one whenever the cyclic collector happens to run -- possibly between two launches of ANOTHER engine's
 # step, with that engine's graphs in flight.  Destroying CUDAGraph objects at such a moment (hipGraphExecDestroy + release of their
@@ -502,6 +569,10 @@ class EngineBase:
         prio = int(os.environ.get("MAESTRO_SIDE_PRIORITY", "0"))
         self.side_streams = [torch.cuda.Stream(device=device, priority=prio) for _ in range(max(0, n_side_streams))]
         self._wgrad_stream = torch.cuda.Stream(device=device)   # plan "ovl": deferred weight gradients under the next segment
+        self._wgrad_tables = {}     # (stack tag, lo, hi) per item -> (GroupedTN, ColsumBatch), see _launch_wgrads
+        # a zero_grad since the last backward has cleared the patch-embed conv-gradient staging buffers (``mb[..]["dw_conv"]``);
+        # otherwise the backward's launch list clears them itself
+        self._dw_conv_clear = False
 
     def _stable_inputs(self, batch: dict) -> dict:
         """The captured launch segments bake device addresses in.  A tensor that keeps its address from step to step (a
@@ -526,6 +597,55 @@ class EngineBase:
                 if buf.data_ptr() != t.data_ptr():
                     buf.copy_(t)
                 out[k] = buf
+        return out
+
+    def _alloc_embed(self) -> None:
+        """One ``PatchEmbedEnd`` per modality spec; ``mb[name]`` is its buffer dict."""
+        self.embed = {name: PatchEmbedEnd(self, s) for name, s in self.mods.items()}
+        self.mb = {name: end.buf for name, end in self.embed.items()}
+
+    def _pack_conv_weights(self) -> None:
+        for end in self.embed.values():
+            end.pack()
+
+    def _stage_inputs(self, batch: dict) -> dict:
+        """Input staging (mim.py:427-432): checks the rasters and their dates, gives every device tensor a stable address and
+        resizes rasters that do not arrive at ``image_size`` into an engine-owned buffer; sets the segments' address key."""
+        sources = [parts[0] for parts in self.model.src_specs.values()]      # one spec per batch entry (band-group 0)
+        for s in sources:
+            img = batch[s.src]
+            if img.dtype != F32 or not img.is_contiguous() or not img.is_cuda:
+                raise ValueError(f"batch[{s.src!r}] must be a contiguous float32 GPU tensor")
+            d = batch[f"{s.src}_dates"]
+            if d.dtype != torch.int16 or not d.is_contiguous():     # (mh_date_features reads int16_t)
+                raise ValueError(f"batch['{s.src}_dates'] must be a contiguous int16 tensor [B, D, 3]")
+        batch = self._stable_inputs(batch)
+        for s in sources:
+            img = batch[s.src]
+            if tuple(img.shape[-2:]) != (s.S, s.S) or self.model.interpolate != "nearest":
+                mode = {"nearest": 0, "bilinear": 1, "bicubic": 2}.get(self.model.interpolate)
+                if mode is None:
+                    raise ValueError(f"Invalid interpolate mode {self.model.interpolate!r} (nearest, bilinear, bicubic)")
+                buf = self.mb[s.name].get("resized")
+                if buf is None:
+                    buf = self.mb[s.name]["resized"] = torch.empty(self.B, s.Dates, s.C_src, s.S, s.S, dtype=F32, device=self.device)
+                hip.resize(img, buf, self.B * s.Dates * s.C_src, img.shape[-2], img.shape[-1], s.S, s.S, mode)
+                batch[s.src] = buf
+        self._staged = batch
+        self._cur_key = tuple(batch[k].data_ptr() for k in sorted(batch) if isinstance(batch[k], torch.Tensor))
+        return batch
+
+    def returned_batch(self, batch: dict) -> dict:
+        """The reference returns the (in place) resized / elevation-rescaled batch (mim.py:425-437, SURVEY Q13)."""
+        out = dict(batch)
+        sources = [parts[0] for parts in self.model.src_specs.values()]
+        out.update({s.src: self._staged[s.src] for s in sources})  # resized rasters (mim.py:427-432)
+        for s in sources:
+            if s.rescale_elev:
+                img = out[s.src]
+                res = torch.empty_like(img)
+                hip.rescale_elev(img, res, img.shape[0] * img.shape[1], s.C_src, s.S)
+                out[s.src] = res
         return out
 
     def _grads_ready(self, module) -> None:
@@ -594,6 +714,29 @@ class EngineBase:
                 self.warm_passes_run += 1
         finally:
             self.grad_hook, self.use_graphs = hook, graphs
+
+    def _first_step_passes(self, one_pass) -> None:
+        """Head of every ``forward``; only the first step does anything.  ``one_pass()``: forward + zero_grad + backward of the
+        current step (same inputs, same draws): the in-step GEMM tile tuning, then the start-up passes."""
+        if self.instep_tune:
+            self._instep_tune(one_pass)
+        if self.warm_passes > 0:
+            self._warm_up(one_pass)
+
+    def _launch_wgrads(self, items) -> None:
+        """One grouped launch for the deferred weight gradients of ``items`` = [(stack, lo, hi)]; the descriptor table is
+        built on first use (always an eager run: segments are captured on their second run)."""
+        items = [(st, lo, hi) for st, lo, hi in items if hi > lo]
+        if not items:
+            return
+        key = tuple((st.tag, lo, hi) for st, lo, hi in items)
+        table = self._wgrad_tables.get(key)
+        if table is None:
+            probs = [p for st, lo, hi in items for p in st.wgrad_problems(lo, hi)]
+            jobs = [j for st, lo, hi in items for j in st.reduce_jobs(lo, hi)]
+            table = self._wgrad_tables[key] = (hip.GroupedTN(probs, self.device), hip.ColsumBatch(jobs, self.device))
+        table[1].launch()   # LayerNorm / bias parameter gradients of the same layers: one batched column-sum launch
+        table[0].launch()
 
     @contextlib.contextmanager
     def _tuning_pass(self, what: str):
@@ -710,7 +853,7 @@ class MAEEngine(EngineBase):
         self.wgrad_mode = os.environ.get("MAESTRO_WGRAD", "auto")
         if self.wgrad_mode not in ("auto", "fused", "deferred"):
             raise ValueError(f"MAESTRO_WGRAD={self.wgrad_mode!r}: expected auto, fused or deferred")
-        self._wgrad_tables, self._wgrad_plans, self._zero_lists = {}, {}, {}
+        self._wgrad_plans, self._zero_lists = {}, {}
         self._h2d_done = [None] * RING   # per ring slot: event after the mask uploads that last used it
         self._opt = None                 # overlapped optimizer (attach_optimizer)
         self.host_wait_s = 0.0           # time the host spent blocked on that ring (diagnostic: not issue work)
@@ -756,21 +899,15 @@ class MAEEngine(EngineBase):
         m, dev, E, Dd = self.model, self.device, self.E, self.Dd  # noqa: N806
         e = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
         z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
-        self.mb = {}
+        self._alloc_embed()
         for name, s in self.mods.items():
             T = s.Beff * s.n_tok  # noqa: N806
-            BD = s.Beff * s.D  # noqa: N806
-            pe = m.patch_embed[s.embed].patchify_bands[s.gi]
             # a modality with several band-groups: ONE loss target over all its channels (the norm_bands groups of
             # model.py:219-229 ignore the band-groups) and one masked-element count, owned by band-group 0, shared by the rest
             first = self.mb[m.src_specs[s.src][0].name] if s.gi else None
-            self.mb[name] = dict(
-                cols=e(T, s.Kpad, dt=BF16), target=first["target"] if first else e(T, s.C_src * s.P * s.P), yconv=e(T, E),
-                gn_partial=e(hip.groupnorm_partial_size(BD, s.L, E)), gn_stats=e(BD, 2), gn_sums=e(BD, 2),
-                pos_enc=m.pos_enc_rows[name].to(dev), norm_bands=torch.tensor(s.norm_bands, dtype=I32, device=dev),
-                w_conv16=z(E, s.Kpad, dt=BF16), dw_conv=z(E, s.Kpad), dyc=e(T, E, dt=BF16),
-                hdec=e(T, Dd, dt=BF16), mean_f=e(T), rstd_f=e(T), rec=e(T, s.K), drec=e(T, s.K, dt=BF16),
-                dh=e(T, Dd, dt=BF16), cnt=first["cnt"] if first else z(1, dt=I32), pe=pe)
+            self.mb[name].update(
+                target=first["target"] if first else e(T, s.C_src * s.P * s.P), hdec=e(T, Dd, dt=BF16), mean_f=e(T), rstd_f=e(T),
+                rec=e(T, s.K), drec=e(T, s.K, dt=BF16), dh=e(T, Dd, dt=BF16), cnt=first["cnt"] if first else z(1, dt=I32))
         self.gb = {}
         self.enc, self.dec = {}, {}
         for g in self.groups:
@@ -827,9 +964,7 @@ class MAEEngine(EngineBase):
         """Derived weight copies beyond the flat bf16 shadow (called wherever the shadows are refreshed: engine start,
         parameters changed behind the engine's back, after every fused AdamW step): the K-padded patch-embed weights and,
         in fp8 mode, the e4m3 weight shadows with their scales."""
-        for name, s in self.mods.items():
-            b = self.mb[name]
-            hip.pack_rows_bf16(b["pe"].conv.weight, b["w_conv16"], self.E, s.K, s.Kpad)
+        super()._pack_conv_weights()
         if self.fp8 is not None:
             if fp8_done:                                  # the fused AdamW has just written the shadows itself
                 self.fp8.refresh_transposed()
@@ -905,18 +1040,12 @@ class MAEEngine(EngineBase):
             n2, s2 = self.draw_masks()
             noise = noise if noise is not None else n2
             struct = struct if struct is not None else s2
-        if self.instep_tune:           # first step: pick the GEMM tiles between the step's own kernels (same inputs, same draws)
-            def one_pass():
-                self.forward(batch, noise=noise, struct=struct)
-                self.zero_grad()
-                self.backward()
-            self._instep_tune(one_pass)
-        if self.warm_passes > 0:
-            def warm_pass():
-                self.forward(batch, noise=noise, struct=struct)
-                self.zero_grad()
-                self.backward()
-            self._warm_up(warm_pass)
+
+        def one_pass():
+            self.forward(batch, noise=noise, struct=struct)
+            self.zero_grad()
+            self.backward()
+        self._first_step_passes(one_pass)
         # host -> pinned ring slot -> device (outside any graph).  A slot is reused every RING steps; only then do we wait
         # for the async copies that last read it (the host may run several steps ahead of the GPU, but a per-step
         # hipEventSynchronize was measured to wake up ~10 ms late and starve the queue).
@@ -953,31 +1082,9 @@ class MAEEngine(EngineBase):
         ev = torch.cuda.Event()
         ev.record()
         self._h2d_done[slot] = ev
-        sources = [parts[0] for parts in self.model.src_specs.values()]      # one spec per batch entry (band-group 0)
-        for s in sources:
-            img = batch[s.src]
-            if img.dtype != F32 or not img.is_contiguous() or not img.is_cuda:
-                raise ValueError(f"batch[{s.src!r}] must be a contiguous float32 GPU tensor")
-        batch = self._stable_inputs(batch)
-        for s in sources:
-            img = batch[s.src]
-            if tuple(img.shape[-2:]) != (s.S, s.S) or self.model.interpolate != "nearest":
-                # input staging (mim.py:427-432): resize to image_size on the GPU into an engine-owned buffer
-                mode = {"nearest": 0, "bilinear": 1, "bicubic": 2}.get(self.model.interpolate)
-                if mode is None:
-                    raise ValueError(f"Invalid interpolate mode {self.model.interpolate!r} (nearest, bilinear, bicubic)")
-                buf = self.mb[s.name].get("resized")
-                if buf is None:
-                    buf = self.mb[s.name]["resized"] = torch.empty(self.B, s.Dates, s.C_src, s.S, s.S, dtype=F32, device=self.device)
-                hip.resize(img, buf, self.B * s.Dates * s.C_src, img.shape[-2], img.shape[-1], s.S, s.S, mode)
-                batch[s.src] = buf
-            d = batch[f"{s.src}_dates"]
-            if d.dtype != torch.int16 or not d.is_contiguous():
-                raise ValueError(f"batch['{s.src}_dates'] must be a contiguous int16 tensor [B, D, 3]")
-        self._staged = batch
-        key = self._cur_key = tuple(batch[k].data_ptr() for k in sorted(batch) if isinstance(batch[k], torch.Tensor))
+        batch = self._stage_inputs(batch)
         with self._tuning_pass("forward"):
-            self._segment("forward" if self._opt is None else "forward:opt", key, lambda: self._forward_launches(batch))
+            self._segment("forward" if self._opt is None else "forward:opt", self._cur_key, lambda: self._forward_launches(batch))
         if self._opt is not None:
             self.store.mark_synced()   # the optimizer stages inside the forward refreshed the bf16 shadows themselves
         return self.loss_acc
@@ -1081,7 +1188,6 @@ class MAEEngine(EngineBase):
     def _forward_launches(self, batch: dict) -> None:
         m, E, Dd = self.model, self.E, self.Dd  # noqa: N806
         self.loss_acc.zero_()
-        ref_date = batch["ref_date"]
         if self._opt is not None:
             self._opt_launch_stages()
 
@@ -1091,33 +1197,7 @@ class MAEEngine(EngineBase):
                 self._opt_wait("embed")
                 # ---- embed: patchify -> conv GEMM -> GroupNorm + encodings into the group sequence
                 for s in g.mods:
-                    b = self.mb[s.name]
-                    BD = s.Beff * s.D  # noqa: N806
-                    if s.G == 1:
-                        hip.patchify(batch[s.name], b["cols"], b["target"], BD, s.C, s.S, s.P, s.Kpad, b["norm_bands"],
-                                     len(s.norm_bands), self.normalise, s.rescale_elev)
-                    else:   # one band-group: its channel window for the conv; the modality's target once, over all channels
-                        hip.patchify_bands(batch[s.src], b["cols"], None, BD, s.C_src, s.c0, s.C, s.S, s.P, s.Kpad, None, 0, False,
-                                           s.rescale_elev)
-                        if s.gi == 0:
-                            k_src = s.C_src * s.P * s.P
-                            hip.patchify_bands(batch[s.src], None, b["target"], BD, s.C_src, 0, s.C_src, s.S, s.P,
-                                               (k_src + 7) // 8 * 8, b["norm_bands"], len(s.norm_bands), self.normalise,
-                                               s.rescale_elev)
-                    dates = batch[f"{s.src}_dates"]
-                    if s.D != s.Dates:   # dates folded into the batch: one date row per sequence
-                        hip.date_features(dates, ref_date, gbuf["dates"].view(self.B, s.Dates, 8), self.B, s.Dates, s.Dates,
-                                          0, m.fac_date_enc)
-                    else:
-                        hip.date_features(dates, ref_date, gbuf["dates"], self.B, s.D, gbuf["n_dates"], s.date_off,
-                                          m.fac_date_enc)
-                    pe = b["pe"]
-                    T = s.Beff * s.n_tok  # noqa: N806
-                    hip.gemm(hip.GEMM_NT, T, E, s.Kpad, b["cols"], s.Kpad, b["w_conv16"], s.Kpad, b["yconv"], E,
-                             hip.OUT_F32 | hip.BIAS, bias=pe.conv.bias)
-                    hip.groupnorm_stats(b["yconv"], b["gn_partial"], b["gn_stats"], BD, s.L, E)
-                    hip.embed_finish(b["yconv"], b["gn_stats"], pe.norm.weight, pe.norm.bias, b["pos_enc"], gbuf["dates"],
-                                     gbuf["n_dates"], s.date_off, gbuf["xg"], s.Beff, s.D, s.L, E, s.tok_off, g.L)
+                    self.embed[s.name].forward(batch, gbuf, gbuf["xg"], g.L, self.mb[s.name]["target"], self.normalise)
                 # ---- mask + gather + per-group encoder + its final LN (into the joint sequence, or bf16 for enc_to_dec)
                 hip.mask_select(gbuf["noise"], gbuf["struct"], gbuf["vis"], gbuf["msk"], gbuf["inv"], gbuf["mask"], g.Beff,
                                 g.L, g.k)
@@ -1281,21 +1361,6 @@ class MAEEngine(EngineBase):
     def _all_stacks(self) -> list:
         return list(self.dec.values()) + ([self.joint] if self.joint is not None else []) + list(self.enc.values())
 
-    def _launch_wgrads(self, items) -> None:
-        """One grouped launch for the deferred weight gradients of ``items`` = [(stack, lo, hi)]; the descriptor table is
-        built on first use (always an eager run: segments are captured on their second run)."""
-        items = [(st, lo, hi) for st, lo, hi in items if hi > lo]
-        if not items:
-            return
-        key = tuple((st.tag, lo, hi) for st, lo, hi in items)
-        table = self._wgrad_tables.get(key)
-        if table is None:
-            probs = [p for st, lo, hi in items for p in st.wgrad_problems(lo, hi)]
-            jobs = [j for st, lo, hi in items for j in st.reduce_jobs(lo, hi)]
-            table = self._wgrad_tables[key] = (hip.GroupedTN(probs, self.device), hip.ColsumBatch(jobs, self.device))
-        table[1].launch()   # LayerNorm / bias parameter gradients of the same layers: one batched column-sum launch
-        table[0].launch()
-
     def _with_overlapped_wgrads(self, fn, previous, own):
         """Plan "ovl": the weight gradients of the PREVIOUS segment run on a side stream under this segment's dgrad chain (their
         operands -- the per-layer dY / activation buffers -- are final, nothing here writes them); the last segment also issues
@@ -1344,7 +1409,7 @@ class MAEEngine(EngineBase):
         key = getattr(self, "_cur_key", None)
         plan = self._plan = self._wgrad_plan()
         sfx = f":{plan}:{'h' if self.grad_hook is not None else 'n'}"   # graphs are specific to the launch plan
-        if not getattr(self, "_dw_conv_clear", False):
+        if not self._dw_conv_clear:
             sfx += ":nz"     # no zero_grad since the last backward: this launch list clears the conv-gradient staging buffers itself
         if self.fp8 is not None and self.fp8.dgrad:
             sfx += ":f8" if self.fp8.grad_ready else ":cal"       # (the first backward calibrates the gradient scales in bf16)
@@ -1433,7 +1498,6 @@ class MAEEngine(EngineBase):
         """Layers ``hi-1 .. lo`` of every group encoder (groups on parallel streams); ``first`` also runs the final-LN
         backward, ``last`` the scatter + patch-embed backward."""
         m, E, ps = self.model, self.E, self.store  # noqa: N806
-        AT = hip.OUT_F32 | hip.ATOMIC  # noqa: N806
 
         def side(g):
             def run():
@@ -1464,17 +1528,7 @@ class MAEEngine(EngineBase):
             # patch-embed backward per modality
             hip.expand_rows(dx0, gbuf["inv"], gbuf["dxg"], g.Beff, g.L, g.N, E)
             for s in g.mods:
-                b = self.mb[s.name]
-                pe = b["pe"]
-                T = s.Beff * s.n_tok  # noqa: N806
-                hip.embed_finish_bwd(gbuf["dxg"], b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"],
-                                     ps.g(pe.norm.weight), ps.g(pe.norm.bias), b["gn_sums"], s.Beff, s.D, s.L, E,
-                                     s.tok_off, g.L)
-                if not getattr(self, "_dw_conv_clear", False):   # (normally cleared by zero_grad's span launch)
-                    b["dw_conv"].zero_()
-                hip.gemm(hip.GEMM_TN, E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, b["dw_conv"], s.Kpad, AT)
-                hip.unpack_rows_add(b["dw_conv"], ps.g(pe.conv.weight), E, s.K, s.Kpad)
-                hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+                self.embed[s.name].backward(gbuf["dxg"], g.L, not self._dw_conv_clear)   # (normally cleared by zero_grad's span launch)
 
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":      # this segment's layers of every group encoder
@@ -1505,19 +1559,6 @@ class MAEEngine(EngineBase):
                 pixels[src] = torch.cat([pixels.pop(s.name) for s in parts], dim=2)
                 masks[src] = torch.cat([masks.pop(s.name) for s in parts], dim=2)
         return pixels, masks
-
-    def returned_batch(self, batch: dict) -> dict:
-        """The reference returns the (in place) resized / elevation-rescaled batch (mim.py:425-437, SURVEY Q13)."""
-        out = dict(batch)
-        sources = [parts[0] for parts in self.model.src_specs.values()]
-        out.update({s.src: self._staged[s.src] for s in sources})  # resized rasters (mim.py:427-432)
-        for s in sources:
-            if s.rescale_elev:
-                img = out[s.src]
-                res = torch.empty_like(img)
-                hip.rescale_elev(img, res, img.shape[0] * img.shape[1], s.C_src, s.S)
-                out[s.src] = res
-        return out
 
     def logged_sample(self, name_mod: str):
         """Sample ``[0, 0]`` of one modality for the image logs (``maestro/train/model.py:160-193`` keeps only that sample):

@@ -73,14 +73,8 @@ class SupervisedEngine(EngineBase):
         m, dev, E, B = self.model, self.device, self.E, self.B  # noqa: N806
         e = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
         z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
-        self.mb, self.gb, self.enc = {}, {}, {}
-        for name, s in self.mods.items():
-            T, BD = s.Beff * s.n_tok, s.Beff * s.D  # noqa: N806
-            pe = m.patch_embed[s.embed].patchify_bands[s.gi]
-            self.mb[name] = dict(cols=e(T, s.Kpad, dt=BF16), yconv=e(T, E), gn_partial=e(hip.groupnorm_partial_size(BD, s.L, E)),
-                                 gn_stats=e(BD, 2), gn_sums=e(BD, 2), pos_enc=m.pos_enc_rows[name].to(dev),
-                                 norm_bands=torch.tensor(s.norm_bands, dtype=I32, device=dev),
-                                 w_conv16=z(E, s.Kpad, dt=BF16), dw_conv=z(E, s.Kpad), dyc=e(T, E, dt=BF16), pe=pe)
+        self.gb, self.enc = {}, {}
+        self._alloc_embed()
         ws_rows = B * self.JL
         for g in self.groups:
             n_dates = sum(s.D for s in g.mods)
@@ -127,34 +121,18 @@ class SupervisedEngine(EngineBase):
         self.ln_ws = e(max(1, hip.layernorm_bwd_workspace(ws_rows, E)))
         self.scratch = e(ws_rows, E)      # LayerNorm-backward dx sink when the features are detached (probe)
 
-    def _pack_conv_weights(self) -> None:
-        for name, s in self.mods.items():
-            b = self.mb[name]
-            hip.pack_rows_bf16(b["pe"].conv.weight, b["w_conv16"], self.E, s.K, s.Kpad)
-
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, batch: dict) -> torch.Tensor:
         """Forward + ``loss_pred``; returns the loss as a 1-element device tensor (no host sync)."""
         if self.store.refresh_half():
             self._pack_conv_weights()
-        if self.instep_tune:           # first step: pick the GEMM tiles between the step's own kernels (engine.py:_instep_tune)
-            def one_pass():
-                self.forward(batch)
-                self.zero_grad()
-                self.backward()
-            self._instep_tune(one_pass)
-        if self.warm_passes > 0:       # start-up passes of the first step (engine.py: warm_passes)
-            def warm_pass():
-                self.forward(batch)
-                self.zero_grad()
-                self.backward()
-            self._warm_up(warm_pass)
+
+        def one_pass():
+            self.forward(batch)
+            self.zero_grad()
+            self.backward()
+        self._first_step_passes(one_pass)
         batch = dict(batch)
-        sources = [parts[0] for parts in self.model.src_specs.values()]      # one spec per batch entry (band-group 0)
-        for s in sources:
-            img = batch[s.src]
-            if img.dtype != F32 or not img.is_contiguous() or not img.is_cuda:
-                raise ValueError(f"batch[{s.src!r}] must be a contiguous float32 GPU tensor")
         for t, c in self.model.dataset.targets.items():
             y = batch[t]
             if not y.is_cuda or not y.is_contiguous():
@@ -163,47 +141,18 @@ class SupervisedEngine(EngineBase):
                 batch[t] = y.float()
             elif c.type_target != "multilabel_classif" and y.dtype.is_floating_point:
                 batch[t] = y.long()
-        batch = self._stable_inputs(batch)
-        for s in sources:
-            img = batch[s.src]
-            if tuple(img.shape[-2:]) != (s.S, s.S) or self.model.interpolate != "nearest":
-                mode = {"nearest": 0, "bilinear": 1, "bicubic": 2}.get(self.model.interpolate)
-                if mode is None:
-                    raise ValueError(f"Invalid interpolate mode {self.model.interpolate!r} (nearest, bilinear, bicubic)")
-                buf = self.mb[s.name].get("resized")
-                if buf is None:
-                    buf = self.mb[s.name]["resized"] = torch.empty(self.B, s.Dates, s.C_src, s.S, s.S, dtype=F32, device=self.device)
-                hip.resize(img, buf, self.B * s.Dates * s.C_src, img.shape[-2], img.shape[-1], s.S, s.S, mode)
-                batch[s.src] = buf
-        self._staged = batch
-        key = self._cur_key = tuple(batch[k].data_ptr() for k in sorted(batch) if isinstance(batch[k], torch.Tensor))
+        batch = self._stage_inputs(batch)
         with self._tuning_pass("forward"):
-            self._segment("sup_forward", key, lambda: self._forward_launches(batch))
+            self._segment("sup_forward", self._cur_key, lambda: self._forward_launches(batch))
         return self.loss_acc
 
     def _embed_encode(self, g, batch) -> None:
-        m, E, B = self.model, self.E, self.B  # noqa: N806
+        E, B = self.E, self.B  # noqa: N806
         gbuf, st = self.gb[g.name], self.enc[g.name]
         xg = st.x0.view(g.Beff, g.L, E)       # the embedding is written straight into the encoder's input (no masking)
         Lb = self.Lb[g.name]  # noqa: N806
         for s in g.mods:
-            b = self.mb[s.name]
-            BD = s.Beff * s.D  # noqa: N806
-            hip.patchify_bands(batch[s.src], b["cols"], None, BD, s.C_src, s.c0, s.C, s.S, s.P, s.Kpad, None, 0, False,
-                               s.rescale_elev)            # (band-group window of the raster; the whole raster when there is one)
-            if s.D != s.Dates:   # dates folded into the batch: one date row per sequence
-                hip.date_features(batch[f"{s.src}_dates"], batch["ref_date"], gbuf["dates"].view(B, s.Dates, 8), B, s.Dates,
-                                  s.Dates, 0, m.fac_date_enc)
-            else:
-                hip.date_features(batch[f"{s.src}_dates"], batch["ref_date"], gbuf["dates"], B, s.D, gbuf["n_dates"], s.date_off,
-                                  m.fac_date_enc)
-            pe = b["pe"]
-            T = s.Beff * s.n_tok  # noqa: N806
-            hip.gemm(hip.GEMM_NT, T, E, s.Kpad, b["cols"], s.Kpad, b["w_conv16"], s.Kpad, b["yconv"], E, hip.OUT_F32 | hip.BIAS,
-                     bias=pe.conv.bias)
-            hip.groupnorm_stats(b["yconv"], b["gn_partial"], b["gn_stats"], BD, s.L, E)
-            hip.embed_finish(b["yconv"], b["gn_stats"], pe.norm.weight, pe.norm.bias, b["pos_enc"], gbuf["dates"],
-                             gbuf["n_dates"], s.date_off, xg, s.Beff, s.D, s.L, E, s.tok_off, g.L)
+            self.embed[s.name].forward(batch, gbuf, xg, g.L)
         st.forward()
         nrm = st.t.norm
         dst = self.joint.x0 if self.joint is not None else self.xenc
@@ -394,17 +343,9 @@ class SupervisedEngine(EngineBase):
                 self._defer = False
         return self._defer
 
-    def _deferred_tables(self, part: str, stacks: list):
-        tabs = self.__dict__.setdefault("_wgrad_tables", {})
-        if part not in tabs:
-            tabs[part] = (hip.ColsumBatch([j for st in stacks for j in st.reduce_jobs()], self.device),
-                          hip.GroupedTN([p for st in stacks for p in st.wgrad_problems()], self.device))
-        return tabs[part]
-
     def _bwd_encoder(self, part: str = "all") -> None:
         """``part``: "all" (one segment), or "joint" followed by "groups" (two segments, see ``backward``)."""
         m, E, B, ps = self.model, self.E, self.B, self.store  # noqa: N806
-        AT = hip.OUT_F32 | hip.ATOMIC  # noqa: N806
         defer = self._wgrad_deferred()
         if part in ("all", "joint"):
             self._src = self.dxenc
@@ -417,8 +358,7 @@ class SupervisedEngine(EngineBase):
                 self._grads_ready(jn)
             if part == "joint":
                 if defer:
-                    for tab in self._deferred_tables("joint", [self.joint]):
-                        tab.launch()
+                    self._launch_wgrads([(self.joint, 0, self.joint.depth)])
                     self._grads_ready(m.encoder_inter)
                 return
         src = self._src
@@ -431,23 +371,14 @@ class SupervisedEngine(EngineBase):
                                   None, st.dxa, st.top16, ps.g(nrm.weight), ps.g(nrm.bias), st.top_bias_grad(), st.ln_ws, B, Lb, E)
                 dx0, _ = st.backward(st.dxa, defer=defer, ready=False)
                 dxg = dx0.view(g.Beff, g.L, E)
-                for s in g.mods:
-                    b = self.mb[s.name]
-                    pe = b["pe"]
-                    T = s.Beff * s.n_tok  # noqa: N806
-                    hip.embed_finish_bwd(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight),
-                                         ps.g(pe.norm.bias), b["gn_sums"], s.Beff, s.D, s.L, E, s.tok_off, g.L)
-                    b["dw_conv"].zero_()
-                    hip.gemm(hip.GEMM_TN, E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, b["dw_conv"], s.Kpad, AT)
-                    hip.unpack_rows_add(b["dw_conv"], ps.g(pe.conv.weight), E, s.K, s.Kpad)
-                    hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+                for s in g.mods:    # (this engine's zero_grad leaves the conv-gradient staging buffers alone: cleared here, every time)
+                    self.embed[s.name].backward(dxg, g.L, not self._dw_conv_clear)
             return run
 
         self._run_parallel([side(g) for g in self.groups])
         if defer:
             stacks = list(self.enc.values()) + ([self.joint] if (self.joint is not None and part == "all") else [])
-            for tab in self._deferred_tables(part, stacks):   # deferred LayerNorm / bias parameter gradients + weight gradients
-                tab.launch()
+            self._launch_wgrads([(st, 0, st.depth) for st in stacks])   # deferred LayerNorm / bias parameter + weight gradients
         for name in m.patch_embed:
             self._grads_ready(m.patch_embed[name])
         for name in m.encoder:
@@ -497,16 +428,3 @@ class SupervisedEngine(EngineBase):
         lg = lg if hb["PPCp"] == hb["PPC"] else lg[:, : hb["PPC"]].contiguous()
         hip.depatchify(lg, img, 1, hb["C"], S, hb["P"])
         return img[0].argmax(dim=0)
-
-    def returned_batch(self, batch: dict) -> dict:
-        """The reference returns the resized / elevation-rescaled batch (mim.py:425-437)."""
-        out = dict(batch)
-        sources = [parts[0] for parts in self.model.src_specs.values()]
-        out.update({s.src: self._staged[s.src] for s in sources})
-        for s in sources:
-            if s.rescale_elev:
-                img = out[s.src]
-                res = torch.empty_like(img)
-                hip.rescale_elev(img, res, img.shape[0] * img.shape[1], s.C_src, s.S)
-                out[s.src] = res
-        return out
