@@ -2,6 +2,7 @@
 // See include/maestro_hip.h for the reference lines each entry point replaces.  All HBM-bound: coalesced row reads,
 // LDS transposes where the output order differs from the input order, wavefront reductions for statistics.
 #include "common.hpp"
+#include "reduce_det.hpp"
 #include "../../include/maestro_hip.h"
 
 namespace {
@@ -266,7 +267,9 @@ constexpr int EB_ROWS = 8;
 // NV = ceil(E / 256) four-column chunks per lane (round 6): a lane owns the same columns in every row, so the dgamma / dbeta partial sums
 // of its EB_ROWS rows stay in registers and touch LDS once at the end (they used to be read-modify-written in LDS for every element:
 // two LDS round trips per element in a kernel that streams 8 bytes per element from HBM).  NV = 0: any E (the LDS form).
-template <int NV>
+// DET (deterministic mode, include/maestro_hip_det.h): no atomics -- the block writes its (S1, S2) to sums[bd, blockIdx.x, 2] and its
+// dgamma | dbeta row to dgamma[(bd * gridDim.x + blockIdx.x), 2 E] (dbeta unused); LDS then carries 8 more floats for the waves' sums.
+template <int NV, bool DET>
 __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __restrict__ dxg, const float* __restrict__ y,
                                                               const float* __restrict__ stats, const float* __restrict__ gamma,
                                                               float* __restrict__ sums, float* __restrict__ dgamma,
@@ -339,12 +342,32 @@ __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __res
         }
     }
     s1 = wave_sum(s1); s2 = wave_sum(s2);
+    if constexpr (DET) {
+        if (lane == 0) { red[8 * E + 2 * w] = s1; red[8 * E + 2 * w + 1] = s2; }
+    } else {
     if (lane == 0) { atomicAdd(sums + bd * 2, s1); atomicAdd(sums + bd * 2 + 1, s2); }
+    }
     __syncthreads();
     for (int c = threadIdx.x; c < 2 * E; c += 256) {
         const float t = red[c] + red[2 * E + c] + red[4 * E + c] + red[6 * E + c];
+        if constexpr (DET) {
+            dgamma[((size_t)bd * gridDim.x + blockIdx.x) * 2 * E + c] = t;
+        } else {
         if (c < E) atomicAdd(dgamma + c, t); else atomicAdd(dbeta + (c - E), t);
+        }
     }
+    if constexpr (DET) {
+        if (threadIdx.x < 2) {
+            const float* ws = red + 8 * E + threadIdx.x;
+            sums[((size_t)bd * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = ((ws[0] + ws[2]) + ws[4]) + ws[6];
+        }
+    }
+}
+
+// deterministic mode: sums[bd, k] = the ordered sum (reduce_det.hpp) of blk_sums[bd, 0 .. nblk, k]; one thread per output
+__global__ __launch_bounds__(64) void embed_bwd_sums_det_kernel(const float* __restrict__ blk_sums, float* __restrict__ sums, int nblk) {
+    if (threadIdx.x < 2)
+        sums[blockIdx.x * 2 + threadIdx.x] = 0.f + ordered_job_total(blk_sums + (size_t)blockIdx.x * nblk * 2 + threadIdx.x, nblk, 2);
 }
 
 __global__ __launch_bounds__(256) void zero_f32_kernel(float* __restrict__ p, int n) {
@@ -619,7 +642,7 @@ extern "C" int mh_embed_finish_bwd(const float* dxg, const float* y, const float
     {
         const dim3 grid(ceil_div(L, 4 * EB_ROWS), B * D), block(256);
         const size_t lds = (size_t)8 * E * sizeof(float);
-#define MH_EB_LAUNCH(NV) hipLaunchKernelGGL(embed_bwd_stats_kernel<NV>, grid, block, lds, s, dxg, y, stats, gamma, sums, dgamma, dbeta, B, D, L, E, tok_off, Lgroup)
+#define MH_EB_LAUNCH(NV) hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, false>), grid, block, lds, s, dxg, y, stats, gamma, sums, dgamma, dbeta, B, D, L, E, tok_off, Lgroup)
         switch ((E + 255) / 256) {
             case 1: MH_EB_LAUNCH(1); break;
             case 2: MH_EB_LAUNCH(2); break;
@@ -629,6 +652,36 @@ extern "C" int mh_embed_finish_bwd(const float* dxg, const float* y, const float
         }
 #undef MH_EB_LAUNCH
     }
+    hipLaunchKernelGGL(embed_bwd_apply_kernel, dim3(ceil_div((long)B * D * L, 4)), dim3(256), 0, s, dxg, y, stats, gamma, sums,
+                       (bf16_t*)dyc, B, D, L, E, tok_off, Lgroup);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_embed_bwd_partial_rows(int BD, int L) { return BD > 0 && L > 0 ? BD * ceil_div(L, 4 * EB_ROWS) : 0; }
+
+extern "C" int mh_embed_finish_bwd_det(const float* dxg, const float* y, const float* stats, const float* gamma, void* dyc,
+                                       float* param_partial, float* blk_sums, float* sums, int B, int D, int L, int E, int tok_off,
+                                       int Lgroup, void* stream) {
+    MH_CHECK_ARG(dxg && y && stats && gamma && dyc && param_partial && blk_sums && sums, "mh_embed_finish_bwd_det: null pointer");
+    MH_CHECK_ARG(B > 0 && D > 0 && L > 0 && E > 0 && E % 4 == 0 && tok_off >= 0 && tok_off + D * L <= Lgroup,
+                 "mh_embed_finish_bwd_det: bad sizes B=%d D=%d L=%d E=%d tok_off=%d Lgroup=%d", B, D, L, E, tok_off, Lgroup);
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = ceil_div(L, 4 * EB_ROWS);
+    {
+        const dim3 grid(nblk, B * D), block(256);
+        const size_t lds = (size_t)(8 * E + 8) * sizeof(float);
+#define MH_EB_LAUNCH(NV) hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, true>), grid, block, lds, s, dxg, y, stats, gamma, blk_sums, param_partial, (float*)nullptr, B, D, L, E, tok_off, Lgroup)
+        switch ((E + 255) / 256) {
+            case 1: MH_EB_LAUNCH(1); break;
+            case 2: MH_EB_LAUNCH(2); break;
+            case 3: MH_EB_LAUNCH(3); break;
+            case 4: MH_EB_LAUNCH(4); break;
+            default: MH_EB_LAUNCH(0); break;
+        }
+#undef MH_EB_LAUNCH
+    }
+    hipLaunchKernelGGL(embed_bwd_sums_det_kernel, dim3(B * D), dim3(64), 0, s, blk_sums, sums, nblk);
     hipLaunchKernelGGL(embed_bwd_apply_kernel, dim3(ceil_div((long)B * D * L, 4)), dim3(256), 0, s, dxg, y, stats, gamma, sums,
                        (bf16_t*)dyc, B, D, L, E, tok_off, Lgroup);
     MH_LAUNCH_CHECK();

@@ -1,5 +1,6 @@
 // Masked reconstruction loss at patch layout + its gradient, bias-gradient column sums, casts, fused AdamW.
 #include "gemm_common.hpp"
+#include "../../include/maestro_hip_det.h"
 
 namespace {
 
@@ -8,6 +9,9 @@ namespace {
 // coef * de/drec for masked tokens, 0 elsewhere, with coef = weight / (n_masked_tokens * PPC).
 // One WAVE per token (4 tokens per block), 16-byte accesses; the block reduces its partial loss through LDS and issues one
 // atomic (32768 -> 8192 atomics for the aerial modality; blocks whose 4 tokens are all visible issue none).
+// DET (deterministic mode, include/maestro_hip_det.h): the same arithmetic, but the block's partial loss goes to acc[blockIdx.x]
+// with a plain store instead of being added to the loss word.
+template <bool DET>
 __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restrict__ rec, const float* __restrict__ target,
                                                           const uint8_t* __restrict__ mask_group, const int* __restrict__ n_masked,
                                                           float weight, float* __restrict__ acc, bf16_t* __restrict__ drec,
@@ -60,10 +64,14 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
     __syncthreads();
     if (threadIdx.x == 0) {
         const float t = (red[0] + red[1]) + (red[2] + red[3]);
+        if constexpr (DET) {     // zero is written too: every slot of the partial row is owned by one block
+            acc[blockIdx.x] = (blockIdx.x == 0 && *n_masked == 0) ? __builtin_nanf("") : t * coef;
+        } else {
         if (t != 0.f) atomicAdd(acc, t * coef);  // coef = weight / n_elems -> acc accumulates the weighted loss
         // a modality without a single masked token in the batch: the reference takes the mean of an empty selection
         // (maestro/train/model.py:241-243) -> NaN loss, zero gradient for this modality; reproduced, not guarded
         if (blockIdx.x == 0 && *n_masked == 0) atomicAdd(acc, __builtin_nanf(""));
+        }
     }
 }
 
@@ -71,6 +79,8 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
 // launch is bound by two things that pull in opposite directions -- memory-level parallelism (wants many resident waves) and the
 // same-address atomics of the final add (M / rows_per_block per column: wants few, fat blocks) -- so a block is 16 waves on up to
 // 1024 rows: 32768 x 768 bf16 31.7 -> see scripts/bench_small_reductions.py.
+// DET (include/maestro_hip_det.h): row block blockIdx.y stores its sums to out[blockIdx.y, :] instead of adding them to out[:].
+template <bool DET>
 __global__ __launch_bounds__(1024) void colsum_kernel(const void* __restrict__ x, int is_f32, float* __restrict__ out, int M,
                                                       int N, int ld, int rows_per_block) {
     __shared__ f32x4 red[16][64];
@@ -99,8 +109,12 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const void* __restrict__ x
     if (w == 0 && c < N) {
         f32x4 t = red[0][lane];
         for (int i = 1; i < nw; ++i) t += red[i][lane];
+        if constexpr (DET) {
+            *reinterpret_cast<f32x4*>(out + (size_t)blockIdx.y * N + c) = t;
+        } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) atomicAdd(out + c + e, t[e]);
+        }
     }
 }
 
@@ -263,7 +277,7 @@ extern "C" int mh_masked_loss(const float* rec, const float* target, const uint8
     MH_CHECK_ARG(rec && target && mask_group && n_masked && acc, "mh_masked_loss: null pointer");
     MH_CHECK_ARG((p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss: bad arguments");
     const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL(masked_loss_kernel, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target, mask_group, n_masked,
+    hipLaunchKernelGGL(masked_loss_kernel<false>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target, mask_group, n_masked,
                        weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, 1, 0, 1, 0, rpw);
     MH_LAUNCH_CHECK();
     return 0;
@@ -277,8 +291,50 @@ extern "C" int mh_masked_loss_bands(const float* rec, const float* target, const
     MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "mh_masked_loss_bands: band window [%d, %d) of %d",
                  tgt_c0, tgt_c0 + n_g, tgt_C);
     const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL(masked_loss_kernel, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target, mask_group, n_elems,
+    hipLaunchKernelGGL(masked_loss_kernel<false>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target, mask_group, n_elems,
                        weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_masked_loss_partial_size(int B, int Lm) {
+    const long rows = (long)B * Lm;
+    return rows > 0 ? ceil_div(rows, 4 * loss_rows_per_wave(rows)) : 0;
+}
+
+extern "C" int mh_masked_loss_det(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked,
+                                  float weight, float* loss_partial, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC,
+                                  int p, void* stream) {
+    MH_CHECK_ARG(rec && target && mask_group && n_masked && loss_partial, "mh_masked_loss_det: null pointer");
+    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss_det: bad arguments");
+    const int rpw = loss_rows_per_wave((long)B * Lm);
+    hipLaunchKernelGGL(masked_loss_kernel<true>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target,
+                       mask_group, n_masked, weight, loss_partial, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, 1, 0, 1, 0, rpw);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_masked_loss_bands_det(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems,
+                                        float weight, float* loss_partial, void* drec, int B, int Lm, int Lgroup, int tok_off,
+                                        int PPC, int p, int tgt_C, int tgt_c0, int n_g, void* stream) {
+    MH_CHECK_ARG(rec && target && mask_group && n_elems && loss_partial, "mh_masked_loss_bands_det: null pointer");
+    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss_bands_det: bad arguments");
+    MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "mh_masked_loss_bands_det: band window [%d, %d) of %d",
+                 tgt_c0, tgt_c0 + n_g, tgt_C);
+    const int rpw = loss_rows_per_wave((long)B * Lm);
+    hipLaunchKernelGGL(masked_loss_kernel<true>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target,
+                       mask_group, n_elems, weight, loss_partial, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_colsum_partial_rows(int M) { return M > 0 ? ceil_div(M, MH_COLSUM_PARTIAL_ROWS) : 0; }
+
+extern "C" int mh_colsum_partial(const void* x, int x_is_f32, float* partial, int M, int N, int ld, void* stream) {
+    MH_CHECK_ARG(x && partial && ((uintptr_t)partial % 16) == 0, "mh_colsum_partial: null pointer / partial not 16-byte aligned");
+    MH_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0 && N <= ld, "mh_colsum_partial: bad sizes M=%d N=%d ld=%d", M, N, ld);
+    hipLaunchKernelGGL(colsum_kernel<true>, dim3(ceil_div(N, 256), ceil_div(M, MH_COLSUM_PARTIAL_ROWS)), dim3(1024), 0,
+                       (hipStream_t)stream, x, x_is_f32, partial, M, N, ld, MH_COLSUM_PARTIAL_ROWS);
     MH_LAUNCH_CHECK();
     return 0;
 }
@@ -289,7 +345,7 @@ extern "C" int mh_colsum(const void* x, int x_is_f32, float* out, int M, int N, 
     const int col_blocks = ceil_div(N, 256);
     int rows_per_block = 1024;
     while (rows_per_block > 128 && (long)col_blocks * ceil_div(M, rows_per_block) < 128) rows_per_block >>= 1;
-    hipLaunchKernelGGL(colsum_kernel, dim3(col_blocks, ceil_div(M, rows_per_block)), dim3(1024), 0, (hipStream_t)stream, x,
+    hipLaunchKernelGGL(colsum_kernel<false>, dim3(col_blocks, ceil_div(M, rows_per_block)), dim3(1024), 0, (hipStream_t)stream, x,
                        x_is_f32, out, M, N, ld, rows_per_block);
     MH_LAUNCH_CHECK();
     return 0;

@@ -135,6 +135,8 @@ __global__ __launch_bounds__(256) void unmask_kernel(const float* __restrict__ y
 // Round 3: 1024 threads and 512 rows per block instead of 256 / 128 -- the launch was bound by its memory-level parallelism (two
 // row lanes x four loads per block) and by B*L/128 same-address atomics per column (36 MB in 46 us = 0.8 TB/s at 32768 x 512).
 constexpr int UM_ROWS = 512, UM_NT = 1024;
+// DET (include/maestro_hip_det.h): the block's sums go to row blockIdx.x of dmask_token [blocks, Dd] with plain stores.
+template <bool DET>
 __global__ __launch_bounds__(UM_NT) void unmask_bwd_token_kernel(const float* __restrict__ dxdec, const uint8_t* __restrict__ mask,
                                                                  const int* __restrict__ tok_slot, float* __restrict__ dmask_token,
                                                                  int B, int L, int Dd, int slot, int t_lo, int t_hi, int slot_stride) {
@@ -178,8 +180,12 @@ __global__ __launch_bounds__(UM_NT) void unmask_bwd_token_kernel(const float* __
     __syncthreads();
     if (sub == 0) {
         for (int s = 1; s < lanes; ++s) acc += *reinterpret_cast<const f32x4*>(red + 4 * (s * cols + col));
+        if constexpr (DET) {
+            *reinterpret_cast<f32x4*>(dmask_token + (size_t)blockIdx.x * Dd + 4 * col) = acc;
+        } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) if (acc[e] != 0.f) atomicAdd(dmask_token + 4 * col + e, acc[e]);
+        }
     }
 }
 
@@ -262,7 +268,7 @@ extern "C" int mh_unmask_token_grad(const float* dxdec, const uint8_t* mask, con
                                     int L, int Dd, int slot, int t_lo, int t_hi, void* stream) {
     MH_CHECK_ARG(dxdec && mask && tok_slot && dmask_token && Dd % 4 == 0 && Dd <= 1024, "mh_unmask_token_grad: bad arguments");
     MH_CHECK_ARG(0 <= t_lo && t_lo < t_hi && t_hi <= L, "mh_unmask_token_grad: bad token range");
-    hipLaunchKernelGGL(unmask_bwd_token_kernel, dim3(ceil_div((long)B * (t_hi - t_lo), UM_ROWS)), dim3(UM_NT), 0,
+    hipLaunchKernelGGL(unmask_bwd_token_kernel<false>, dim3(ceil_div((long)B * (t_hi - t_lo), UM_ROWS)), dim3(UM_NT), 0,
                        (hipStream_t)stream, dxdec, mask, tok_slot, dmask_token, B, L, Dd, slot, t_lo, t_hi, 0);
     MH_LAUNCH_CHECK();
     return 0;
@@ -272,8 +278,31 @@ extern "C" int mh_unmask_token_grad_per_sample(const float* dxdec, const uint8_t
                                                int B, int L, int Dd, int slot, void* stream) {
     MH_CHECK_ARG(dxdec && mask && tok_slot_bl && dmask_token && Dd % 4 == 0 && Dd <= 1024 && B > 0 && L > 0,
                  "mh_unmask_token_grad_per_sample: bad arguments");
-    hipLaunchKernelGGL(unmask_bwd_token_kernel, dim3(ceil_div((long)B * L, UM_ROWS)), dim3(UM_NT), 0, (hipStream_t)stream, dxdec, mask,
+    hipLaunchKernelGGL(unmask_bwd_token_kernel<false>, dim3(ceil_div((long)B * L, UM_ROWS)), dim3(UM_NT), 0, (hipStream_t)stream, dxdec, mask,
                        tok_slot_bl, dmask_token, B, L, Dd, slot, 0, L, L);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_unmask_token_grad_partial_rows(long n_rows) { return n_rows > 0 ? ceil_div(n_rows, UM_ROWS) : 0; }
+
+extern "C" int mh_unmask_token_grad_det(const float* dxdec, const uint8_t* mask, const int* tok_slot, float* partial, int B, int L,
+                                        int Dd, int slot, int t_lo, int t_hi, void* stream) {
+    MH_CHECK_ARG(dxdec && mask && tok_slot && partial && ((uintptr_t)partial % 16) == 0 && B > 0 && Dd > 0 && Dd % 4 == 0 && Dd <= 1024,
+                 "mh_unmask_token_grad_det: bad arguments");
+    MH_CHECK_ARG(0 <= t_lo && t_lo < t_hi && t_hi <= L, "mh_unmask_token_grad_det: bad token range");
+    hipLaunchKernelGGL(unmask_bwd_token_kernel<true>, dim3(ceil_div((long)B * (t_hi - t_lo), UM_ROWS)), dim3(UM_NT), 0,
+                       (hipStream_t)stream, dxdec, mask, tok_slot, partial, B, L, Dd, slot, t_lo, t_hi, 0);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_unmask_token_grad_per_sample_det(const float* dxdec, const uint8_t* mask, const int* tok_slot_bl, float* partial,
+                                                   int B, int L, int Dd, int slot, void* stream) {
+    MH_CHECK_ARG(dxdec && mask && tok_slot_bl && partial && ((uintptr_t)partial % 16) == 0 && Dd > 0 && Dd % 4 == 0 && Dd <= 1024 &&
+                 B > 0 && L > 0, "mh_unmask_token_grad_per_sample_det: bad arguments");
+    hipLaunchKernelGGL(unmask_bwd_token_kernel<true>, dim3(ceil_div((long)B * L, UM_ROWS)), dim3(UM_NT), 0, (hipStream_t)stream, dxdec,
+                       mask, tok_slot_bl, partial, B, L, Dd, slot, 0, L, L);
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -463,6 +463,8 @@ class PatchEmbedEnd:
         atomics accumulate into it) was not cleared since the last backward."""
         eng, s, b = self.eng, self.s, self.buf
         ps, E, pe, T = eng.store, eng.E, b["pe"], s.Beff * s.n_tok  # noqa: N806
+        if getattr(eng, "deterministic", False):
+            return self._backward_det(dxg, Lgroup)
         hip.embed_finish_bwd(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight), ps.g(pe.norm.bias),
                              b["gn_sums"], s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
         if clear_dw:
@@ -470,6 +472,26 @@ class PatchEmbedEnd:
         hip.gemm(hip.GEMM_TN, E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, b["dw_conv"], s.Kpad, hip.OUT_F32 | hip.ATOMIC)
         hip.unpack_rows_add(b["dw_conv"], ps.g(pe.conv.weight), E, s.K, s.Kpad)
         hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+
+    def _backward_det(self, dxg: torch.Tensor, Lgroup: int) -> None:  # noqa: N803
+        """Deterministic mode: every reduction leaves partial rows in buffers private to this end; the engine's ordered reduce
+        finishes them (the conv gradient through ``dw_conv``: see ``MAEEngine._det_finish_backward``)."""
+        eng, s, b = self.eng, self.s, self.buf
+        ps, E, pe, T = eng.store, eng.E, b["pe"], s.Beff * s.n_tok  # noqa: N806
+
+        def make():
+            e = lambda *sh: torch.empty(*sh, dtype=F32, device=eng.device)  # noqa: E731
+            rows, S, cr = hip.embed_bwd_partial_rows(s.Beff * s.D, s.L), hip.det_slices(T), hip.colsum_partial_rows(T)  # noqa: N806
+            w = dict(gn=e(rows, 2 * E), blk=e(rows, 2), slabs=e(S, E, s.Kpad), cs=e(cr, E))
+            flat = w["gn"].view(-1)
+            return w, [(flat, ps.g(pe.norm.weight), rows, E, 2 * E), (flat[E:], ps.g(pe.norm.bias), rows, E, 2 * E),
+                       (w["slabs"].view(-1), b["dw_conv"].view(-1), S, E * s.Kpad, E * s.Kpad),
+                       (w["cs"].view(-1), ps.g(pe.conv.bias), cr, E, E)]
+        w = eng._det_site("bwd", ("embed", s.name), make)
+        hip.embed_finish_bwd_det(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], w["gn"], w["blk"], b["gn_sums"], s.Beff,
+                                 s.D, s.L, E, s.tok_off, Lgroup)
+        hip.gemm_tn_slabs(E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, w["slabs"])
+        hip.colsum_partial(b["dyc"], w["cs"], T, E, E)
 
 
 # hipGraphs of engines that have been garbage-collected, kept alive until the next SAFE point.  An engine is a reference cycle, so
@@ -480,6 +502,13 @@ class PatchEmbedEnd:
 # collector off, and gone with the graphs never destroyed).  So a dying engine only hands its graphs to this list; they are
 # destroyed by ``drain_retired_graphs`` after a device synchronisation, when the next engine is built (or on request).
 _RETIRED_GRAPHS: list = []
+
+
+def resolve_deterministic(flag: bool | None = None) -> bool:
+    """The ``deterministic`` switch of the public surface: an explicit bool wins; None reads ``MAESTRO_DETERMINISTIC`` ("1" = on)."""
+    if flag is None:
+        return os.environ.get("MAESTRO_DETERMINISTIC", "0") == "1"
+    return bool(flag)
 
 
 def training_warm_passes() -> int:
@@ -824,9 +853,18 @@ class EngineBase:
 # ======================================================================================= the engine
 class MAEEngine(EngineBase):
     def __init__(self, model, batch_size: int, device, loss: str = "l2_norm", dtype: str = "bf16",
-                 fp8_scaling: str | None = None) -> None:
+                 fp8_scaling: str | None = None, deterministic: bool = False) -> None:
         """``fp8_scaling`` (dtype "fp8" only): "tensor" (per-tensor delayed scaling) or "mx" (OCP MX block scales); None reads
-        ``MAESTRO_FP8_SCALING`` (default "tensor").  A numeric-format choice like ``dtype`` (maestro_amd/fp8.py)."""
+        ``MAESTRO_FP8_SCALING`` (default "tensor").  A numeric-format choice like ``dtype`` (maestro_amd/fp8.py).
+
+        ``deterministic``: the same weights, inputs and mask draws give the same bits on every run (loss, every gradient,
+        hence the parameters after AdamW) -- eager launches, capture runs and graph replays, one stream or several.  No
+        floating-point atomics: every reduction of the step leaves partial rows in private buffers and one ordered reduce per
+        phase (``hip.OrderedReduce``) finishes them in a fixed order; kernels and tiles are chosen from shapes alone
+        ("Deterministic mode").  Not with dtype "fp8", an overlapped optimizer or a gradient hook."""
+        self.deterministic = bool(deterministic)
+        if self.deterministic and dtype == "fp8":
+            raise ValueError("deterministic=True is not available with dtype='fp8' (the amax / scale bookkeeping is not covered)")
         if loss not in ("l1", "l2", "l1_norm", "l2_norm"):
             raise ValueError(f"Invalid loss {loss}.")
         if dtype not in ("bf16", "fp8"):
@@ -854,6 +892,9 @@ class MAEEngine(EngineBase):
         if self.wgrad_mode not in ("auto", "fused", "deferred"):
             raise ValueError(f"MAESTRO_WGRAD={self.wgrad_mode!r}: expected auto, fused or deferred")
         self._wgrad_plans, self._zero_lists = {}, {}
+        # deterministic mode: per phase ("fwd", "bwd") the former atomic sites in the order of their first launch -- key ->
+        # (private buffers, ordered-reduce jobs) -- and the tables built from them (see _det_site)
+        self._det_sites, self._det_tables = {"fwd": {}, "bwd": {}}, {}
         self._h2d_done = [None] * RING   # per ring slot: event after the mask uploads that last used it
         self._opt = None                 # overlapped optimizer (attach_optimizer)
         self.host_wait_s = 0.0           # time the host spent blocked on that ring (diagnostic: not issue work)
@@ -893,6 +934,105 @@ class MAEEngine(EngineBase):
             self.fp8.finalize()
         self.store.refresh_half(force=True)
         self._pack_conv_weights()
+
+    # ------------------------------------------------------------------------------------------ deterministic mode
+    @property
+    def grad_hook(self):
+        return self._grad_hook
+
+    @grad_hook.setter
+    def grad_hook(self, fn) -> None:
+        if fn is not None and getattr(self, "deterministic", False):
+            raise ValueError("deterministic=True excludes a gradient hook / exchange: the order of the cross-rank sum is the "
+                             "collective library's, and the ready spans would have to move behind the ordered reduce")
+        self._grad_hook = fn
+
+    def _det_site(self, phase: str, key, make, variant=None):
+        """Private buffers of one former atomic site: ``make() -> (buffers, jobs)`` runs on the site's first launch (always an
+        eager run: segments are captured on their second run) and registers its ordered-reduce jobs ``(src, dst, rows, cols,
+        ld)``.  Sites are listed in the order of their first launch -- the order of the Python launch code: group, then modality
+        -- which is the order of their totals inside a chain.  A buffer is written by one site only, once per step.
+        ``variant``: a site whose launch form changed (``tie_order``) is rebuilt IN PLACE -- same key, same position -- so the
+        buffer of the form that no longer runs leaves the table instead of being summed into the gradient."""
+        site = self._det_sites[phase].get(key)
+        if site is None or site[2] != variant:
+            if torch.cuda.is_current_stream_capturing():
+                raise hip.HipExtensionError(f"deterministic mode: site {key} first launched inside a hipGraph capture")
+            site = self._det_sites[phase][key] = (*make(), variant)
+            self._det_tables.pop(phase, None)       # (a table built earlier does not list this site)
+        return site[0]
+
+    def _det_reduce(self, phase: str, extra_jobs=()) -> None:
+        """One ordered-reduce launch for every site of ``phase`` (+ ``extra_jobs``, listed after them)."""
+        table = self._det_tables.get(phase)
+        if table is None:
+            jobs = [j for _, site_jobs, _ in self._det_sites[phase].values() for j in site_jobs] + list(extra_jobs)
+            table = self._det_tables[phase] = hip.OrderedReduce(jobs, self.device)
+        table.launch()
+
+    def _det_layernorm_bwd(self, key, dy, dy_L, dy_off, x, x_L, x_off, norm, mean, rstd, dx, dx16, bias_grad, B, n, dim) -> None:  # noqa: N803
+        """A final-LayerNorm backward outside the stacks: partial rows (dgamma | dbeta | colsum dx) into the site's own workspace."""
+        def make():
+            size = hip.layernorm_bwd_workspace(B * n, dim)
+            ws, rows, g = torch.empty(size, dtype=F32, device=self.device), size // (3 * dim), self.store.g
+            jobs = [(ws, g(norm.weight), rows, dim, 3 * dim), (ws[dim:], g(norm.bias), rows, dim, 3 * dim)]
+            if bias_grad is not None:
+                jobs.append((ws[2 * dim:], bias_grad, rows, dim, 3 * dim))
+            return ws, jobs
+        ws = self._det_site("bwd", key, make)
+        hip.layernorm_bwd_partial(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, ws, B, n, dim)
+
+    def _det_linear_grads(self, key, dy16, x16, M, N, K, weight_grad, bias_grad) -> None:  # noqa: N803
+        """Weight and bias gradient of a Linear outside the stacks (dW[M, N] = dy[K, M]^T x[K, N], db = colsum dy): K-slices into
+        private slabs and per-row-block column sums, both finished by the ordered reduce."""
+        def make():
+            e = lambda *sh: torch.empty(*sh, dtype=F32, device=self.device)  # noqa: E731
+            S, cr = hip.det_slices(K), hip.colsum_partial_rows(K)  # noqa: N806
+            w = dict(slabs=e(S, M, N), cs=e(cr, M))
+            return w, [(w["slabs"].view(-1), weight_grad.view(-1), S, M * N, M * N), (w["cs"].view(-1), bias_grad, cr, M, M)]
+        w = self._det_site("bwd", key, make)
+        hip.gemm_tn_slabs(M, N, K, dy16, M, x16, N, w["slabs"])
+        hip.colsum_partial(dy16, w["cs"], K, M, M)
+
+    def _det_finish_backward(self) -> None:
+        """End of the backward, on the main stream after the group streams have joined: the deferred weight gradients of every
+        stack (plain stores; a weight written by several stacks -- a holder shared by groups -- gets one slab per writer), then
+        ONE ordered reduce over every partial buffer of the backward, then the patch-embed conv gradients from their padded
+        staging buffers (one add per element and launch, launches in modality order on this stream)."""
+        wg = self._det_tables.get("wgrad")
+        if wg is None:
+            probs = [p for st in self._all_stacks() for p in st.wgrad_problems()]
+            n_writers: dict = {}                 # weight-gradient slot -> number of problems that write it
+            for p in probs:
+                n_writers[p[2].data_ptr()] = n_writers.get(p[2].data_ptr(), 0) + 1
+            slabs_of, seen, slab_jobs, out = {}, {}, [], []
+            for p in probs:
+                dst = p[2]
+                n = n_writers[dst.data_ptr()]
+                if n > 1:       # one slab per writer, in the order of the problems (= group order)
+                    if dst.data_ptr() not in slabs_of:
+                        slabs = slabs_of[dst.data_ptr()] = torch.empty(n, dst.numel(), dtype=F32, device=self.device)
+                        slab_jobs.append((slabs.view(-1), dst.view(-1), n, dst.numel(), dst.numel()))
+                    i = seen[dst.data_ptr()] = seen.get(dst.data_ptr(), -1) + 1
+                    p = p[:2] + (slabs_of[dst.data_ptr()][i].view(dst.shape),) + p[3:]
+                out.append(p)
+            grouped, single = [], []
+            for i, p in enumerate(out):
+                try:
+                    hip.GroupedTN.check(i, p)
+                    grouped.append(p)
+                except hip.HipExtensionError:
+                    single.append(p)        # not eligible for the grouped kernel: a plain-store TN GEMM of its own
+            stack_jobs = [j for st in self._all_stacks() for j in st.reduce_jobs()]
+            wg = self._det_tables["wgrad"] = (hip.GroupedTN(grouped, self.device) if grouped else None, single, stack_jobs + slab_jobs)
+        if wg[0] is not None:
+            wg[0].launch()
+        for (A, B, C, M, N, K, lda, ldb, ldc) in wg[1]:  # noqa: N806
+            hip.gemm(hip.GEMM_TN, M, N, K, A, lda, B, ldb, C, ldc, hip.OUT_F32)
+        self._det_reduce("bwd", wg[2])
+        for end in self.embed.values():
+            b, s = end.buf, end.s
+            hip.unpack_rows_add(b["dw_conv"], self.store.g(b["pe"].conv.weight), self.E, s.K, s.Kpad)
 
     # ------------------------------------------------------------------------------------------ allocation
     def _alloc(self) -> None:
@@ -1032,6 +1172,13 @@ class MAEEngine(EngineBase):
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, batch: dict, noise: dict | None = None, struct: dict | None = None) -> torch.Tensor:
         """Runs the forward pass + loss; returns the loss as a 1-element device tensor (no host sync)."""
+        if self.deterministic:
+            self.tune_gemm = self.instep_tune = False     # no choice of kernel may depend on a measured time
+            with hip.shape_only_tiles():
+                return self._forward(batch, noise, struct)
+        return self._forward(batch, noise, struct)
+
+    def _forward(self, batch: dict, noise: dict | None, struct: dict | None) -> torch.Tensor:
         if self.store.refresh_half():     # parameters were changed behind the engine's back (torch optimizer, state-dict load)
             if self.fp8 is not None:
                 self.fp8._w_ready = False  # ... possibly wholesale: rebuild the e4m3 scales from scratch
@@ -1091,6 +1238,11 @@ class MAEEngine(EngineBase):
 
     # ------------------------------------------------------------------------------------------ overlapped optimizer
     def attach_optimizer(self, opt) -> None:
+        if self.deterministic:
+            raise ValueError("deterministic=True excludes overlap_optimizer (the update inside the next forward is not covered)")
+        self._attach_optimizer(opt)
+
+    def _attach_optimizer(self, opt) -> None:
         """Run ``opt``'s AdamW update of step t INSIDE the forward of step t+1 (``defer_step`` queues it): the update is
         HBM-bound, the forward MFMA-bound, so on a side stream it hides under the GEMMs.  The flat buffer is cut into
         stages in the order the forward needs the parameters (patch embed, encoder layer 0 of every group, layer 1, ...,
@@ -1257,7 +1409,18 @@ class MAEEngine(EngineBase):
                     hip.count_masked(gbuf["mask"], g.Beff, g.L, s.tok_off, s.tok_off + s.n_tok, b["cnt"])
             for s in g.mods:    # (several band-groups: counted by count_band_group_elems, before any decoder side starts)
                 b = self.mb[s.name]
-                if s.G == 1:
+                if self.deterministic:
+                    def make(s=s):
+                        part = torch.empty(hip.masked_loss_partial_size(s.Beff, s.n_tok), dtype=F32, device=self.device)
+                        return part, [(part, self.loss_acc, part.numel(), 1, 1)]
+                    part = self._det_site("fwd", ("loss", s.name), make)
+                    if s.G == 1:
+                        hip.masked_loss_det(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], part,
+                                            b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
+                    else:
+                        hip.masked_loss_bands_det(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], part,
+                                                  b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss, s.C_src, s.c0, s.C)
+                elif s.G == 1:
                     hip.masked_loss(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
                                     b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
                 else:
@@ -1277,6 +1440,8 @@ class MAEEngine(EngineBase):
                     hip.count_masked_elems(self.gb[g.name]["mask"], g.Beff, g.L, s.tok_off, s.tok_off + s.n_tok,
                                            self.mb[s.name]["cnt"], s.K, s.gi > 0)
         self._run_parallel([tail(g) for g in self.groups])
+        if self.deterministic:       # the loss word: one ordered chain over the modalities' partial losses (group, then modality order)
+            self._det_reduce("fwd")
         if self._opt is not None and self._opt_events:
             torch.cuda.current_stream().wait_stream(self._opt_stream)   # join (a capture must end with every fork joined)
         if self.fp8 is not None:
@@ -1332,6 +1497,8 @@ class MAEEngine(EngineBase):
         because every weight gradient then completes last) | "enc" (data parallel: one grouped launch at the end of EVERY
         backward segment -- decoder side, joint encoder, each encoder chunk -- so that finished slices are handed to the
         all-reduce as early as with in-line weight gradients)."""
+        if self.deterministic:       # whatever wgrad_mode says: always deferred, one plain-store launch at the end of the backward
+            return "all"
         if self.wgrad_mode == "fused":
             return "fused"
         hooked = self.grad_hook is not None
@@ -1406,6 +1573,12 @@ class MAEEngine(EngineBase):
         """
         if grad_scale != 1.0:
             raise NotImplementedError("loss scaling is not needed for bf16 (SURVEY §8(f) AMP row)")
+        if self.deterministic:
+            with hip.shape_only_tiles():
+                return self._backward()
+        return self._backward()
+
+    def _backward(self) -> None:
         key = getattr(self, "_cur_key", None)
         plan = self._plan = self._wgrad_plan()
         sfx = f":{plan}:{'h' if self.grad_hook is not None else 'n'}"   # graphs are specific to the launch plan
@@ -1446,6 +1619,12 @@ class MAEEngine(EngineBase):
                     conv = m.embed_to_rec[s.embed].pixelify_bands[s.gi].conv
                     w16 = ps.h(conv.weight).view(s.K, Dd)
                     hip.gemm(hip.GEMM_NN, T, Dd, s.K, b["drec"], s.K, w16, Dd, b["dh"], Dd)
+                    if self.deterministic:
+                        self._det_linear_grads(("rec", s.name), b["drec"], b["hdec"], s.K, Dd, T, ps.g(conv.weight), ps.g(conv.bias))
+                        self._det_layernorm_bwd(("ln_dec", s.name), b["dh"], s.n_tok, 0, st.x_last, g.L, s.tok_off, nrm, b["mean_f"],
+                                                b["rstd_f"], dx, dx16, st.top_bias_grad(), s.Beff, s.n_tok, Dd)
+                        self._grads_ready(m.embed_to_rec[s.embed])
+                        continue
                     hip.gemm(hip.GEMM_TN, s.K, Dd, T, b["drec"], s.K, b["hdec"], Dd, ps.g(conv.weight).view(s.K, Dd), Dd, AT)
                     hip.colsum(b["drec"], ps.g(conv.bias), T, s.K, s.K)
                     hip.layernorm_bwd(b["dh"], s.n_tok, 0, st.x_last, g.L, s.tok_off, nrm.weight, b["mean_f"], b["rstd_f"],
@@ -1461,7 +1640,21 @@ class MAEEngine(EngineBase):
             # unmask backward: visible rows -> enc_to_dec output grad; masked rows -> mask-token grads
             hip.gather_rows(dx0, gbuf["vis"], gbuf["dy_e2d"], g.Beff, g.L, g.N, Dd, g.N, 0)
             for s in g.mods:
-                if self.tie_order == "torch":
+                if self.deterministic:
+                    per_sample = self.tie_order == "torch"
+                    n_rows = g.Beff * (g.L if per_sample else s.n_tok)
+
+                    def make(s=s, n_rows=n_rows):
+                        rows = hip.unmask_token_grad_partial_rows(n_rows)
+                        part = torch.empty(rows, Dd, dtype=F32, device=self.device)
+                        return part, [(part.view(-1), ps.g(m.mask_token[s.src]).view(s.G, Dd)[s.gi], rows, Dd, Dd)]
+                    part = self._det_site("bwd", ("tok", s.name), make, variant=per_sample)
+                    if per_sample:
+                        hip.unmask_token_grad_per_sample_det(dx0, gbuf["mask"], gbuf["tok_slot_ps"], part, g.Beff, g.L, Dd, s.slot)
+                    else:
+                        hip.unmask_token_grad_det(dx0, gbuf["mask"], gbuf["tok_slot"], part, g.Beff, g.L, Dd, s.slot, s.tok_off,
+                                                  s.tok_off + s.n_tok)
+                elif self.tie_order == "torch":
                     hip.unmask_token_grad_per_sample(dx0, gbuf["mask"], gbuf["tok_slot_ps"],
                                                      ps.g(m.mask_token[s.src]).view(s.G, Dd)[s.gi], g.Beff, g.L, Dd, s.slot)
                 else:
@@ -1473,15 +1666,23 @@ class MAEEngine(EngineBase):
             if not self.e2d_identity:
                 hip.cast_bf16(gbuf["dy_e2d"], gbuf["dy_e2d16"], M * Dd)
                 hip.gemm(hip.GEMM_NN, M, E, Dd, gbuf["dy_e2d16"], Dd, ps.h(lin.weight), E, gbuf["dhenc"], E)
-                hip.gemm(hip.GEMM_TN, Dd, E, M, gbuf["dy_e2d16"], Dd, gbuf["henc"], E, ps.g(lin.weight), E, AT)
-                hip.colsum(gbuf["dy_e2d16"], ps.g(lin.bias), M, Dd, Dd)
+                if self.deterministic:
+                    self._det_linear_grads(("e2d", g.name), gbuf["dy_e2d16"], gbuf["henc"], Dd, E, M, ps.g(lin.weight), ps.g(lin.bias))
+                else:
+                    hip.gemm(hip.GEMM_TN, Dd, E, M, gbuf["dy_e2d16"], Dd, gbuf["henc"], E, ps.g(lin.weight), E, AT)
+                    hip.colsum(gbuf["dy_e2d16"], ps.g(lin.bias), M, Dd, Dd)
                 self._grads_ready(lin)
             if self.joint is not None:   # final LN of the joint encoder, this group's rows
                 jt = self.joint
                 jn = jt.t.norm
-                hip.layernorm_bwd(gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn.weight, gbuf["mean_j"],
-                                  gbuf["rstd_j"], None, jt.dxa, jt.top16, ps.g(jn.weight), ps.g(jn.bias),
-                                  jt.top_bias_grad(), gbuf["ln_ws"], g.Beff, g.N, E)
+                dy = gbuf["dy_e2d" if self.e2d_identity else "dhenc"]
+                if self.deterministic:
+                    self._det_layernorm_bwd(("ln_joint", g.name), dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn, gbuf["mean_j"],
+                                            gbuf["rstd_j"], jt.dxa, jt.top16, jt.top_bias_grad(), g.Beff, g.N, E)
+                else:
+                    hip.layernorm_bwd(dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn.weight, gbuf["mean_j"],
+                                      gbuf["rstd_j"], None, jt.dxa, jt.top16, ps.g(jn.weight), ps.g(jn.bias),
+                                      jt.top_bias_grad(), gbuf["ln_ws"], g.Beff, g.N, E)
 
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":
@@ -1504,7 +1705,14 @@ class MAEEngine(EngineBase):
                 gbuf, st = self.gb[g.name], self.enc[g.name]
                 nrm = st.t.norm
                 s_hi, s_lo = min(hi, st.depth), min(lo, st.depth)
-                if first:
+                if first and self.deterministic:
+                    dy, dy_L, dy_off = ((self._djoint, m.joint_N, g.joint_off) if self.joint is not None else  # noqa: N806
+                                        (gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0))
+                    self._det_layernorm_bwd(("ln_enc", g.name), dy, dy_L, dy_off, st.x_last, g.N, 0, nrm, gbuf["mean_e"], gbuf["rstd_e"],
+                                            st.dxa, st.top16, st.top_bias_grad(), g.Beff, g.N, E)
+                    self._grads_ready(nrm)
+                    self._enc_state[g.name] = (st.dxa, st.top16)
+                elif first:
                     if self.joint is not None:
                         hip.layernorm_bwd(self._djoint, m.joint_N, g.joint_off, st.x_last, g.N, 0, nrm.weight, gbuf["mean_e"],
                                           gbuf["rstd_e"], None, st.dxa, st.top16, ps.g(nrm.weight), ps.g(nrm.bias),
@@ -1533,6 +1741,8 @@ class MAEEngine(EngineBase):
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":      # this segment's layers of every group encoder
             self._launch_wgrads([(st, min(lo, st.depth), min(hi, st.depth)) for st in self.enc.values()])
+        elif self.deterministic and last:
+            self._det_finish_backward()
         elif self._plan == "all" and last:
             self._launch_wgrads([(st, 0, st.depth) for st in self._all_stacks()])
         if last:

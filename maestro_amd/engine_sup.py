@@ -22,9 +22,12 @@ from maestro_amd.engine import BF16, F32, I32, EngineBase, ParamStore, Stack
 
 
 class SupervisedEngine(EngineBase):
-    def __init__(self, model, batch_size: int, device, phase: str = "finetune") -> None:
+    def __init__(self, model, batch_size: int, device, phase: str = "finetune", deterministic: bool = False) -> None:
         if phase not in ("probe", "finetune"):
             raise ValueError(f"Invalid ssl phase {phase}. Expected 'probe' or 'finetune'")
+        if deterministic:
+            raise ValueError("deterministic=True is not available for the probe / finetune step: the loss accumulators and the "
+                             "head reductions of SupervisedEngine still use floating-point atomics (pretraining only)")
         device = torch.device(device)
         if device.type != "cuda":
             raise hip.HipExtensionError("SupervisedEngine needs a GPU device; there is no CPU fallback")

@@ -7,6 +7,7 @@ with HIP events on their launch stream for bench.py's roofline leg.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from pathlib import Path
@@ -42,6 +43,10 @@ def lib() -> ctypes.CDLL:
         _lib.mh_confusion_ce.argtypes = [vp, vp, ci, ctypes.c_long, vp, ci, ci, ci, ci, ci, vp]
         _lib.mh_confusion_bce.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp, ci, ci, vp]
         _lib.mh_confusion_ce.restype = _lib.mh_confusion_bce.restype = ci
+        _lib.mh_reduce_ordered.argtypes = [vp, vp, ci, vp, ci, vp]          # include/maestro_hip_det.h
+        _lib.mh_colsum_partial_rows.argtypes = [ci]
+        _lib.mh_masked_loss_partial_size.argtypes = _lib.mh_embed_bwd_partial_rows.argtypes = [ci, ci]
+        _lib.mh_unmask_token_grad_partial_rows.argtypes = [ctypes.c_long]
     return _lib
 
 
@@ -241,7 +246,25 @@ def _tune_gemm(key, args) -> int:
     return best
 
 
+_shape_only = 0
+
+
+@contextlib.contextmanager
+def shape_only_tiles():
+    """Deterministic mode: inside the block every GEMM without an explicit tile runs the library's own rule (MH_TILE_AUTO, a
+    function of shapes, strides and flags) -- neither the process-wide table of tuned tiles nor the MH_GEMM_* experiment
+    switches are consulted, so the kernel that runs does not depend on a measured time or on the environment."""
+    global _shape_only
+    _shape_only += 1
+    try:
+        yield
+    finally:
+        _shape_only -= 1
+
+
 def _pick_tile(layout, M, N, K, flags, args) -> int:  # noqa: N803
+    if _shape_only:
+        return TILE_AUTO
     tflags = flags & ~COLSUM                 # the column-sum side output does not change the kernel's cost profile
     key = (layout, M, N, K, tflags)
     tile = _tile_choice.get(key)
@@ -415,6 +438,137 @@ class ColsumBatch:
 
     def launch(self) -> None:
         call("mh_colsum_batched", self.table, _I(self.n), self.blocks, _I(self.n_blocks))
+
+
+# ---- deterministic mode (include/maestro_hip_det.h): atomic-free first phases + the ordered reduction that finishes them
+ORDERED_ROWS, ORDERED_ADD = 16, 1     # MH_ORDERED_ROWS, MH_ORDERED_ADD
+COLSUM_PARTIAL_ROWS = 256             # MH_COLSUM_PARTIAL_ROWS
+
+
+class _MhOrderedJob(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
+                ("ld", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+class OrderedReduce:
+    """Descriptor table (built once: all buffers are static) for ``mh_reduce_ordered``: jobs ``(src f32 [rows, ld], dst f32 [cols],
+    rows, cols, ld[, add])`` -> ``dst = (add ? dst : 0) + ordered column sums of src`` in one launch, without atomics.  Jobs that
+    share a ``dst`` form a chain: the table lists chains in the order of their first job and keeps the caller's order inside a
+    chain, which is the order in which their totals are added.  ``add`` must agree inside a chain."""
+
+    def __init__(self, jobs, device) -> None:
+        if not jobs:
+            raise HipExtensionError("OrderedReduce: no jobs")
+        chains: dict = {}
+        for i, job in enumerate(jobs):
+            if len(job) not in (5, 6):
+                raise HipExtensionError(f"OrderedReduce job {i}: (src, dst, rows, cols, ld[, add]) expected")
+            src, dst, rows, cols, ld = job[:5]
+            add = bool(job[5]) if len(job) == 6 else False
+            if not (isinstance(src, torch.Tensor) and isinstance(dst, torch.Tensor)) or src.dtype != torch.float32 \
+                    or dst.dtype != torch.float32 or not src.is_cuda or not dst.is_cuda:
+                raise HipExtensionError(f"OrderedReduce job {i}: f32 device tensors expected")
+            if rows <= 0 or cols <= 0 or ld < cols or src.numel() < (rows - 1) * ld + cols or dst.numel() < cols:
+                raise HipExtensionError(f"OrderedReduce job {i}: shape ({rows}, {cols}, ld {ld}) does not fit its buffers")
+            chain = chains.setdefault(dst.data_ptr(), [])
+            if chain and (chain[0][3] != cols or chain[0][5] != add):
+                raise HipExtensionError(f"OrderedReduce job {i}: cols / add differ from the other jobs of its destination")
+            chain.append((src, dst, rows, cols, ld, add))
+        spans = sorted((c[0][1].data_ptr(), c[0][1].data_ptr() + 4 * c[0][3]) for c in chains.values())
+        if any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+            raise HipExtensionError("OrderedReduce: two destinations overlap without being the same")
+        flat = [j for chain in chains.values() for j in chain]
+        arr = (_MhOrderedJob * len(flat))()
+        blocks, i = [], 0
+        for chain in chains.values():
+            blocks += [(i << 32) | cb for cb in range(-(-chain[0][3] // 256))]
+            for src, dst, rows, cols, ld, add in chain:
+                arr[i] = _MhOrderedJob(src.data_ptr(), dst.data_ptr(), rows, cols, ld, ORDERED_ADD if add else 0)
+                i += 1
+        self.keep = [t for j in flat for t in j[:2]]         # the descriptors hold raw pointers
+        self.host = arr
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+        self.blocks = torch.tensor(blocks, dtype=torch.int64).to(device)
+        self.n, self.n_blocks, self.n_chains = len(flat), len(blocks), len(chains)
+        self.nbytes = 4.0 * (sum(j[2] * j[3] for j in flat) + sum(c[0][3] for c in chains.values()))     # algorithmic: partial rows read, outputs written
+
+    def launch(self) -> None:
+        ev = _timer.record_bytes("reduce_ordered", self.nbytes) if _timer is not None else None
+        if ev is not None:
+            ev[0].record()
+        _check(lib().mh_reduce_ordered(ctypes.byref(self.host), ptr(self.table), _I(self.n), ptr(self.blocks), _I(self.n_blocks),
+                                       stream()), "mh_reduce_ordered")
+        if ev is not None:
+            ev[1].record()
+
+
+def colsum_partial_rows(M) -> int:  # noqa: N803
+    return int(lib().mh_colsum_partial_rows(_I(M)))
+
+
+def colsum_partial(x, partial, M, N, ld):  # noqa: N803
+    """Per-row-block column sums of ``x`` (bf16 / f32 [M, ld]) into ``partial`` f32 [colsum_partial_rows(M), N], plain stores."""
+    call("mh_colsum_partial", x, _I(1 if x.dtype == torch.float32 else 0), partial, _I(M), _I(N), _I(ld))
+
+
+def masked_loss_partial_size(B, Lm) -> int:  # noqa: N803
+    return int(lib().mh_masked_loss_partial_size(_I(B), _I(Lm)))
+
+
+def masked_loss_det(rec, target, mask_group, n_masked, weight, loss_partial, drec, B, Lm, Lgroup, tok_off, PPC, p):  # noqa: N803
+    """``masked_loss`` whose workgroups store their partial losses to ``loss_partial`` [masked_loss_partial_size(B, Lm)]."""
+    _hbm_call("masked_loss", float(B) * Lm * (PPC * (_esz(rec) + 4 + _esz(drec)) + 1), "mh_masked_loss_det", rec, target, mask_group,
+              n_masked, _F(weight), loss_partial, drec, _I(B), _I(Lm), _I(Lgroup), _I(tok_off), _I(PPC), _I(p))
+
+
+def masked_loss_bands_det(rec, target, mask_group, n_elems, weight, loss_partial, drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C,  # noqa: N803
+                          tgt_c0, n_g):
+    call("mh_masked_loss_bands_det", rec, target, mask_group, n_elems, _F(weight), loss_partial, drec, _I(B), _I(Lm), _I(Lgroup),
+         _I(tok_off), _I(PPC), _I(p), _I(tgt_C), _I(tgt_c0), _I(n_g))
+
+
+def unmask_token_grad_partial_rows(n_rows) -> int:
+    return int(lib().mh_unmask_token_grad_partial_rows(_L(n_rows)))
+
+
+def unmask_token_grad_det(dxdec, mask, tok_slot, partial, B, L, Dd, slot, t_lo, t_hi):  # noqa: N803
+    """``unmask_token_grad`` into per-workgroup rows ``partial`` [unmask_token_grad_partial_rows(B * (t_hi - t_lo)), Dd]."""
+    call("mh_unmask_token_grad_det", dxdec, mask, tok_slot, partial, _I(B), _I(L), _I(Dd), _I(slot), _I(t_lo), _I(t_hi))
+
+
+def unmask_token_grad_per_sample_det(dxdec, mask, tok_slot_bl, partial, B, L, Dd, slot):  # noqa: N803
+    """``unmask_token_grad_per_sample`` into per-workgroup rows ``partial`` [unmask_token_grad_partial_rows(B * L), Dd]."""
+    call("mh_unmask_token_grad_per_sample_det", dxdec, mask, tok_slot_bl, partial, _I(B), _I(L), _I(Dd), _I(slot))
+
+
+def embed_bwd_partial_rows(BD, L) -> int:  # noqa: N803
+    return int(lib().mh_embed_bwd_partial_rows(_I(BD), _I(L)))
+
+
+def embed_finish_bwd_det(dxg, y, stats, gamma, dyc, param_partial, blk_sums, sums, B, D, L, E, tok_off, Lgroup):  # noqa: N803
+    """``embed_finish_bwd`` without atomics: ``param_partial`` [embed_bwd_partial_rows(B * D, L), 2 E] keeps the dgamma | dbeta rows
+    for an ``OrderedReduce``, ``blk_sums`` [embed_bwd_partial_rows(B * D, L), 2] is scratch of the call."""
+    call("mh_embed_finish_bwd_det", dxg, y, stats, gamma, dyc, param_partial, blk_sums, sums, _I(B), _I(D), _I(L), _I(E),
+         _I(tok_off), _I(Lgroup))
+
+
+def det_slices(K: int) -> int:  # noqa: N803
+    """Number of K-slices of a weight-gradient GEMM outside the transformer stacks in deterministic mode: a function of the
+    shape alone (one slice per 1024 rows of K, at most 8)."""
+    return max(1, min(8, K // 1024))
+
+
+def gemm_tn_slabs(M, N, K, A, lda, B, ldb, slabs):  # noqa: N803
+    """dW[M, N] = A[K, M]^T B[K, N] as ``det_slices(K)`` plain-store TN GEMMs on consecutive K-slices, slice i into the private
+    fp32 slab ``slabs[i]`` ([M, N] dense); an ``OrderedReduce`` job (rows = slices, cols = M N, ld = M N) sums them."""
+    S = slabs.shape[0]  # noqa: N806
+    step = -(-(-(-K // S)) // 64) * 64
+    for i in range(S):
+        k0 = i * step
+        kn = min(K, k0 + step) - k0
+        if kn <= 0:                      # (cannot happen for det_slices: K // S >= 1024 > 64)
+            raise HipExtensionError(f"gemm_tn_slabs: empty K-slice {i} of {S} (K = {K})")
+        gemm(GEMM_TN, M, N, kn, A[k0:], lda, B[k0:], ldb, slabs[i], N, OUT_F32)
 
 
 def attn_fwd(qkv, out, lse, B, N, H, D, scale):

@@ -234,38 +234,45 @@ class MAE(nn.Module):
 
     # ------------------------------------------------------------------------------------------ engine plumbing
     def engine(self, batch_size: int, device=None, loss: str = "l2_norm", dtype: str | None = None,
-               fp8_scaling: str | None = None):
+               fp8_scaling: str | None = None, deterministic: bool | None = None):
         """Return (building on first use / batch-size change) the HIP step engine bound to these parameters.  ``dtype``:
         "bf16" (default) or "fp8" (e4m3 forward GEMMs, maestro_amd/fp8.py); None keeps the current engine's / MAESTRO_DTYPE.
-        ``fp8_scaling`` (fp8 only): "tensor" or "mx"; None keeps the current fp8 engine's / MAESTRO_FP8_SCALING."""
+        ``fp8_scaling`` (fp8 only): "tensor" or "mx"; None keeps the current fp8 engine's / MAESTRO_FP8_SCALING.
+        ``deterministic``: bit-reproducible steps without floating-point atomics (``MAEEngine``); None reads
+        ``MAESTRO_DETERMINISTIC`` ("1" = on).  A change of the flag rebuilds the engine, as a change of ``dtype`` does."""
         import os
 
-        from maestro_amd.engine import MAEEngine
+        from maestro_amd.engine import MAEEngine, resolve_deterministic
         from maestro_amd.fp8 import resolve_scaling
 
         device = torch.device(device) if device is not None else next(self.parameters()).device
         if dtype is None:
             dtype = self._engine.dtype if self._engine is not None else os.environ.get("MAESTRO_DTYPE", "bf16")
+        det = resolve_deterministic(deterministic)
         scaling = None
         if dtype == "fp8":
             keep = self._engine is not None and self._engine.fp8_scaling is not None and fp8_scaling is None
             scaling = self._engine.fp8_scaling if keep else resolve_scaling(fp8_scaling)
         if self._engine is None or self._engine.B != batch_size or self._engine.loss != loss \
-                or self._engine.device != device or self._engine.dtype != dtype or self._engine.fp8_scaling != scaling:
+                or self._engine.device != device or self._engine.dtype != dtype or self._engine.fp8_scaling != scaling \
+                or self._engine.deterministic != det:
             self._sup_engine = None
-            self._engine = MAEEngine(self, batch_size, device, loss=loss, dtype=dtype, fp8_scaling=scaling)
+            self._engine = MAEEngine(self, batch_size, device, loss=loss, dtype=dtype, fp8_scaling=scaling, deterministic=det)
         return self._engine
 
-    def sup_engine(self, batch_size: int, device=None, phase: str = "finetune"):
+    def sup_engine(self, batch_size: int, device=None, phase: str = "finetune", deterministic: bool | None = None):
         """The probe / finetune step engine (unmasked encoders + heads + loss_pred).  One engine owns the parameters at a
-        time: building this one re-homes them, so a pretrain engine of the same model is dropped (and vice versa)."""
+        time: building this one re-homes them, so a pretrain engine of the same model is dropped (and vice versa).
+        ``deterministic`` (None reads ``MAESTRO_DETERMINISTIC``): refused, the supervised step has no deterministic mode yet."""
+        from maestro_amd.engine import resolve_deterministic
         from maestro_amd.engine_sup import SupervisedEngine
 
         device = torch.device(device) if device is not None else next(self.parameters()).device
         e = self._sup_engine
-        if e is None or e.B != batch_size or e.phase != phase or e.device != device:
-            self._engine = None
-            self._sup_engine = SupervisedEngine(self, batch_size, device, phase=phase)
+        det = resolve_deterministic(deterministic)      # resolved on every call: a cached engine does not bypass the refusal
+        if det or e is None or e.B != batch_size or e.phase != phase or e.device != device:
+            new = SupervisedEngine(self, batch_size, device, phase=phase, deterministic=det)    # (raises when det)
+            self._engine, self._sup_engine = None, new
         return self._sup_engine
 
     def forward(self, batch: dict, ssl_phase: str = "pretrain"):

@@ -34,14 +34,22 @@ class PretrainLoop:
                  betas=(0.9, 0.99), weight_decay: float = 0.01, total_steps: int = 1000, world_size: int = 1,
                  final_factor: float = 1e7, bucket_mb: int = 64, exchange: bool | None = None,
                  accumulate: int = 1, overlap_optimizer: bool = False, bucket_dtype=None, dtype: str | None = None,
-                 exchange_mode: str | None = None, fp8_scaling: str | None = None) -> None:
-        """``exchange_mode``: "all_reduce" (default; ``MAESTRO_EXCHANGE`` overrides) -- every bucket is all-reduced, every rank runs
+                 exchange_mode: str | None = None, fp8_scaling: str | None = None, deterministic: bool | None = None) -> None:
+        """``deterministic``: bit-reproducible steps (``MAEEngine``; None reads ``MAESTRO_DETERMINISTIC``); excludes a gradient
+        exchange, ``overlap_optimizer`` and ``dtype="fp8"``.  ``exchange_mode``: "all_reduce" (default; ``MAESTRO_EXCHANGE`` overrides) -- every bucket is all-reduced, every rank runs
         the whole AdamW; "rs_ag" -- every bucket is reduce-scattered, a rank updates its 1 / world share of every bucket and the
         updated fp32 masters are all-gathered (``GradSync`` / ``FusedAdamW.step_sharded``).  ``fp8_scaling`` (with
         ``dtype="fp8"``): "tensor" or "mx" (maestro_amd/fp8.py); None reads ``MAESTRO_FP8_SCALING``."""
         import os
         self.exchange_mode = exchange_mode or os.environ.get("MAESTRO_EXCHANGE", "all_reduce")
-        self.engine = model.engine(batch_size, device, loss=loss, dtype=dtype, fp8_scaling=fp8_scaling)
+        from maestro_amd.engine import resolve_deterministic
+        if resolve_deterministic(deterministic):     # refused before anything is built
+            if overlap_optimizer:
+                raise ValueError("deterministic=True excludes overlap_optimizer")
+            if exchange or (exchange is None and world_size > 1):
+                raise ValueError("deterministic=True excludes a gradient exchange (the order of the cross-rank sum is the "
+                                 "collective library's)")
+        self.engine = model.engine(batch_size, device, loss=loss, dtype=dtype, fp8_scaling=fp8_scaling, deterministic=deterministic)
         self.engine.warm_passes = training_warm_passes()     # a training entry point: start-up passes on (engine.py: warm_passes)
         if overlap_optimizer and self.engine.fp8 is not None:
             raise ValueError("overlap_optimizer is not available with dtype='fp8' (the e4m3 weight shadows are rebuilt after the update)")
