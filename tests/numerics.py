@@ -11,6 +11,8 @@ tests/test_numerics_gpu.py (the HIP kernels against the same bounds).  Nothing h
   the CDF; 2^-22 covers the handful of fp32 roundings of the epilogue's arithmetic.
 * Normalisation statistics (``norm_ceiling``): twice the larger error of two honest fp32 algorithms (torch's own op; a two-pass
   reduction in wave order, ``wave_two_pass_stats``) against fp64 on the very inputs of the case.
+* Attention (``attn_bounds``): a first-order propagation of every rounding of csrc/attn.hip through softmax and its gradient; the
+  derivation stands in front of the function, the measured slack in profiles/attn_numerics.md.
 """
 
 from __future__ import annotations
@@ -260,3 +262,251 @@ def max_rel_err(got: torch.Tensor, want64: torch.Tensor) -> float:
 def norm_ceiling(err_a: float, err_b: float) -> float:
     """Twice the larger error of two legitimate fp32 algorithms: the kernel may use a third order of the same quality."""
     return 2.0 * max(err_a, err_b)
+
+
+# ------------------------------------------------------------------------------------------------ attention
+# Per head: q, k, v, do [N, D] fp32 tensors holding bf16 values; scale = D^-0.5, c = scale log2(e).  Kernels: csrc/attn.hip.
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+FLUSH_F32 = 2.0 ** -126     # smallest normal fp32: v_exp_f32 and the matrix cores return 0 below it
+ATTN_TILE = 64              # keys per forward tile
+ATTN_RANGE = 24.0           # ATTN_LAZY_RANGE
+ATTN_KINDS = ("randn1.5", "randn3", "offset", "neg", "rising", "peaked", "spike_late", "low_after_high")
+# terms of attn_bounds that the self-check removes one at a time to show that each is needed
+ATTN_BOUND_TERMS = ("fold", "fl_E", "fl_EP", "fl_store")
+B_FACTOR = 2.0              # criterion B: norm_ceiling's factor (the kernel may use another order of the same quality)
+B_FLOOR = 0.02              # criterion B is void where the emulation's own error norm is below this share of the bound's norm
+
+
+def attn_operands(kind: str, N: int, D: int, seed: int = 0):  # noqa: N803
+    """``q, k, v, do`` [N, D].  The shifted kinds put a logit of about +-40 on one direction (amp^2 scale = 40), as
+    test_attention_reference_exponent_moves does:
+
+    randn1.5 / randn3   q, k = a randn: logit sigma a^2 (2.25: the regime of test_attention_fwd_bwd; 9: maxima about 45)
+    offset / neg        q + amp e0, k +- amp e0: every logit about +-40, the first tile moves the reference exponent up / down
+    rising              q = 0.3 q + amp e0, k = 0.3 k + 0.75 amp (j // 64) e0: the reference moves up at every tile; from three tiles
+                        on the early keys' probabilities are fp32 denormals
+    peaked              q = 0.3 q + amp u_i, k = 0.3 k + amp u_perm(i), u_i random unit vectors: one key at logit about 40 per query,
+                        a saturated softmax (dP - delta cancels)
+    spike_late          plain randn, but queries 7 and 40 are 0.3 q + amp e0 and key 150 (the last key where N <= 150) is
+                        0.3 k + 3 amp e0: one wave leaves the range at a late tile while most of its lanes do not
+    low_after_high      q + amp e0; keys >= 64 get - 1.5 amp e0: tiles far below an established reference, which never moves down"""
+    g = torch.Generator().manual_seed(2654435 * seed + 131 * N + D + 7919 * ATTN_KINDS.index(kind))
+    q, k, v, do = (torch.randn(N, D, generator=g) for _ in range(4))
+    amp = (40.0 * D ** 0.5) ** 0.5
+    e0 = torch.zeros(D)
+    e0[0] = 1.0
+    if kind.startswith("randn"):
+        a = float(kind[5:])
+        q, k = a * q, a * k
+    elif kind == "offset":
+        q, k = q + amp * e0, k + amp * e0
+    elif kind == "neg":
+        q, k = q + amp * e0, k - amp * e0
+    elif kind == "rising":
+        q = 0.3 * q + amp * e0
+        k = 0.3 * k + 0.75 * amp * (torch.arange(N) // ATTN_TILE).float()[:, None] * e0
+    elif kind == "peaked":
+        perm = torch.randperm(N, generator=g)
+        u = torch.nn.functional.normalize(torch.randn(N, D, generator=g), dim=-1)
+        q, k = 0.3 * q + amp * u, 0.3 * k + amp * u[perm]
+    elif kind == "spike_late":
+        for i in (7, 40):
+            if i < N:
+                q[i] = 0.3 * q[i] + amp * e0
+        j = 150 if N > 150 else N - 1
+        k[j] = 0.3 * k[j] + 3.0 * amp * e0
+    elif kind == "low_after_high":
+        q = q + amp * e0
+        k[ATTN_TILE:] = k[ATTN_TILE:] - 1.5 * amp * e0
+    else:
+        raise ValueError(kind)
+    return bf16_round(q), bf16_round(k), bf16_round(v), bf16_round(do)
+
+
+def attn_ref64(q, k, v, do):
+    """fp64 attention forward and backward of one head on the operands' device (dict): S = q k^T, A = S scale, lse, P, O, delta,
+    G = dP - delta, dQ, dK, dV and Sabs = |q| |k|^T."""
+    q, k, v, do = (t.double() for t in (q, k, v, do))
+    scale = q.shape[-1] ** -0.5
+    S = q @ k.T  # noqa: N806
+    A = S * scale  # noqa: N806
+    lse = torch.logsumexp(A, -1)
+    P = torch.exp(A - lse[:, None])  # noqa: N806
+    O = P @ v  # noqa: N806, E741
+    delta = (O * do).sum(-1)
+    G = do @ v.T - delta[:, None]  # noqa: N806
+    dSs = P * G  # noqa: N806  (dS / scale)
+    return dict(S=S, A=A, lse=lse, P=P, O=O, delta=delta, G=G, dQ=scale * dSs @ k, dK=scale * dSs.T @ q, dV=P.T @ do,
+                Sabs=q.abs() @ k.abs().T)
+
+
+# The error model, to first order (expm1 where an exponent error is exponentiated); u = 2^-24, HB = 2^-8, FL = 2^-126, 2^-23 per
+# accumulated fp32 term as in gemm_bound.  Line numbers: csrc/attn.hip.
+#
+# Forward (attn_fwd_kernel).  The exp2 argument of score j of query i is fma(s, c, -m) - mx (fms4, :252 and :282): s is an fp32
+# sum of D exact products (c D 2^-23 Sabs in log2 units), c = fl(scale log2e) (u |A| log2e), the two FMAs round a value of at most
+# (|A| + amax) log2e + 24 (the reference m lies within 24 of a score that was there): together dt.  m itself is common to the row
+# and cancels in P / l; in lse it is multiplied by ln 2 once (:409).  v_exp_f32 is good to one ulp (2^-22 covers it), and every
+# move of the reference multiplies what was accumulated by alpha = exp2(-mx), one exp2 and one product per tile: nt 2^-22.
+# eta is the relative error of an fp32 probability, eta_b = eta + HB (1 + eta) that of its bf16 image (pack_bf2, :297).
+# O = (sum_j pb_j v_j) / l: the numerator is an fp32 sum of N exact products of erroneous pb; the denominator is the same sum
+# against ones at D = 32 (ATTN_SUM_MFMA, :379: eta_b) and an fp32 sum of the unrounded p at D = 64 (:294-296: eta).  1 / l and
+# the product with it (:400, :404) are 2^-22 |O|, the store (:405) HB.
+# lse = m ln2 + logf(l) (:409): the relative error of l, one ulp of logf and of the sum at |lse|, the product m ln2 with
+# |m ln2| <= amax + 24: b_lse.  (ocml's logf is stated at 1 ulp; 4 u (|lse| + ...) has room for that, not widened.)
+#
+# Backward (attn_bwd_dq_kernel / attn_bwd_dkv_kernel).  Both recompute P = exp2(q' k^T - lse log2e) with ONE operand folded:
+# q' = bf16(fl(q fl(c))) (scale_frag, :162, called at :456 resp. :600 on k): HB + 3u relative per product, so (HB + 3u) c Sabs --
+# the FOLD term.  The MFMA chain starts at -fl(lse log2e) (:464/:499, :635/:656) and adds D products: (D + 2) 2^-23 of the
+# magnitudes; the lse it is given is off by lse_err.  rho is the relative error of a recomputed probability.
+# delta (:460-463) is an fp32 sum of D products of the bf16 out (off from O64 by out_err) with dO.  dP - delta is a chain that
+# starts at -delta and adds D products (:503, :515): eg.  dS / scale = bf16(p g) (:534/:680 mul4, pack_acc): E.  dQ, dK are fp32
+# sums over N of exact products, times scale (:558, :711), stored as bf16.  dV uses bf16(p) (:687): EP.
+# Underflow: a probability, a product p g or a bf16 image below 2^-126 is returned as 0 by the hardware (and an fp64 reference
+# keeps it): FL per element of E and EP (fl_E, fl_EP), and FL on each stored gradient / output (fl_store).
+def attn_bounds(ref, q, k, v, do, lse_err=None, out_err=None, drop=()):
+    """Elementwise a-priori bounds (dict: O, lse, delta, dQ, dK, dV) for ``ref = attn_ref64(q, k, v, do)``.  ``lse_err`` [N] /
+    ``out_err`` [N, D]: the errors of the lse / out handed to the backward (default: an fp32-rounded lse64 and a bf16-rounded O64).
+    ``drop``: names from ATTN_BOUND_TERMS to leave out (self-check only)."""
+    assert set(drop) <= set(ATTN_BOUND_TERMS), drop
+    N, D = q.shape  # noqa: N806
+    scale = D ** -0.5
+    c = scale * LOG2E
+    u, HB = U_F32, HALF_ULP_BF16  # noqa: N806
+    fl_e = 0.0 if "fl_E" in drop else FLUSH_F32
+    fl_ep = 0.0 if "fl_EP" in drop else FLUSH_F32
+    fl_st = 0.0 if "fl_store" in drop else FLUSH_F32
+    fold = 0.0 if "fold" in drop else HB
+    q, k, v, do = (t.double().abs() for t in (q, k, v, do))
+    P, O, A, Sabs = ref["P"], ref["O"].abs(), ref["A"].abs(), ref["Sabs"]  # noqa: N806, E741
+    lse = ref["lse"].abs()
+    amax = A.max(-1, keepdim=True).values
+    nt = (N + ATTN_TILE - 1) // ATTN_TILE
+    # forward
+    dt = c * D * 2.0 ** -23 * Sabs + 2.0 ** -22 * ((A + amax) * LOG2E + ATTN_RANGE)
+    eta = torch.expm1(LN2 * dt) + 2.0 ** -22 + nt * 2.0 ** -22
+    eta_b = eta + HB * (1 + eta)
+    eta_den = eta_b if D == 32 else eta
+    num = (P * eta_b) @ v + N * 2.0 ** -23 * (P @ v)
+    den = (P * eta_den).sum(-1, keepdim=True) + N * 2.0 ** -23
+    bO = (num + O * den) * (1 + den)  # noqa: N806
+    bO = bO + HB * (O + bO) + 2.0 ** -22 * O + fl_st  # noqa: N806
+    b_lse = den[:, 0] + 2.0 ** -22 + 4 * u * (lse + amax[:, 0] + ATTN_RANGE)
+    # backward
+    le = u * lse if lse_err is None else lse_err.double()
+    dtb = (fold + 3 * u) * c * Sabs + (D + 2) * 2.0 ** -23 * (c * Sabs + lse[:, None] * LOG2E) + LOG2E * le[:, None]
+    rho = torch.expm1(LN2 * dtb) + 2.0 ** -22
+    OdO = (O * do).sum(-1)  # noqa: N806
+    oe = HB * OdO if out_err is None else (out_err.double() * do).sum(-1)
+    b_delta = oe + (D + 2) * 2.0 ** -23 * OdO
+    eg = b_delta[:, None] + (D + 2) * 2.0 ** -23 * (do @ v.T + ref["delta"].abs()[:, None])
+    G = ref["G"].abs()  # noqa: N806
+    mag = (G + eg) * (1 + rho)
+    E = P * (rho * G + (1 + rho) * eg + 2 * u * (G + eg) + HB * mag) + fl_e * (mag + 1)  # noqa: N806
+    b_dq = scale * (E @ k + N * 2.0 ** -23 * ((P * mag) @ k))
+    b_dq = b_dq + HB * (ref["dQ"].abs() + b_dq) + 2 * u * ref["dQ"].abs() + fl_st
+    b_dk = scale * (E.T @ q + N * 2.0 ** -23 * ((P * mag).T @ q))
+    b_dk = b_dk + HB * (ref["dK"].abs() + b_dk) + 2 * u * ref["dK"].abs() + fl_st
+    EP = P * (rho + HB * (1 + rho)) + 2 * fl_ep  # noqa: N806
+    b_dv = EP.T @ do + N * 2.0 ** -23 * (P.T @ do)
+    b_dv = b_dv + HB * (ref["dV"].abs() + b_dv) + fl_st
+    return dict(O=bO, lse=b_lse, delta=b_delta, dQ=b_dq, dK=b_dk, dV=b_dv)
+
+
+def _fma32(a: torch.Tensor, c: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """fl32(a c - b) with one rounding (the product of two fp32 values is exact in fp64)."""
+    return (a.double() * c.double() - b.double()).float()
+
+
+def _flush32(x: torch.Tensor) -> torch.Tensor:
+    """What the hardware returns for an fp32 denormal result of v_exp_f32, of a bf16 convert or of a matrix-core sum: zero."""
+    return torch.where(x.abs() < FLUSH_F32, torch.zeros_like(x), x)
+
+
+def _c32(D: int) -> torch.Tensor:  # noqa: N803
+    """fl(scale log2e) as the kernels form it: an fp32 product of the fp32 scale and the fp32 constant."""
+    return torch.tensor(D ** -0.5, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32)
+
+
+def attn_emulated_fwd(q, k, v, defect=None):
+    """torch fp32 emulation of attn_fwd_kernel as written (ATTN_LAZY_MAX = 1): groups of 16 queries (one ``qt`` of a wave) over
+    64-key tiles, the range test per lane (16 keys of the tile) as in the kernel; returns ``out`` (bf16 values) and ``lse``.  ``defect`` = "p_trunc": the WRONG form that truncates P to bf16."""
+    N, D = q.shape  # noqa: N806
+    c = _c32(D)
+    ng = (N + 15) // 16
+    qq = torch.zeros(ng * 16, D)
+    qq[:N] = q                                   # rows >= N: zero operands, as frag_global gives them
+    qq = qq.view(ng, 16, D)
+    m = torch.zeros(ng, 16)
+    lsum = torch.zeros(ng, 16)
+    o = torch.zeros(ng, 16, D)
+    for it, k0 in enumerate(range(0, N, ATTN_TILE)):
+        kk, vv = k[k0:k0 + ATTN_TILE], v[k0:k0 + ATTN_TILE]
+        s = _fma32(qq @ kk.T, c, m[..., None])
+        mx = s.max(-1).values
+        first = it == 0
+        # a lane holds keys 16 kt + 4 g + r (kt, r < 4) of its query and tests ITS maximum, keys >= N at -inf, before the cross-lane one
+        lane = torch.full((ng, 16, ATTN_TILE), -math.inf)
+        lane[..., :s.shape[-1]] = s
+        lane = lane.view(ng, 16, 4, 4, 4).amax((2, 4))
+        leave = (lane > ATTN_RANGE) | (lane < -ATTN_RANGE) if first else lane > ATTN_RANGE
+        moved = leave.any(-1).any(-1, keepdim=True)     # the ballot: one lane out of range moves all 16 queries to their row maxima
+        if not first:
+            mx = mx.clamp_min(0.0)
+        shift = torch.where(moved, mx, torch.zeros_like(mx))
+        alpha = torch.ones_like(mx) if first else torch.where(moved, torch.exp2(-mx), torch.ones_like(mx))
+        m = m + shift
+        s = s - shift[..., None]
+        lsum, o = lsum * alpha, o * alpha[..., None]
+        p = _flush32(torch.exp2(s))
+        pb = bf16_truncate(p) if defect == "p_trunc" else _flush32(bf16_round(p))
+        lsum = lsum + (pb if D == 32 else p).sum(-1)
+        o = o + pb @ vv
+    out = bf16_round(o * (1.0 / lsum)[..., None]).view(ng * 16, D)[:N]
+    lse = (m * torch.tensor(LN2, dtype=torch.float32) + torch.log(lsum)).view(-1)[:N]
+    return out.contiguous(), lse.contiguous()
+
+
+def attn_emulated_bwd(q, k, v, do, out, lse, fold=True, defect=None, row=0):
+    """torch fp32 emulation of attn_bwd_dq_kernel + attn_bwd_dkv_kernel as written; returns ``dq, dk, dv`` (bf16 values) and the
+    fp32 ``delta``.  ``fold=False`` applies scale log2(e) in fp32 instead of folding it into a bf16 operand (what the fold costs).
+    WRONG forms for the self-check: ``defect`` = "delta_bf16" (delta rounded to bf16), "fold_both" (sqrt(c) folded into Q and K,
+    both rounded), "row_lse" (the lse of the single query ``row`` is read 0.2 too high: its recomputed probabilities are 18 % low)."""
+    D = q.shape[1]  # noqa: N806
+    c = _c32(D)
+    scale = torch.tensor(D ** -0.5, dtype=torch.float32)
+    delta = (out * do).sum(-1)
+    if defect == "delta_bf16":
+        delta = bf16_round(delta)
+    if defect == "row_lse":
+        lse = lse.clone()
+        lse[row] += 0.2
+    lse2 = (lse * torch.tensor(LOG2E, dtype=torch.float32))[:, None]
+    if defect == "fold_both":
+        t_q = t_k = bf16_round(q * torch.sqrt(c)) @ bf16_round(k * torch.sqrt(c)).T - lse2
+    elif fold:
+        t_q = bf16_round(q * c) @ k.T - lse2          # dQ pass
+        t_k = q @ bf16_round(k * c).T - lse2          # dK / dV pass
+    else:
+        t_q = t_k = _fma32(q @ k.T, c, lse2)
+    g = do @ v.T - delta[:, None]
+    p_q, p_k = _flush32(torch.exp2(t_q)), _flush32(torch.exp2(t_k))
+    rb = lambda x: _flush32(bf16_round(x))  # noqa: E731
+    dq = rb(_flush32(rb(p_q * g) @ k) * scale)
+    dk = rb(_flush32(rb(p_k * g).T @ q) * scale)
+    dv = rb(_flush32(rb(p_k).T @ do))
+    return dq, dk, dv, delta
+
+
+def rel_l2(got: torch.Tensor, want64: torch.Tensor) -> float:
+    return float((got.double() - want64).norm() / want64.norm().clamp_min(1e-300))
+
+
+def attn_criterion_b(got, emulated, want64, bound):
+    """Criterion B: ``||got - want64|| <= B_FACTOR ||emulated - want64||``.  Returns ``(applies, got_norm, emulated_norm)``;
+    ``applies`` is False where the emulation's own error is below B_FLOOR of ``||bound||`` (a saturated softmax: both errors are a
+    few roundings of almost nothing, and their quotient says nothing)."""
+    e_got = float((got.double() - want64).norm())
+    e_emu = float((emulated.double().to(want64.device) - want64).norm())
+    return e_emu >= B_FLOOR * float(bound.norm()), e_got, e_emu
