@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "reduce_det.hpp"
 #include "../../include/maestro_hip.h"
+#include "../../include/maestro_hip_ends.h"
 
 namespace {
 
@@ -269,12 +270,17 @@ constexpr int EB_ROWS = 8;
 // two LDS round trips per element in a kernel that streams 8 bytes per element from HBM).  NV = 0: any E (the LDS form).
 // DET (deterministic mode, include/maestro_hip_det.h): no atomics -- the block writes its (S1, S2) to sums[bd, blockIdx.x, 2] and its
 // dgamma | dbeta row to dgamma[(bd * gridDim.x + blockIdx.x), 2 E] (dbeta unused); LDS then carries 8 more floats for the waves' sums.
-template <int NV, bool DET>
+// MAP (include/maestro_hip_ends.h, NV > 0 only): dxg is the gradient of the VISIBLE rows [B, n_vis, E] and inv [B, Lgroup] maps a group
+// position to its visible row (< 0: masked = a zero gradient).  A masked row adds nothing to any of the sums: the wave skips it
+// (the branch is wave-uniform) and issues none of its loads.
+template <int NV, bool DET, bool MAP = false>
 __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __restrict__ dxg, const float* __restrict__ y,
                                                               const float* __restrict__ stats, const float* __restrict__ gamma,
                                                               float* __restrict__ sums, float* __restrict__ dgamma,
                                                               float* __restrict__ dbeta, int B, int D, int L, int E,
-                                                              int tok_off, int Lgroup) {
+                                                              int tok_off, int Lgroup, const int* __restrict__ inv = nullptr,
+                                                              int n_vis = 0) {
+    static_assert(!MAP || NV > 0, "the position-map form keeps its sums in registers");
     extern __shared__ __attribute__((aligned(16))) float red[];  // [4][2][E]
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int bd = blockIdx.y, b = bd / D, d = bd - b * D;
@@ -296,6 +302,11 @@ __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __res
             if (l >= L) break;
             const float* yr = y + ((size_t)bd * L + l) * E;
             const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
+            if constexpr (MAP) {
+                const int iv = inv[(size_t)b * Lgroup + tok_off + d * L + l];
+                if (iv < 0) continue;
+                gr = dxg + ((size_t)b * n_vis + iv) * E;
+            }
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 const int c = lane * 4 + 256 * j;
@@ -402,6 +413,72 @@ __global__ __launch_bounds__(256) void embed_bwd_apply_kernel(const float* __res
         u32x2 pk = {pack_bf2(r[0], r[1]), pack_bf2(r[2], r[3])};
         *reinterpret_cast<u32x2*>(o + c) = pk;
     }
+}
+
+// ---- backward pass 2 with the conv bias gradient (include/maestro_hip_ends.h): the same arithmetic per element, EA_ROWS rows per wave, so
+// that a lane owns the same columns in every row and the column sums of the bf16 values it stores stay in registers; the block's four
+// waves meet in LDS and store one partial row.  MAP: the gradient through the position map (see embed_bwd_stats_kernel); a masked
+// row is a zero gradient -- its dyc row still depends on yconv -- and its gradient loads are skipped.
+constexpr int EA_ROWS = 8;
+template <int NV, bool MAP>
+__global__ __launch_bounds__(256) void embed_bwd_apply_cs_kernel(const float* __restrict__ dxg, const int* __restrict__ inv, int n_vis,
+                                                                 const float* __restrict__ y, const float* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ sums,
+                                                                 bf16_t* __restrict__ dyc, float* __restrict__ cs_partial,
+                                                                 int B, int D, int L, int E, int tok_off, int Lgroup) {
+    __shared__ f32x4 red[4][64 * NV];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long rows = (long)B * D * L, row0 = ((long)blockIdx.x * 4 + w) * EA_ROWS;
+    const float n = (float)L * (float)E;
+    f32x4 gm[NV], cs[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = lane * 4 + 256 * j;
+        cs[j] = (f32x4){0, 0, 0, 0};
+        gm[j] = c < E ? *reinterpret_cast<const f32x4*>(gamma + c) : (f32x4){0, 0, 0, 0};
+    }
+#pragma unroll 2
+    for (int rr = 0; rr < EA_ROWS; ++rr) {
+        const long row = row0 + rr;
+        if (row >= rows) break;
+        const int bd = (int)(row / L), l = (int)(row - (long)bd * L), b = bd / D, d = bd - b * D;
+        const float mu = stats[bd * 2], rs = stats[bd * 2 + 1];
+        const float c1 = sums[bd * 2] / n, c2 = sums[bd * 2 + 1] / n;
+        const float* yr = y + (size_t)row * E;
+        const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
+        bool vis = true;
+        if constexpr (MAP) {
+            const int iv = inv[(size_t)b * Lgroup + tok_off + d * L + l];
+            vis = iv >= 0;
+            gr = dxg + ((size_t)b * n_vis + (vis ? iv : 0)) * E;
+        }
+        bf16_t* o = dyc + (size_t)row * E;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = lane * 4 + 256 * j;
+            if (c < E) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(yr + c);
+                f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+                if (vis) dd = *reinterpret_cast<const f32x4*>(gr + c);
+                float r[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float z = (v[e] - mu) * rs;
+                    r[e] = rs * (dd[e] * gm[j][e] - c1 - z * c2);
+                }
+                const u32x2 pk = {pack_bf2(r[0], r[1]), pack_bf2(r[2], r[3])};
+                *reinterpret_cast<u32x2*>(o + c) = pk;
+                cs[j] += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
+                                 __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) red[w][lane + 64 * j] = cs[j];
+    __syncthreads();
+    const float* cr = reinterpret_cast<const float*>(red);
+    for (int c = threadIdx.x; c < E; c += 256)
+        cs_partial[(size_t)blockIdx.x * E + c] = (cr[c] + cr[256 * NV + c]) + (cr[512 * NV + c] + cr[768 * NV + c]);
 }
 
 // ---- patch layout -> image layout
@@ -654,6 +731,38 @@ extern "C" int mh_embed_finish_bwd(const float* dxg, const float* y, const float
     }
     hipLaunchKernelGGL(embed_bwd_apply_kernel, dim3(ceil_div((long)B * D * L, 4)), dim3(256), 0, s, dxg, y, stats, gamma, sums,
                        (bf16_t*)dyc, B, D, L, E, tok_off, Lgroup);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_embed_bwd_cs_rows(long rows) { return rows > 0 ? (int)ceil_div(rows, (long)(4 * EA_ROWS)) : 0; }
+
+extern "C" int mh_embed_finish_bwd_ends(const float* dx, const int* inv, int n_vis, const float* y, const float* stats,
+                                        const float* gamma, void* dyc, float* dgamma, float* dbeta, float* sums, float* cs_partial,
+                                        int B, int D, int L, int E, int tok_off, int Lgroup, void* stream) {
+    MH_CHECK_ARG(dx && y && stats && gamma && dyc && dgamma && dbeta && sums && cs_partial, "mh_embed_finish_bwd_ends: null pointer");
+    MH_CHECK_ARG(B > 0 && D > 0 && L > 0 && E > 0 && E % 4 == 0 && E <= 1024 && tok_off >= 0 && tok_off + D * L <= Lgroup &&
+                 (!inv || (n_vis > 0 && n_vis <= Lgroup)),
+                 "mh_embed_finish_bwd_ends: bad sizes B=%d D=%d L=%d E=%d (E %% 4 == 0, E <= 1024) tok_off=%d Lgroup=%d n_vis=%d", B, D, L, E,
+                 tok_off, Lgroup, n_vis);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(zero_f32_kernel, dim3(ceil_div((long)B * D * 2, 256)), dim3(256), 0, s, sums, B * D * 2);   // (a kernel: see mh_embed_finish_bwd)
+    const dim3 grid(ceil_div(L, 4 * EB_ROWS), B * D), block(256), grid2(mh_embed_bwd_cs_rows((long)B * D * L));
+    const size_t lds = (size_t)8 * E * sizeof(float);
+#define MH_EB_LAUNCH(NV, MAP) do { \
+        hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, false, MAP>), grid, block, lds, s, dx, y, stats, gamma, sums, dgamma, dbeta, B, D, L, \
+                           E, tok_off, Lgroup, inv, n_vis); \
+        hipLaunchKernelGGL((embed_bwd_apply_cs_kernel<NV, MAP>), grid2, block, 0, s, dx, inv, n_vis, y, stats, gamma, sums, (bf16_t*)dyc, \
+                           cs_partial, B, D, L, E, tok_off, Lgroup); } while (0)
+#define MH_EB_FORMS(NV) do { if (inv) MH_EB_LAUNCH(NV, true); else MH_EB_LAUNCH(NV, false); } while (0)
+    switch ((E + 255) / 256) {
+        case 1: MH_EB_FORMS(1); break;
+        case 2: MH_EB_FORMS(2); break;
+        case 3: MH_EB_FORMS(3); break;
+        default: MH_EB_FORMS(4); break;
+    }
+#undef MH_EB_FORMS
+#undef MH_EB_LAUNCH
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -1,6 +1,7 @@
 // Masked reconstruction loss at patch layout + its gradient, bias-gradient column sums, casts, fused AdamW.
 #include "gemm_common.hpp"
 #include "../../include/maestro_hip_det.h"
+#include "../../include/maestro_hip_ends.h"
 
 namespace {
 
@@ -11,12 +12,17 @@ namespace {
 // atomic (32768 -> 8192 atomics for the aerial modality; blocks whose 4 tokens are all visible issue none).
 // DET (deterministic mode, include/maestro_hip_det.h): the same arithmetic, but the block's partial loss goes to acc[blockIdx.x]
 // with a plain store instead of being added to the loss word.
-template <bool DET>
+// CS (include/maestro_hip_ends.h): the block also stores the column sums of the bf16 values it writes to drec -- the pixelify bias
+// gradient -- to cs_partial[blockIdx.x, 0 .. PPC) (plain stores, zeros included), PPC <= 256 * LOSS_CS_NV.  A lane owns the same
+// columns in every row, so the sums stay in registers until the block's four waves meet in LDS.
+constexpr int LOSS_CS_NV = 4;
+template <bool DET, bool CS = false>
 __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restrict__ rec, const float* __restrict__ target,
                                                           const uint8_t* __restrict__ mask_group, const int* __restrict__ n_masked,
                                                           float weight, float* __restrict__ acc, bf16_t* __restrict__ drec,
                                                           int B, int Lm, int Lgroup, int tok_off, int PPC, int p, int tgt_C,
-                                                          int tgt_c0, int n_g, int denom_is_elems, int rows_per_wave) {
+                                                          int tgt_c0, int n_g, int denom_is_elems, int rows_per_wave,
+                                                          float* __restrict__ cs_partial = nullptr) {
     // band window (several band-groups per modality): rec column k = pixel * n_g + c pairs with target column
     // pixel * tgt_C + tgt_c0 + c of the MODALITY's target rows (tgt_C channels); n_g == tgt_C: the plain case
     __shared__ float red[4];
@@ -25,6 +31,9 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
     const bool window = n_g != tgt_C;
     const int tgt_ld = window ? PPC / n_g * tgt_C : PPC;
     float s = 0.f;
+    f32x4 cs[CS ? LOSS_CS_NV : 1];
+#pragma unroll
+    for (int j = 0; j < (CS ? LOSS_CS_NV : 1); ++j) cs[j] = (f32x4){0, 0, 0, 0};
     // several rows per wave: the block's ONE atomic into the loss word costs ~10 ns of serialised time (same-line atomics,
     // scripts/micro_amax.hip) -- 8192 blocks of 4 rows made the aerial modality's launch 80 us of atomics
     for (int rr = 0; rr < rows_per_wave; ++rr) {
@@ -35,7 +44,7 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
         const float* r = rec + (size_t)row * PPC;
         const float* g = target + (size_t)row * tgt_ld;
         bf16_t* d = drec ? drec + (size_t)row * PPC : nullptr;
-        for (int c = lane * 4; c < PPC; c += 256) {
+        auto chunk = [&](int c, f32x4* colsum) {
             float dd[4] = {0.f, 0.f, 0.f, 0.f};
             if (masked) {
                 const f32x4 rv = *reinterpret_cast<const f32x4*>(r + c);
@@ -53,11 +62,28 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
                     else { s += fabsf(diff); dd[e] = (diff > 0.f ? coef : (diff < 0.f ? -coef : 0.f)); }
                 }
             }
-            if (d) {
-                u32x2 pk = {pack_bf2(dd[0], dd[1]), pack_bf2(dd[2], dd[3])};
-                *reinterpret_cast<u32x2*>(d + c) = pk;
-            }
+            u32x2 pk = {pack_bf2(dd[0], dd[1]), pack_bf2(dd[2], dd[3])};
+            if (d) *reinterpret_cast<u32x2*>(d + c) = pk;
+            if (CS && masked)
+                *colsum += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
+                                   __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+        };
+        if constexpr (CS) {
+#pragma unroll
+            for (int j = 0; j < LOSS_CS_NV; ++j)
+                if (lane * 4 + 256 * j < PPC) chunk(lane * 4 + 256 * j, &cs[j]);
+        } else {
+            for (int c = lane * 4; c < PPC; c += 256) chunk(c, nullptr);
         }
+    }
+    if constexpr (CS) {
+        __shared__ f32x4 csred[4][64 * LOSS_CS_NV];
+#pragma unroll
+        for (int j = 0; j < LOSS_CS_NV; ++j) csred[w][lane + 64 * j] = cs[j];
+        __syncthreads();
+        const float* cr = reinterpret_cast<const float*>(csred);
+        for (int c = threadIdx.x; c < PPC; c += 256)
+            cs_partial[(size_t)blockIdx.x * PPC + c] = (cr[c] + cr[256 * LOSS_CS_NV + c]) + (cr[512 * LOSS_CS_NV + c] + cr[768 * LOSS_CS_NV + c]);
     }
     s = wave_sum(s);
     if (lane == 0) red[w] = s;
@@ -324,6 +350,37 @@ extern "C" int mh_masked_loss_bands_det(const float* rec, const float* target, c
     const int rpw = loss_rows_per_wave((long)B * Lm);
     hipLaunchKernelGGL(masked_loss_kernel<true>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target,
                        mask_group, n_elems, weight, loss_partial, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_masked_loss_cs_rows(int B, int Lm) { return mh_masked_loss_partial_size(B, Lm); }
+
+extern "C" int mh_masked_loss_cs(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked, float weight,
+                                 float* acc, void* drec, float* cs_partial, int B, int Lm, int Lgroup, int tok_off, int PPC, int p,
+                                 void* stream) {
+    MH_CHECK_ARG(rec && target && mask_group && n_masked && acc && drec && cs_partial, "mh_masked_loss_cs: null pointer");
+    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC > 0 && PPC % 4 == 0 && PPC <= 256 * LOSS_CS_NV && tok_off >= 0 &&
+                 tok_off + Lm <= Lgroup, "mh_masked_loss_cs: bad arguments (PPC %% 4 == 0, PPC <= %d)", 256 * LOSS_CS_NV);
+    const int rpw = loss_rows_per_wave((long)B * Lm);
+    hipLaunchKernelGGL((masked_loss_kernel<false, true>), dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec,
+                       target, mask_group, n_masked, weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, 1, 0, 1, 0, rpw, cs_partial);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_masked_loss_bands_cs(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems,
+                                       float weight, float* acc, void* drec, float* cs_partial, int B, int Lm, int Lgroup, int tok_off,
+                                       int PPC, int p, int tgt_C, int tgt_c0, int n_g, void* stream) {
+    MH_CHECK_ARG(rec && target && mask_group && n_elems && acc && drec && cs_partial, "mh_masked_loss_bands_cs: null pointer");
+    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC > 0 && PPC % 4 == 0 && PPC <= 256 * LOSS_CS_NV && tok_off >= 0 &&
+                 tok_off + Lm <= Lgroup, "mh_masked_loss_bands_cs: bad arguments (PPC %% 4 == 0, PPC <= %d)", 256 * LOSS_CS_NV);
+    MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "mh_masked_loss_bands_cs: band window [%d, %d) of %d",
+                 tgt_c0, tgt_c0 + n_g, tgt_C);
+    const int rpw = loss_rows_per_wave((long)B * Lm);
+    hipLaunchKernelGGL((masked_loss_kernel<false, true>), dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec,
+                       target, mask_group, n_elems, weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw,
+                       cs_partial);
     MH_LAUNCH_CHECK();
     return 0;
 }

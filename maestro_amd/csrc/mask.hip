@@ -2,6 +2,7 @@
 // Integer/index work is bit-exact by construction (counting rank = stable argsort).
 #include "common.hpp"
 #include "../../include/maestro_hip.h"
+#include "../../include/maestro_hip_ends.h"
 
 namespace {
 
@@ -78,6 +79,55 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     const float* s = src + ((size_t)b * src_L + idx[row]) * dim;
     float* d = dst + ((size_t)b * dst_L + dst_off + j) * dim;
     for (int c = lane * 4; c < dim; c += 256) *reinterpret_cast<f32x4*>(d + c) = *reinterpret_cast<const f32x4*>(s + c);
+}
+
+// dst16[row, :] = bf16(src[b, idx[row], :]) and, per workgroup, the column sums of the bf16 values written (the enc_to_dec bias
+// gradient as partial rows, include/maestro_hip_ends.h).  GC_ROWS rows per wave: a lane owns the same columns in every row, the
+// wave's loads of all its rows go out before the first is used, the four waves meet in LDS once.
+constexpr int GC_ROWS = 8;
+template <int NV>
+__global__ __launch_bounds__(256) void gather_rows_bf16_cs_kernel(const float* __restrict__ src, const int* __restrict__ idx,
+                                                                  bf16_t* __restrict__ dst, float* __restrict__ cs_partial, int B,
+                                                                  int src_L, int n_idx, int dim) {
+    __shared__ f32x4 red[4][64 * NV];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long rows = (long)B * n_idx, row0 = ((long)blockIdx.x * 4 + w) * GC_ROWS;
+    f32x4 v[GC_ROWS][NV], cs[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) cs[j] = (f32x4){0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < GC_ROWS; ++r) {
+        // (every load is issued, none sits behind a branch: a row past the end re-reads the last row, a lane past the last
+        //  column re-reads column 0; neither is stored or summed)
+        const long row = min(row0 + r, rows - 1);
+        const float* s = src + ((size_t)(row / n_idx) * src_L + idx[row]) * dim;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = lane * 4 + 256 * j;
+            v[r][j] = *reinterpret_cast<const f32x4*>(s + (c < dim ? c : 0));
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < GC_ROWS; ++r) {
+        const long row = row0 + r;
+        if (row >= rows) break;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = lane * 4 + 256 * j;
+            if (c < dim) {
+                const u32x2 pk = {pack_bf2(v[r][j][0], v[r][j][1]), pack_bf2(v[r][j][2], v[r][j][3])};
+                *reinterpret_cast<u32x2*>(dst + (size_t)row * dim + c) = pk;
+                cs[j] += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
+                                 __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) red[w][lane + 64 * j] = cs[j];
+    __syncthreads();
+    const float* cr = reinterpret_cast<const float*>(red);
+    for (int c = threadIdx.x; c < dim; c += 256)
+        cs_partial[(size_t)blockIdx.x * dim + c] = (cr[c] + cr[256 * NV + c]) + (cr[512 * NV + c] + cr[768 * NV + c]);
 }
 
 // dsrc[b, idx[b, j], :] = ddst[b, dst_off + j, :]  (dsrc pre-zeroed; indices are unique per sample)
@@ -221,6 +271,27 @@ extern "C" int mh_gather_rows(const float* src, const int* idx, float* dst, int 
     MH_CHECK_ARG(src && idx && dst && dim % 4 == 0 && dst_off + n_idx <= dst_L, "mh_gather_rows: bad arguments");
     hipLaunchKernelGGL(gather_rows_kernel, dim3(ceil_div((long)B * n_idx, 4)), dim3(256), 0, (hipStream_t)stream, src, idx, dst, B,
                        src_L, n_idx, dim, dst_L, dst_off);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_gather_rows_cs_rows(long rows) { return rows > 0 ? (int)ceil_div(rows, (long)(4 * GC_ROWS)) : 0; }
+
+extern "C" int mh_gather_rows_bf16_cs(const float* src, const int* idx, void* dst16, float* cs_partial, int B, int src_L, int n_idx,
+                                      int dim, void* stream) {
+    MH_CHECK_ARG(src && idx && dst16 && cs_partial, "mh_gather_rows_bf16_cs: null pointer");
+    MH_CHECK_ARG(B > 0 && src_L > 0 && n_idx > 0 && n_idx <= src_L && dim > 0 && dim % 4 == 0 && dim <= 1024,
+                 "mh_gather_rows_bf16_cs: bad sizes B=%d src_L=%d n_idx=%d dim=%d (dim %% 4 == 0, dim <= 1024)", B, src_L, n_idx, dim);
+    const dim3 grid(mh_gather_rows_cs_rows((long)B * n_idx)), block(256);
+#define MH_GC_LAUNCH(NV) hipLaunchKernelGGL((gather_rows_bf16_cs_kernel<NV>), grid, block, 0, (hipStream_t)stream, src, idx, \
+                                            (bf16_t*)dst16, cs_partial, B, src_L, n_idx, dim)
+    switch ((dim + 255) / 256) {
+        case 1: MH_GC_LAUNCH(1); break;
+        case 2: MH_GC_LAUNCH(2); break;
+        case 3: MH_GC_LAUNCH(3); break;
+        default: MH_GC_LAUNCH(4); break;
+    }
+#undef MH_GC_LAUNCH
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -4,6 +4,7 @@
 // sequences" (reference mim.py:408-423) is done by addressing instead of copies:
 //     row(b, j) = b * L + off + j,  j < n.
 #include "gemm_common.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -435,6 +436,104 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const bf16_t* __restri
         prow[c] = red[c] + red[3 * dim + c] + red[6 * dim + c] + red[9 * dim + c];
 }
 
+// The same straight-line sequence for the final LayerNorms of the step (decoder per modality, joint / encoder per group): no
+// residual gradient to add, dy bf16 or fp32 (DY_F32: one 16-byte load per chunk, nothing to unpack).  Both are compile-time forms,
+// so nothing is decided inside the pipeline.  A kernel of its own and not a shared inlined body: routed through a common
+// __device__ function the blocks' form above grew from 177 to 200 registers at dim 768 and from 238 to 262 at dim 1024.
+template <int NV, int DEPTH, bool DY_F32>
+__global__ __launch_bounds__(256) void ln_bwd_final_kernel(const void* __restrict__ dy, RowMap dym, const float* __restrict__ x,
+                                                          RowMap xm, const float* __restrict__ gamma,
+                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          float* __restrict__ dx,
+                                                          bf16_t* __restrict__ dx_bf16, float* __restrict__ partial, int B, int n) {
+    constexpr int dim = 256 * NV;
+    static_assert(DEPTH >= 1 && DEPTH <= ROWS_PER_WAVE, "prefetch distance in rows");
+    extern __shared__ __attribute__((aligned(16))) float red[];  // [4 waves][3][dim]
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    f32x4 gsum[NV], bsum[NV], csum[NV], gm[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        gsum[i] = (f32x4){0, 0, 0, 0}; bsum[i] = (f32x4){0, 0, 0, 0}; csum[i] = (f32x4){0, 0, 0, 0};
+        gm[i] = *reinterpret_cast<const f32x4*>(gamma + 4 * (lane + 64 * i));
+    }
+    const int row0 = (blockIdx.x * 4 + w) * ROWS_PER_WAVE;
+    if (row0 < B * n) {
+        f32x4 xq[ROWS_PER_WAVE][NV];
+        std::conditional_t<DY_F32, f32x4, u32x2> dq[ROWS_PER_WAVE][NV];
+        float muq[ROWS_PER_WAVE], rsq[ROWS_PER_WAVE];
+        size_t xrowq[ROWS_PER_WAVE];
+        auto fetch = [&](int p) {
+            const int row = row0 + p, b = row / n, j = row - b * n;
+            xrowq[p] = map_row(xm, b, j) * dim;
+            const size_t dyrow = map_row(dym, b, j) * dim;
+            muq[p] = mean[row]; rsq[p] = rstd[row];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int c4 = 4 * (lane + 64 * i);
+                xq[p][i] = *reinterpret_cast<const f32x4*>(x + xrowq[p] + c4);
+                if constexpr (DY_F32) dq[p][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(dy) + dyrow + c4);
+                else dq[p][i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(dy) + dyrow + c4);
+            }
+        };
+#pragma unroll
+        for (int p = 0; p < DEPTH; ++p) fetch(p);
+#pragma unroll
+        for (int rr = 0; rr < ROWS_PER_WAVE; ++rr) {
+            if (rr + DEPTH < ROWS_PER_WAVE) fetch(rr + DEPTH);
+            __builtin_amdgcn_sched_barrier(0);
+            const float mu = muq[rr], rs = rsq[rr];
+            f32x4 xh[NV], dz[NV];
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                f32x4 d;
+                if constexpr (DY_F32) {
+                    d = dq[rr][i];
+                } else {
+                    const u32x2 pk = dq[rr][i];
+                    d = (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
+                                __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    xh[i][e] = (xq[rr][i][e] - mu) * rs;
+                    dz[i][e] = d[e] * gm[i][e];
+                    s1 += dz[i][e];
+                    s2 += dz[i][e] * xh[i][e];
+                    gsum[i][e] += d[e] * xh[i][e];
+                    bsum[i][e] += d[e];
+                }
+            }
+            const float c1 = ln_wave_sum(s1) / dim, c2 = ln_wave_sum(s2) / dim;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int c4 = 4 * (lane + 64 * i);
+                f32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = rs * (dz[i][e] - c1 - xh[i][e] * c2);
+                csum[i] += o;
+                *reinterpret_cast<f32x4*>(dx + xrowq[rr] + c4) = o;
+                const u32x2 pk = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
+                *reinterpret_cast<u32x2*>(dx_bf16 + xrowq[rr] + c4) = pk;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (!partial) return;
+    float* rg = red + (size_t)w * 3 * dim;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c4 = 4 * (lane + 64 * i);
+        *reinterpret_cast<f32x4*>(rg + c4) = gsum[i];
+        *reinterpret_cast<f32x4*>(rg + dim + c4) = bsum[i];
+        *reinterpret_cast<f32x4*>(rg + 2 * dim + c4) = csum[i];
+    }
+    __syncthreads();
+    float* prow = partial + (size_t)blockIdx.x * 3 * dim;
+    for (int c = threadIdx.x; c < 3 * dim; c += 256)
+        prow[c] = red[c] + red[3 * dim + c] + red[6 * dim + c] + red[9 * dim + c];
+}
+
 #ifndef LN_BWD_DEPTH
 #define LN_BWD_DEPTH 4    // rows of operands in flight per wave before the first is reduced (dim <= 768)
 #endif
@@ -561,8 +660,19 @@ static int layernorm_bwd_impl(const void* dy, int dy_L, int dy_off, int dy_is_f3
 #define LN_BWD_FAST(NV, DEPTH) hipLaunchKernelGGL((ln_bwd_fast_kernel<NV, DEPTH>), grid, block, lds, s, (const bf16_t*)dy, \
                                                   RowMap{dy_L, dy_off}, x, RowMap{x_L, x_off}, gamma, mean, rstd, dres, dx, \
                                                   (bf16_t*)dx_bf16, part, B, n)
+#define LN_BWD_FINAL(NV, DEPTH) do { \
+        if (dy_is_f32) hipLaunchKernelGGL((ln_bwd_final_kernel<NV, DEPTH, true>), grid, block, lds, s, dy, RowMap{dy_L, dy_off}, x, \
+                                          RowMap{x_L, x_off}, gamma, mean, rstd, dx, (bf16_t*)dx_bf16, part, B, n); \
+        else hipLaunchKernelGGL((ln_bwd_final_kernel<NV, DEPTH, false>), grid, block, lds, s, dy, RowMap{dy_L, dy_off}, x, \
+                                RowMap{x_L, x_off}, gamma, mean, rstd, dx, (bf16_t*)dx_bf16, part, B, n); } while (0)
     const int nvs = ln_nv(dim);
-    if (MH_LN_FAST && nvs <= 4 && dim == 256 * nvs && !dy_is_f32 && dres && dx_bf16 && rows % ROWS_PER_WAVE == 0) {
+    const bool fast = MH_LN_FAST && nvs <= 4 && dim == 256 * nvs && dx_bf16 && rows % ROWS_PER_WAVE == 0;
+    if (fast && !dres) {
+        // the final LayerNorms: no residual gradient, dy bf16 or fp32
+        constexpr int DEPTH = LN_BWD_DEPTH < ROWS_PER_WAVE ? LN_BWD_DEPTH : ROWS_PER_WAVE, DEPTH4 = 2 < ROWS_PER_WAVE ? 2 : ROWS_PER_WAVE;
+        switch (nvs) { case 1: LN_BWD_FINAL(1, DEPTH); break; case 2: LN_BWD_FINAL(2, DEPTH); break;
+                       case 3: LN_BWD_FINAL(3, DEPTH); break; default: LN_BWD_FINAL(4, DEPTH4); }
+    } else if (fast && !dy_is_f32) {
         // the transformer blocks' own case: straight-line kernel, all of a wave's rows in flight (two at dim 1024: registers)
         constexpr int DEPTH = LN_BWD_DEPTH < ROWS_PER_WAVE ? LN_BWD_DEPTH : ROWS_PER_WAVE, DEPTH4 = 2 < ROWS_PER_WAVE ? 2 : ROWS_PER_WAVE;
         switch (nvs) { case 1: LN_BWD_FAST(1, DEPTH); break; case 2: LN_BWD_FAST(2, DEPTH); break;
@@ -572,6 +682,7 @@ static int layernorm_bwd_impl(const void* dy, int dy_L, int dy_off, int dy_is_f3
                        case 4: LN_BWD(4); break; default: LN_BWD(8); }
     }
 #undef LN_BWD_FAST
+#undef LN_BWD_FINAL
 #undef LN_BWD
     if (dgamma && !partial_only)
         hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(ceil_div(3 * dim, 256), ceil_div(nblk, RED_ROWS)), dim3(256), 0, s,

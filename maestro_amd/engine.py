@@ -458,20 +458,53 @@ class PatchEmbedEnd:
         hip.embed_finish(b["yconv"], b["gn_stats"], pe.norm.weight, pe.norm.bias, b["pos_enc"], gbuf["dates"], gbuf["n_dates"],
                          s.date_off, xg, s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
 
-    def backward(self, dxg: torch.Tensor, Lgroup: int, clear_dw: bool) -> None:  # noqa: N803
+    def backward(self, dxg: torch.Tensor, Lgroup: int, clear_dw: bool, defer_wgrad: bool = False) -> None:  # noqa: N803
         """``dxg`` [Beff, Lgroup, E]: gradient of the group sequence.  ``clear_dw``: the conv-gradient staging buffer (split-K
-        atomics accumulate into it) was not cleared since the last backward."""
+        atomics accumulate into it) was not cleared since the last backward.  ``defer_wgrad``: the conv weight gradient is
+        ``wgrad_problem()`` of the caller's grouped launch, with ``unpack_rows_add`` behind it."""
         eng, s, b = self.eng, self.s, self.buf
         ps, E, pe, T = eng.store, eng.E, b["pe"], s.Beff * s.n_tok  # noqa: N806
         if getattr(eng, "deterministic", False):
             return self._backward_det(dxg, Lgroup)
         hip.embed_finish_bwd(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight), ps.g(pe.norm.bias),
                              b["gn_sums"], s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
+        if not defer_wgrad:
+            self._wgrad_in_line(clear_dw)
+        hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+
+    def _wgrad_in_line(self, clear_dw: bool) -> None:
+        """The conv weight gradient as a launch of its own: split-K atomics into the (cleared) padded staging buffer."""
+        eng, s, b = self.eng, self.s, self.buf
+        E, T = eng.E, s.Beff * s.n_tok  # noqa: N806
         if clear_dw:
             b["dw_conv"].zero_()
         hip.gemm(hip.GEMM_TN, E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, b["dw_conv"], s.Kpad, hip.OUT_F32 | hip.ATOMIC)
-        hip.unpack_rows_add(b["dw_conv"], ps.g(pe.conv.weight), E, s.K, s.Kpad)
-        hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+        hip.unpack_rows_add(b["dw_conv"], eng.store.g(b["pe"].conv.weight), E, s.K, s.Kpad)
+
+    def wgrad_problem(self) -> tuple:
+        """The conv weight gradient dW[E, Kpad] = dyc[T, E]^T cols[T, Kpad] into the padded staging buffer as a ``hip.GroupedTN``
+        entry (a plain store: the buffer then needs no clearing); ``unpack_rows_add`` follows the grouped launch."""
+        b, s, E = self.buf, self.s, self.eng.E  # noqa: N806
+        return (b["dyc"], b["cols"], b["dw_conv"], E, s.Kpad, s.Beff * s.n_tok, E, s.Kpad, s.Kpad)
+
+    def cs_buffer(self) -> torch.Tensor:
+        """Partial rows of colsum(dyc) -- the conv bias gradient -- written by ``backward_ends``."""
+        b, s = self.buf, self.s
+        if b.get("dyc_cs") is None:
+            b["dyc_cs"] = torch.empty(hip.embed_bwd_cs_rows(s.Beff * s.n_tok), self.eng.E, dtype=F32, device=self.eng.device)
+        return b["dyc_cs"]
+
+    def backward_ends(self, dx: torch.Tensor, inv, n_vis: int, Lgroup: int, defer_wgrad: bool, clear_dw: bool) -> None:  # noqa: N803
+        """The backward with its side reductions left to the segment's batched launches: ``dx`` is the gradient of the visible
+        rows [Beff, n_vis, E] read through the position map ``inv`` [Beff, Lgroup] (``inv`` None: the dense group-sequence
+        gradient), the conv bias gradient leaves as partial rows (``cs_buffer``), and with ``defer_wgrad`` the conv weight
+        gradient is ``wgrad_problem()`` of the caller's grouped launch (the caller also issues ``unpack_rows_add`` behind it)."""
+        eng, s, b = self.eng, self.s, self.buf
+        ps, E, pe = eng.store, eng.E, b["pe"]  # noqa: N806
+        hip.embed_finish_bwd_ends(dx, inv, n_vis, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight),
+                                  ps.g(pe.norm.bias), b["gn_sums"], self.cs_buffer(), s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
+        if not defer_wgrad:
+            self._wgrad_in_line(clear_dw)
 
     def _backward_det(self, dxg: torch.Tensor, Lgroup: int) -> None:  # noqa: N803
         """Deterministic mode: every reduction leaves partial rows in buffers private to this end; the engine's ordered reduce
@@ -598,7 +631,7 @@ class EngineBase:
         prio = int(os.environ.get("MAESTRO_SIDE_PRIORITY", "0"))
         self.side_streams = [torch.cuda.Stream(device=device, priority=prio) for _ in range(max(0, n_side_streams))]
         self._wgrad_stream = torch.cuda.Stream(device=device)   # plan "ovl": deferred weight gradients under the next segment
-        self._wgrad_tables = {}     # (stack tag, lo, hi) per item -> (GroupedTN, ColsumBatch), see _launch_wgrads
+        self._wgrad_tables = {}     # ((stack tag, lo, hi) per item, ends tags) -> (GroupedTN, ColsumBatch, ...), see _launch_wgrads
         # a zero_grad since the last backward has cleared the patch-embed conv-gradient staging buffers (``mb[..]["dw_conv"]``);
         # otherwise the backward's launch list clears them itself
         self._dw_conv_clear = False
@@ -752,20 +785,34 @@ class EngineBase:
         if self.warm_passes > 0:
             self._warm_up(one_pass)
 
-    def _launch_wgrads(self, items) -> None:
+    def _launch_wgrads(self, items, ends=()) -> None:
         """One grouped launch for the deferred weight gradients of ``items`` = [(stack, lo, hi)]; the descriptor table is
-        built on first use (always an eager run: segments are captured on their second run)."""
+        built on first use (always an eager run: segments are captured on their second run).  ``ends``: tags of the step ends
+        whose weight gradients and partial rows join the same two launches (``MAEEngine._ends_table``)."""
         items = [(st, lo, hi) for st, lo, hi in items if hi > lo]
-        if not items:
+        if not items and not ends:
             return
-        key = tuple((st.tag, lo, hi) for st, lo, hi in items)
+        key = (tuple((st.tag, lo, hi) for st, lo, hi in items), tuple(ends))
         table = self._wgrad_tables.get(key)
         if table is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise hip.HipExtensionError(f"weight-gradient table {key} first needed inside a hipGraph capture")
             probs = [p for st, lo, hi in items for p in st.wgrad_problems(lo, hi)]
             jobs = [j for st, lo, hi in items for j in st.reduce_jobs(lo, hi)]
-            table = self._wgrad_tables[key] = (hip.GroupedTN(probs, self.device), hip.ColsumBatch(jobs, self.device))
-        table[1].launch()   # LayerNorm / bias parameter gradients of the same layers: one batched column-sum launch
-        table[0].launch()
+            after, ready = [], []
+            for tag in ends:
+                e_probs, e_jobs, e_after, e_ready = self._ends_table(tag)
+                probs, jobs, after, ready = probs + e_probs, jobs + e_jobs, after + e_after, ready + e_ready
+            table = self._wgrad_tables[key] = (hip.GroupedTN(probs, self.device) if probs else None,
+                                               hip.ColsumBatch(jobs, self.device) if jobs else None, after, ready)
+        if table[1] is not None:
+            table[1].launch()   # LayerNorm / bias parameter gradients of the same layers: one batched column-sum launch
+        if table[0] is not None:
+            table[0].launch()
+        for fn in table[2]:     # what has to follow the grouped launch (the patch-embed conv gradients leave their padded buffers)
+            fn()
+        for module in table[3]:  # the ends' parameters are final only now
+            self._grads_ready(module)
 
     @contextlib.contextmanager
     def _tuning_pass(self, what: str):
@@ -892,6 +939,16 @@ class MAEEngine(EngineBase):
         if self.wgrad_mode not in ("auto", "fused", "deferred"):
             raise ValueError(f"MAESTRO_WGRAD={self.wgrad_mode!r}: expected auto, fused or deferred")
         self._wgrad_plans, self._zero_lists = {}, {}
+        # The ends of the backward (pixelify head, final LayerNorms, enc_to_dec, patch embed) under a deferred plan, default path:
+        # "a" = their weight gradients join the segment's grouped launch, "b" = their bias / LayerNorm side reductions leave as
+        # partial rows for the segment's batched column sum, "c" = the patch-embed backward reads the encoder gradient through
+        # the position map (no expanded group-sequence gradient; needs "b": the same kernels).  MAESTRO_ENDS (A/B aid, default
+        # "abc") selects a subset; not in deterministic mode (its own launch list), not with fp8, not under the "fused" plan.
+        self.ends_parts = frozenset(os.environ.get("MAESTRO_ENDS", "abc")) if not self.deterministic and dtype != "fp8" else frozenset()
+        if not self.ends_parts <= frozenset("abc") or ("c" in self.ends_parts and "b" not in self.ends_parts):
+            raise ValueError(f"MAESTRO_ENDS={os.environ.get('MAESTRO_ENDS')!r}: a subset of 'abc' expected, 'c' only with 'b'")
+        self._loss_cs = False       # the last forward's loss launches left the pixelify bias gradients as partial rows
+        self._ends_ws = {}          # site key -> private partial-row workspace (see _ends_buf)
         # deterministic mode: per phase ("fwd", "bwd") the former atomic sites in the order of their first launch -- key ->
         # (private buffers, ordered-reduce jobs) -- and the tables built from them (see _det_site)
         self._det_sites, self._det_tables = {"fwd": {}, "bwd": {}}, {}
@@ -1048,6 +1105,8 @@ class MAEEngine(EngineBase):
             self.mb[name].update(
                 target=first["target"] if first else e(T, s.C_src * s.P * s.P), hdec=e(T, Dd, dt=BF16), mean_f=e(T), rstd_f=e(T),
                 rec=e(T, s.K), drec=e(T, s.K, dt=BF16), dh=e(T, Dd, dt=BF16), cnt=first["cnt"] if first else z(1, dt=I32))
+            if "b" in self.ends_parts and s.K <= 1024:   # partial rows of colsum(drec), written by the loss launch itself
+                self.mb[name]["drec_cs"] = e(hip.masked_loss_cs_rows(s.Beff, s.n_tok), s.K)
         self.gb = {}
         self.enc, self.dec = {}, {}
         for g in self.groups:
@@ -1057,12 +1116,13 @@ class MAEEngine(EngineBase):
             date_row = torch.cat([(s.date_off + torch.arange(s.n_tok) // s.L).to(I32) for s in g.mods])
             pos_dec = torch.cat([m.pos_dec_rows[s.name].repeat(s.D, 1) for s in g.mods], dim=0)
             self.gb[g.name] = dict(
-                xg=e(Bn, L, E), dxg=z(Bn, L, E),       # (noise / struct + their pinned ring slots: views, see _alloc_mask_upload)
+                xg=e(Bn, L, E),                        # (noise / struct + their pinned ring slots: views, see _alloc_mask_upload)
                 vis=e(Bn, N, dt=I32), msk=e(Bn, g.k, dt=I32), inv=e(Bn, L, dt=I32), mask=e(Bn, L, dt=U8),
                 dates=z(Bn, n_dates, 8), n_dates=n_dates, tok_slot=tok_slot.to(dev), date_row=date_row.to(dev),
                 pos_dec=pos_dec.to(dev).contiguous(), tok_table=e(len(g.mods), Dd),
                 henc=e(Bn * N, E, dt=BF16), mean_e=e(Bn * N), rstd_e=e(Bn * N), y_e2d=e(Bn * N, Dd),
                 dy_e2d=e(Bn * N, Dd), dy_e2d16=e(Bn * N, Dd, dt=BF16), dhenc=e(Bn * N, E, dt=BF16),
+                e2d_cs=e(hip.gather_rows_cs_rows(Bn * N), Dd) if "b" in self.ends_parts and Dd <= 1024 else None,
                 mean_j=e(Bn * N), rstd_j=e(Bn * N))
             holder = m.encoder[g.model]
             self.enc[g.name] = Stack(self, holder, Bn, N, f"enc.{g.name}")
@@ -1231,7 +1291,11 @@ class MAEEngine(EngineBase):
         self._h2d_done[slot] = ev
         batch = self._stage_inputs(batch)
         with self._tuning_pass("forward"):
-            self._segment("forward" if self._opt is None else "forward:opt", self._cur_key, lambda: self._forward_launches(batch))
+            # the loss launch writes the pixelify bias gradient's partial rows only where the backward will sum them (not under
+            # the "fused" plan: its launch list is the previous one); the form is part of the forward graph's key
+            self._loss_cs = "b" in self.ends_parts and self._wgrad_plan() != "fused"
+            self._segment("forward" if self._opt is None else "forward:opt", (self._cur_key, self._loss_cs),
+                          lambda: self._forward_launches(batch))
         if self._opt is not None:
             self.store.mark_synced()   # the optimizer stages inside the forward refreshed the bf16 shadows themselves
         return self.loss_acc
@@ -1420,6 +1484,14 @@ class MAEEngine(EngineBase):
                     else:
                         hip.masked_loss_bands_det(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], part,
                                                   b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss, s.C_src, s.c0, s.C)
+                elif self._loss_cs and b.get("drec_cs") is not None:   # the same launch also leaves the pixelify bias gradient as partial rows
+                    if s.G == 1:
+                        hip.masked_loss_cs(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
+                                           b["drec"], b["drec_cs"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
+                    else:
+                        hip.masked_loss_bands_cs(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
+                                                 b["drec"], b["drec_cs"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss,
+                                                 s.C_src, s.c0, s.C)
                 elif s.G == 1:
                     hip.masked_loss(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
                                     b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
@@ -1480,8 +1552,9 @@ class MAEEngine(EngineBase):
             # the patch-embed weight-gradient staging buffers ([E, Kpad] fp32 per modality: split-K atomics accumulate into them) are
             # cleared by the same launch -- offsets relative to the gradient buffer's base (one flat device address space) -- instead
             # of one torch fill each inside the backward
-            for b in self.mb.values():
-                if b.get("dw_conv") is not None:
+            # (a buffer that the grouped launch STORES -- _ends_deferred -- needs no clearing)
+            for name, b in self.mb.items():
+                if b.get("dw_conv") is not None and not self._ends_deferred(self.embed[name].wgrad_problem(), plan):
                     spans.append(((b["dw_conv"].data_ptr() - base) // 4, b["dw_conv"].numel()))
             dev = torch.tensor([v for sp in spans for v in sp], dtype=torch.int64, device=self.device)
             z = self._zero_lists[plan] = (dev, len(spans), max(n for _, n in spans))
@@ -1529,7 +1602,8 @@ class MAEEngine(EngineBase):
         return list(self.dec.values()) + ([self.joint] if self.joint is not None else []) + list(self.enc.values())
 
     def _with_overlapped_wgrads(self, fn, previous, own):
-        """Plan "ovl": the weight gradients of the PREVIOUS segment run on a side stream under this segment's dgrad chain (their
+        """``previous`` / ``own``: (items, ends) of ``_launch_wgrads``.
+        Plan "ovl": the weight gradients of the PREVIOUS segment run on a side stream under this segment's dgrad chain (their
         operands -- the per-layer dY / activation buffers -- are final, nothing here writes them); the last segment also issues
         its own at its end.  The grouped TN launch is one workgroup per 256 x 256 tile with a 128 KiB ring, the dgrad chain two
         64 KiB workgroups per CU: a CU runs one or the other, so the side stream fills the CUs that the chain's small launches
@@ -1540,15 +1614,15 @@ class MAEEngine(EngineBase):
                 side = self._wgrad_stream
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    self._launch_wgrads(previous)
+                    self._launch_wgrads(*previous)
                 fn()
                 main.wait_stream(side)
             else:
                 if previous:
-                    self._launch_wgrads(previous)
+                    self._launch_wgrads(*previous)
                 fn()
             if own:
-                self._launch_wgrads(own)
+                self._launch_wgrads(*own)
         return run
 
     def _enc_cuts(self) -> list:
@@ -1586,27 +1660,150 @@ class MAEEngine(EngineBase):
             sfx += ":nz"     # no zero_grad since the last backward: this launch list clears the conv-gradient staging buffers itself
         if self.fp8 is not None and self.fp8.dgrad:
             sfx += ":f8" if self.fp8.grad_ready else ":cal"       # (the first backward calibrates the gradient scales in bf16)
+        if self._ends("b") and not self._loss_cs:
+            sfx += ":nolcs"
         cuts = self._enc_cuts()
-        # (name, launches, deferred weight gradients of the segment)
-        segs = [("bwd_dec", self._bwd_decoder_side, [(st, 0, st.depth) for st in self.dec.values()])]
+        # (name, launches, deferred weight gradients of the segment, ends whose reductions the segment produces)
+        segs = [("bwd_dec", self._bwd_decoder_side, [(st, 0, st.depth) for st in self.dec.values()], self._ends_tags("dec"))]
         if self.joint is not None:
-            segs.append(("bwd_joint", self._bwd_joint, [(self.joint, 0, self.joint.depth)]))
+            segs.append(("bwd_joint", self._bwd_joint, [(self.joint, 0, self.joint.depth)], ()))
         for i in range(len(cuts) - 1):
-            segs.append((f"bwd_enc{i}", lambda hi=cuts[i], lo=cuts[i + 1], first=(i == 0), last=(i == len(cuts) - 2):
+            first, last = i == 0, i == len(cuts) - 2
+            segs.append((f"bwd_enc{i}", lambda hi=cuts[i], lo=cuts[i + 1], first=first, last=last:
                          self._bwd_encoder_side(hi, lo, first, last),
-                         [(st, min(cuts[i + 1], st.depth), min(cuts[i], st.depth)) for st in self.enc.values()]))
+                         [(st, min(cuts[i + 1], st.depth), min(cuts[i], st.depth)) for st in self.enc.values()],
+                         self._ends_tags(*(["enc_first"] if first else []), *(["enc_last"] if last else []))))
         with self._tuning_pass("backward"):
-            for i, (name, fn, items) in enumerate(segs):
+            for i, (name, fn, items, ends) in enumerate(segs):
                 if plan == "ovl":
-                    fn = self._with_overlapped_wgrads(fn, segs[i - 1][2] if i else None, items if i == len(segs) - 1 else None)
+                    fn = self._with_overlapped_wgrads(fn, segs[i - 1][2:] if i else None, (items, ends) if i == len(segs) - 1 else None)
                 self._segment(name + sfx, key, fn)
         self._dw_conv_clear = False
         if self.fp8 is not None:
             self.fp8.end_of_backward()      # next step's e5m2 gradient scales from this backward's absmax values
 
+    # ------------------------------------------------------------------------------------------ the ends of the backward
+    def _ends(self, part: str, plan: str | None = None) -> bool:
+        """Whether part "a" / "b" / "c" of the ends' launch structure (see ``ends_parts``) is in force under ``plan``."""
+        return part in self.ends_parts and (self._plan if plan is None else plan) in ("all", "enc", "ovl")
+
+    def _ends_tags(self, *tags) -> tuple:
+        """The ends tags of a segment, or none under the "fused" plan.  "dec:nolcs": the forward ran before the plan became a
+        deferred one (a gradient hook or ``wgrad_mode`` set between forward and backward) and left no partial rows of the
+        pixelify bias gradient: that backward takes the column sums of ``drec`` itself, with tables and graphs of its own."""
+        if not self.ends_parts or self._plan == "fused":
+            return ()
+        stale = self._ends("b") and not self._loss_cs
+        return tuple("dec:nolcs" if t == "dec" and stale else t for t in tags)
+
+    def _ends_deferred(self, prob, plan: str | None = None) -> bool:
+        """Part "a": this weight gradient of an end joins the segment's grouped launch.  A problem the grouped kernel cannot
+        address (``GroupedTN.check``: in practice an operand beyond its 2 GiB descriptor range, the M, N % 8 rule being the split-K
+        launch's own as well) keeps its split-K launch."""
+        if not self._ends("a", plan):
+            return False
+        try:
+            hip.GroupedTN.check(0, prob)
+            return True
+        except hip.HipExtensionError:
+            return False
+
+    def _embed_cs(self) -> bool:
+        """The patch-embed backward runs in its ends form (``PatchEmbedEnd.backward_ends``: conv bias gradient as partial rows,
+        optionally through the position map); its kernels keep a row's columns in registers, hence the width limit."""
+        return self._ends("b") and self.E <= 1024
+
+    def _ends_buf(self, key, *shape) -> torch.Tensor:
+        """Private fp32 partial-row workspace of one site of the ends, allocated on the site's first launch (an eager run)."""
+        buf = self._ends_ws.get(key)
+        if buf is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise hip.HipExtensionError(f"ends workspace {key} first needed inside a hipGraph capture")
+            buf = self._ends_ws[key] = torch.empty(*shape, dtype=F32, device=self.device)
+        return buf
+
+    def _final_layernorm_bwd(self, key, gbuf, dy, dy_L, dy_off, x, x_L, x_off, norm, mean, rstd, dx, dx16, bias_grad, B, n, dim) -> None:  # noqa: N803
+        """Backward of a final LayerNorm (no residual gradient).  Part "b": partial rows (dgamma | dbeta | colsum dx) into the
+        site's own workspace, summed by the segment's batched column sum (``_ends_ln_jobs``); else the two-launch form with
+        the group's shared workspace."""
+        if self._ends("b"):
+            ws = self._ends_buf(key, hip.layernorm_bwd_workspace(B * n, dim))
+            hip.layernorm_bwd_partial(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, ws, B, n, dim)
+        else:
+            g = self.store.g
+            hip.layernorm_bwd(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, g(norm.weight), g(norm.bias),
+                              bias_grad, gbuf["ln_ws"], B, n, dim)
+
+    def _ends_ln_jobs(self, key, norm, bias_grad, dim) -> list:
+        ws, g = self._ends_ws[key], self.store.g
+        rows = ws.numel() // (3 * dim)
+        jobs = [(ws, g(norm.weight), rows, dim, 3 * dim), (ws[dim:], g(norm.bias), rows, dim, 3 * dim)]
+        if bias_grad is not None:
+            jobs.append((ws[2 * dim:], bias_grad, rows, dim, 3 * dim))
+        return jobs
+
+    def _rec_wgrad(self, s) -> tuple:
+        """Pixelify conv weight gradient dW[K, Dd] = drec[T, K]^T hdec[T, Dd] of one modality spec as a ``hip.GroupedTN`` entry."""
+        b, Dd = self.mb[s.name], self.Dd  # noqa: N806
+        conv = self.model.embed_to_rec[s.embed].pixelify_bands[s.gi].conv
+        return (b["drec"], b["hdec"], self.store.g(conv.weight).view(s.K, Dd), s.K, Dd, s.Beff * s.n_tok, s.K, Dd, Dd)
+
+    def _e2d_wgrad(self, g) -> tuple:
+        gbuf, lin = self.gb[g.name], self.model.enc_to_dec[g.model]
+        return (gbuf["dy_e2d16"], gbuf["henc"], self.store.g(lin.weight), self.Dd, self.E, g.Beff * g.N, self.Dd, self.E, self.E)
+
+    def _ends_table(self, tag: str):
+        """What the ends produced by one backward segment add to its two batched launches: ``(grouped problems, column-sum
+        jobs, launches that must follow the grouped one, modules whose gradients are final after it)``.  Built with the
+        segment's table, i.e. after the segment's first (eager) run has allocated the sites' workspaces."""
+        m, ps, E, Dd = self.model, self.store, self.E, self.Dd  # noqa: N806
+        probs, jobs, after, ready = [], [], [], []
+        if tag in ("dec", "dec:nolcs"):
+            for g in self.groups:
+                gbuf, st = self.gb[g.name], self.dec[g.name]
+                for s in g.mods:
+                    b = self.mb[s.name]
+                    conv = m.embed_to_rec[s.embed].pixelify_bands[s.gi].conv
+                    if self._ends_deferred(self._rec_wgrad(s)):
+                        probs.append(self._rec_wgrad(s))
+                    if self._ends("b"):
+                        if tag == "dec" and b.get("drec_cs") is not None:
+                            jobs.append((b["drec_cs"].view(-1), ps.g(conv.bias), b["drec_cs"].shape[0], s.K, s.K))
+                        jobs += self._ends_ln_jobs(("ln_dec", s.name), st.t.norm, st.top_bias_grad(), Dd)
+                    ready.append(m.embed_to_rec[s.embed])
+                ready.append(st.t.norm)
+                if not self.e2d_identity:
+                    if self._ends_deferred(self._e2d_wgrad(g)):
+                        probs.append(self._e2d_wgrad(g))
+                    if self._ends("b") and gbuf["e2d_cs"] is not None:
+                        jobs.append((gbuf["e2d_cs"].view(-1), ps.g(m.enc_to_dec[g.model].bias), gbuf["e2d_cs"].shape[0], Dd, Dd))
+                    ready.append(m.enc_to_dec[g.model])
+                if self.joint is not None and self._ends("b"):
+                    jobs += self._ends_ln_jobs(("ln_joint", g.name), self.joint.t.norm, self.joint.top_bias_grad(), E)
+        elif tag == "enc_first":
+            for g in self.groups:
+                st = self.enc[g.name]
+                if self._ends("b"):
+                    jobs += self._ends_ln_jobs(("ln_enc", g.name), st.t.norm, st.top_bias_grad(), E)
+                ready.append(st.t.norm)
+        elif tag == "enc_last":
+            for g in self.groups:
+                for s in g.mods:
+                    end, b = self.embed[s.name], self.mb[s.name]
+                    if self._ends_deferred(end.wgrad_problem()):
+                        probs.append(end.wgrad_problem())
+                        after.append(lambda b=b, s=s: hip.unpack_rows_add(b["dw_conv"], ps.g(b["pe"].conv.weight), E, s.K, s.Kpad))
+                    if self._embed_cs():
+                        jobs.append((end.cs_buffer().view(-1), ps.g(b["pe"].conv.bias), end.cs_buffer().shape[0], E, E))
+        else:
+            raise ValueError(tag)
+        return probs, jobs, after, ready
+
     def _bwd_decoder_side(self) -> None:
         m, E, Dd, ps = self.model, self.E, self.Dd, self.store  # noqa: N806
         AT = hip.OUT_F32 | hip.ATOMIC  # noqa: N806
+        ends = self._ends_tags("dec")       # set: the ends' modules are reported ready behind the launch that finishes them
+        loss_cs = ends == ("dec",) and self._ends("b")      # the forward's loss launches left the pixelify bias partial rows
 
         def side(g):
             def run():
@@ -1625,20 +1822,28 @@ class MAEEngine(EngineBase):
                                                 b["rstd_f"], dx, dx16, st.top_bias_grad(), s.Beff, s.n_tok, Dd)
                         self._grads_ready(m.embed_to_rec[s.embed])
                         continue
-                    hip.gemm(hip.GEMM_TN, s.K, Dd, T, b["drec"], s.K, b["hdec"], Dd, ps.g(conv.weight).view(s.K, Dd), Dd, AT)
-                    hip.colsum(b["drec"], ps.g(conv.bias), T, s.K, s.K)
-                    hip.layernorm_bwd(b["dh"], s.n_tok, 0, st.x_last, g.L, s.tok_off, nrm.weight, b["mean_f"], b["rstd_f"],
-                                      None, dx, dx16, ps.g(nrm.weight), ps.g(nrm.bias), st.top_bias_grad(), gbuf["ln_ws"],
-                                      s.Beff, s.n_tok, Dd)
-                    self._grads_ready(m.embed_to_rec[s.embed])
+                    if not self._ends_deferred(self._rec_wgrad(s)):
+                        hip.gemm(hip.GEMM_TN, s.K, Dd, T, b["drec"], s.K, b["hdec"], Dd, ps.g(conv.weight).view(s.K, Dd), Dd, AT)
+                    if not (loss_cs and b.get("drec_cs") is not None):   # (else: partial rows left by the loss launch)
+                        hip.colsum(b["drec"], ps.g(conv.bias), T, s.K, s.K)
+                    self._final_layernorm_bwd(("ln_dec", s.name), gbuf, b["dh"], s.n_tok, 0, st.x_last, g.L, s.tok_off, nrm, b["mean_f"],
+                                              b["rstd_f"], dx, dx16, st.top_bias_grad(), s.Beff, s.n_tok, Dd)
+                    if not ends:
+                        self._grads_ready(m.embed_to_rec[s.embed])
                 dx0, _ = st.backward(dx, defer=self._plan in ("all", "enc", "ovl"))
                 side_post(g, gbuf, st, dx0)
             return run
 
         def side_post(g, gbuf, st, dx0):
-            self._grads_ready(st.t.norm)
+            if not ends:
+                self._grads_ready(st.t.norm)
             # unmask backward: visible rows -> enc_to_dec output grad; masked rows -> mask-token grads
-            hip.gather_rows(dx0, gbuf["vis"], gbuf["dy_e2d"], g.Beff, g.L, g.N, Dd, g.N, 0)
+            # (part "b": the gather writes the bf16 operand of the enc_to_dec GEMMs directly, with its column sums as partial rows)
+            e2d_cs = gbuf["e2d_cs"] if self._ends("b") and not self.e2d_identity else None
+            if e2d_cs is not None:
+                hip.gather_rows_bf16_cs(dx0, gbuf["vis"], gbuf["dy_e2d16"], e2d_cs, g.Beff, g.L, g.N, Dd)
+            else:
+                hip.gather_rows(dx0, gbuf["vis"], gbuf["dy_e2d"], g.Beff, g.L, g.N, Dd, g.N, 0)
             for s in g.mods:
                 if self.deterministic:
                     per_sample = self.tie_order == "torch"
@@ -1664,14 +1869,18 @@ class MAEEngine(EngineBase):
             M = g.Beff * g.N  # noqa: N806
             lin = m.enc_to_dec[g.model]
             if not self.e2d_identity:
-                hip.cast_bf16(gbuf["dy_e2d"], gbuf["dy_e2d16"], M * Dd)
+                if e2d_cs is None:
+                    hip.cast_bf16(gbuf["dy_e2d"], gbuf["dy_e2d16"], M * Dd)
                 hip.gemm(hip.GEMM_NN, M, E, Dd, gbuf["dy_e2d16"], Dd, ps.h(lin.weight), E, gbuf["dhenc"], E)
                 if self.deterministic:
                     self._det_linear_grads(("e2d", g.name), gbuf["dy_e2d16"], gbuf["henc"], Dd, E, M, ps.g(lin.weight), ps.g(lin.bias))
                 else:
-                    hip.gemm(hip.GEMM_TN, Dd, E, M, gbuf["dy_e2d16"], Dd, gbuf["henc"], E, ps.g(lin.weight), E, AT)
-                    hip.colsum(gbuf["dy_e2d16"], ps.g(lin.bias), M, Dd, Dd)
-                self._grads_ready(lin)
+                    if not self._ends_deferred(self._e2d_wgrad(g)):
+                        hip.gemm(hip.GEMM_TN, Dd, E, M, gbuf["dy_e2d16"], Dd, gbuf["henc"], E, ps.g(lin.weight), E, AT)
+                    if e2d_cs is None:
+                        hip.colsum(gbuf["dy_e2d16"], ps.g(lin.bias), M, Dd, Dd)
+                if not ends:
+                    self._grads_ready(lin)
             if self.joint is not None:   # final LN of the joint encoder, this group's rows
                 jt = self.joint
                 jn = jt.t.norm
@@ -1680,13 +1889,12 @@ class MAEEngine(EngineBase):
                     self._det_layernorm_bwd(("ln_joint", g.name), dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn, gbuf["mean_j"],
                                             gbuf["rstd_j"], jt.dxa, jt.top16, jt.top_bias_grad(), g.Beff, g.N, E)
                 else:
-                    hip.layernorm_bwd(dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn.weight, gbuf["mean_j"],
-                                      gbuf["rstd_j"], None, jt.dxa, jt.top16, ps.g(jn.weight), ps.g(jn.bias),
-                                      jt.top_bias_grad(), gbuf["ln_ws"], g.Beff, g.N, E)
+                    self._final_layernorm_bwd(("ln_joint", g.name), gbuf, dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn, gbuf["mean_j"],
+                                              gbuf["rstd_j"], jt.dxa, jt.top16, jt.top_bias_grad(), g.Beff, g.N, E)
 
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":
-            self._launch_wgrads([(st, 0, st.depth) for st in self.dec.values()])
+            self._launch_wgrads([(st, 0, st.depth) for st in self.dec.values()], ends)
 
     def _bwd_joint(self) -> None:
         jt = self.joint
@@ -1699,6 +1907,7 @@ class MAEEngine(EngineBase):
         """Layers ``hi-1 .. lo`` of every group encoder (groups on parallel streams); ``first`` also runs the final-LN
         backward, ``last`` the scatter + patch-embed backward."""
         m, E, ps = self.model, self.E, self.store  # noqa: N806
+        ends = self._ends_tags(*(["enc_first"] if first else []), *(["enc_last"] if last else []))
 
         def side(g):
             def run():
@@ -1713,16 +1922,12 @@ class MAEEngine(EngineBase):
                     self._grads_ready(nrm)
                     self._enc_state[g.name] = (st.dxa, st.top16)
                 elif first:
-                    if self.joint is not None:
-                        hip.layernorm_bwd(self._djoint, m.joint_N, g.joint_off, st.x_last, g.N, 0, nrm.weight, gbuf["mean_e"],
-                                          gbuf["rstd_e"], None, st.dxa, st.top16, ps.g(nrm.weight), ps.g(nrm.bias),
-                                          st.top_bias_grad(), gbuf["ln_ws"], g.Beff, g.N, E)
-                    else:
-                        hip.layernorm_bwd(gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0, st.x_last, g.N, 0, nrm.weight,
-                                          gbuf["mean_e"],
-                                          gbuf["rstd_e"], None, st.dxa, st.top16, ps.g(nrm.weight), ps.g(nrm.bias),
-                                          st.top_bias_grad(), gbuf["ln_ws"], g.Beff, g.N, E)
-                    self._grads_ready(nrm)
+                    dy, dy_L, dy_off = ((self._djoint, m.joint_N, g.joint_off) if self.joint is not None else  # noqa: N806
+                                        (gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0))
+                    self._final_layernorm_bwd(("ln_enc", g.name), gbuf, dy, dy_L, dy_off, st.x_last, g.N, 0, nrm, gbuf["mean_e"],
+                                              gbuf["rstd_e"], st.dxa, st.top16, st.top_bias_grad(), g.Beff, g.N, E)
+                    if not ends:
+                        self._grads_ready(nrm)
                     self._enc_state[g.name] = (st.dxa, st.top16)
                 cur, _ = self._enc_state[g.name]
                 self._enc_state[g.name] = st.backward(cur, s_hi, s_lo, defer=self._plan != "fused")
@@ -1732,19 +1937,31 @@ class MAEEngine(EngineBase):
 
         def side_post(g, gbuf, st):
             dx0 = self._enc_state[g.name][0]
+            if self._ends("c") and self._embed_cs():
+                # the patch-embed backward reads the visible rows' gradient through the position map: no expanded copy
+                for s in g.mods:
+                    end = self.embed[s.name]
+                    end.backward_ends(dx0, gbuf["inv"], g.N, g.L, self._ends_deferred(end.wgrad_problem()), not self._dw_conv_clear)
+                return
             # back to the full group sequence (masked tokens get zero: every row is written, no memset), then the
             # patch-embed backward per modality
+            if gbuf.get("dxg") is None:      # (first needed in an eager run: segments are captured on their second run)
+                gbuf["dxg"] = torch.empty(g.Beff, g.L, E, dtype=F32, device=self.device)
             hip.expand_rows(dx0, gbuf["inv"], gbuf["dxg"], g.Beff, g.L, g.N, E)
             for s in g.mods:
-                self.embed[s.name].backward(gbuf["dxg"], g.L, not self._dw_conv_clear)   # (normally cleared by zero_grad's span launch)
+                end = self.embed[s.name]
+                if self._embed_cs():
+                    end.backward_ends(gbuf["dxg"], None, 0, g.L, self._ends_deferred(end.wgrad_problem()), not self._dw_conv_clear)
+                else:       # (the staging buffer is normally cleared by zero_grad's span launch)
+                    end.backward(gbuf["dxg"], g.L, not self._dw_conv_clear, self._ends_deferred(end.wgrad_problem()))
 
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":      # this segment's layers of every group encoder
-            self._launch_wgrads([(st, min(lo, st.depth), min(hi, st.depth)) for st in self.enc.values()])
+            self._launch_wgrads([(st, min(lo, st.depth), min(hi, st.depth)) for st in self.enc.values()], ends)
         elif self.deterministic and last:
             self._det_finish_backward()
         elif self._plan == "all" and last:
-            self._launch_wgrads([(st, 0, st.depth) for st in self._all_stacks()])
+            self._launch_wgrads([(st, 0, st.depth) for st in self._all_stacks()], self._ends_tags("dec", "enc_first", "enc_last"))
         if last:
             for name in m.patch_embed:
                 self._grads_ready(m.patch_embed[name])

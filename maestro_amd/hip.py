@@ -47,6 +47,8 @@ def lib() -> ctypes.CDLL:
         _lib.mh_colsum_partial_rows.argtypes = [ci]
         _lib.mh_masked_loss_partial_size.argtypes = _lib.mh_embed_bwd_partial_rows.argtypes = [ci, ci]
         _lib.mh_unmask_token_grad_partial_rows.argtypes = [ctypes.c_long]
+        _lib.mh_masked_loss_cs_rows.argtypes = [ci, ci]                     # include/maestro_hip_ends.h
+        _lib.mh_gather_rows_cs_rows.argtypes = _lib.mh_embed_bwd_cs_rows.argtypes = [ctypes.c_long]
     return _lib
 
 
@@ -550,6 +552,45 @@ def embed_finish_bwd_det(dxg, y, stats, gamma, dyc, param_partial, blk_sums, sum
     for an ``OrderedReduce``, ``blk_sums`` [embed_bwd_partial_rows(B * D, L), 2] is scratch of the call."""
     call("mh_embed_finish_bwd_det", dxg, y, stats, gamma, dyc, param_partial, blk_sums, sums, _I(B), _I(D), _I(L), _I(E),
          _I(tok_off), _I(Lgroup))
+
+
+# ---- step ends (include/maestro_hip_ends.h): producers that leave their bias gradient as partial rows for a ColsumBatch job
+def masked_loss_cs_rows(B, Lm) -> int:  # noqa: N803
+    return int(lib().mh_masked_loss_cs_rows(_I(B), _I(Lm)))
+
+
+def masked_loss_cs(rec, target, mask_group, n_masked, weight, acc, drec, cs_partial, B, Lm, Lgroup, tok_off, PPC, p):  # noqa: N803
+    """``masked_loss`` that also stores the per-workgroup column sums of ``drec`` to ``cs_partial`` [masked_loss_cs_rows(B, Lm), PPC]."""
+    _hbm_call("masked_loss", float(B) * Lm * (PPC * (_esz(rec) + 4 + _esz(drec)) + 1), "mh_masked_loss_cs", rec, target, mask_group,
+              n_masked, _F(weight), acc, drec, cs_partial, _I(B), _I(Lm), _I(Lgroup), _I(tok_off), _I(PPC), _I(p))
+
+
+def masked_loss_bands_cs(rec, target, mask_group, n_elems, weight, acc, drec, cs_partial, B, Lm, Lgroup, tok_off, PPC, p, tgt_C,  # noqa: N803
+                         tgt_c0, n_g):
+    call("mh_masked_loss_bands_cs", rec, target, mask_group, n_elems, _F(weight), acc, drec, cs_partial, _I(B), _I(Lm), _I(Lgroup),
+         _I(tok_off), _I(PPC), _I(p), _I(tgt_C), _I(tgt_c0), _I(n_g))
+
+
+def gather_rows_cs_rows(rows) -> int:
+    return int(lib().mh_gather_rows_cs_rows(_L(rows)))
+
+
+def gather_rows_bf16_cs(src, idx, dst16, cs_partial, B, src_L, n_idx, dim):  # noqa: N803
+    """``gather_rows`` + ``cast_bf16`` in one pass (no f32 intermediate) + the per-workgroup column sums of ``dst16`` to ``cs_partial``
+    [gather_rows_cs_rows(B * n_idx), dim]."""
+    call("mh_gather_rows_bf16_cs", src, idx, dst16, cs_partial, _I(B), _I(src_L), _I(n_idx), _I(dim))
+
+
+def embed_bwd_cs_rows(rows) -> int:
+    return int(lib().mh_embed_bwd_cs_rows(_L(rows)))
+
+
+def embed_finish_bwd_ends(dx, inv, n_vis, y, stats, gamma, dyc, dgamma, dbeta, sums, cs_partial, B, D, L, E, tok_off, Lgroup):  # noqa: N803
+    """``embed_finish_bwd`` reading the gradient of the visible rows ``dx`` [B, n_vis, E] through the position map ``inv`` [B, Lgroup]
+    (``inv`` None: ``dx`` is the dense [B, Lgroup, E] gradient) + the per-workgroup column sums of ``dyc`` to ``cs_partial``
+    [embed_bwd_cs_rows(B * D * L), E]."""
+    call("mh_embed_finish_bwd_ends", dx, inv, _I(n_vis), y, stats, gamma, dyc, dgamma, dbeta, sums, cs_partial, _I(B), _I(D), _I(L),
+         _I(E), _I(tok_off), _I(Lgroup))
 
 
 def det_slices(K: int) -> int:  # noqa: N803

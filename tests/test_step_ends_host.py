@@ -1,0 +1,71 @@
+"""Properties of the step-ends kernels that need no GPU: the straight-line LayerNorm backward forms for the final norms are in
+the library without scratch, issue every load of a wave before their first ``s_waitcnt vmcnt`` and never wait for ``vmcnt(0)``
+inside the pipeline (the helpers and the method are those of tests/test_kernel_resources.py); the new entry points are declared
+in their own header, exported by the library and bound."""
+
+import re
+import shutil
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+from tests.test_kernel_resources import _kernel_bodies, _loads_before_first_vm_wait
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "scripts"))
+
+
+def test_final_layernorm_forms_are_in_the_library_without_scratch():
+    import kernel_resources as kr
+    if not kr.LLVM.exists() or not list((ROOT / "maestro_amd" / "csrc" / "build").glob("*.o")):
+        pytest.skip("needs the built objects (python -m maestro_amd.csrc.build) and the ROCm LLVM tools")
+    names = {k["kernel"]: k for k in kr.library_kernels()}
+    for nv, depth in ((1, 4), (2, 4), (3, 4), (4, 2)):
+        for f32 in ("false", "true"):
+            form = f"ln_bwd_final_kernel<{nv}, {depth}, {f32}>"
+            assert form in names, form
+            k = names[form]
+            assert k["vgpr_count"] <= 256 and k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
+    for form, k in names.items():       # the producers with fused column sums and the position-map forms
+        if any(t in form for t in ("masked_loss_kernel", "gather_rows_bf16_cs_kernel", "embed_bwd_apply_cs_kernel", "embed_bwd_stats_kernel")):
+            assert k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0 and k["vgpr_count"] <= 256, k
+
+
+def test_final_layernorm_forms_issue_their_loads_before_the_first_wait():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not Path(hipcc).exists():
+        pytest.skip("needs hipcc")
+    from maestro_amd.csrc import build as B
+    flags = [f for f in B.FLAGS if f != "-fPIC"]
+    r = subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-o", "-", str(B.CSRC / "norm.hip")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    bodies = _kernel_bodies(r.stdout)
+    for nv, depth in ((2, 4), (3, 4)):
+        for f32 in (0, 1):
+            hits = [b for n, b in bodies.items() if f"ln_bwd_final_kernelILi{nv}ELi{depth}ELb{f32}E" in n]
+            assert len(hits) == 1
+            # gamma (NV) + 4 rows x (x, dy) x NV chunks in flight before anything is waited for; every later wait is counted
+            assert _loads_before_first_vm_wait(hits[0]) >= 9 * nv, (nv, f32)
+            assert not any("s_waitcnt vmcnt(0)" in ln for ln in hits[0]), (nv, f32)
+
+
+def test_ends_entry_points_are_declared_exported_and_bound():
+    import ctypes
+
+    from maestro_amd import hip
+    from maestro_amd.csrc.build import LIB
+    if not LIB.exists():
+        pytest.skip("needs the built library")
+    header = (ROOT / "include" / "maestro_hip_ends.h").read_text()
+    names = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", header))
+    assert len(names) == 7
+    main = (ROOT / "include" / "maestro_hip.h").read_text()
+    handle = ctypes.CDLL(str(LIB))
+    binding = (ROOT / "maestro_amd" / "hip.py").read_text()
+    for n in names:
+        assert hasattr(handle, n), n
+        assert n not in main, f"{n} belongs to maestro_hip_ends.h alone"
+        assert n in binding, f"{n} is not bound in maestro_amd/hip.py"
+    assert hip.COLSUM_ROWS == 16
