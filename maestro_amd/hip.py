@@ -49,6 +49,9 @@ def lib() -> ctypes.CDLL:
         _lib.mh_unmask_token_grad_partial_rows.argtypes = [ctypes.c_long]
         _lib.mh_masked_loss_cs_rows.argtypes = [ci, ci]                     # include/maestro_hip_ends.h
         _lib.mh_gather_rows_cs_rows.argtypes = _lib.mh_embed_bwd_cs_rows.argtypes = [ctypes.c_long]
+        _lib.mh_select_dates.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ctypes.c_long, ci, ci,
+                                         ctypes.c_float, vp]               # include/maestro_hip_staging.h
+        _lib.mh_select_dates.restype = ci
     return _lib
 
 
@@ -728,6 +731,72 @@ def dihedral(x, out, flags):
     B, S = x.shape[0], x.shape[-1]  # noqa: N806
     planes = x.numel() // (B * S * S)
     call("mh_dihedral", x, out, flags, _I(B), _L(planes), _I(S), _I(x.element_size()))
+
+
+# ---- input staging: median-date selection (csrc/staging.hip, include/maestro_hip_staging.h)
+RAW_U8, RAW_I16, RAW_U16, RAW_F32 = 0, 1, 2, 3
+SELECT_MAX_WINDOW = 64
+_RAW_CODE = {torch.uint8: RAW_U8, torch.int16: RAW_I16, torch.uint16: RAW_U16, torch.float32: RAW_F32}
+
+
+def select_dates(raw, dates, t_start, t_win, num_dates, *, mask=None, mask_floor=0, scores=None, log_scale=False, norm_fac=None,
+                 t_start_dev=None, t_win_dev=None, out=None, out_dates=None, out_index=None):
+    """Median-date selection of one modality of one batch (``maestro/dataset/dataset.py:188-220``).
+
+    ``raw`` ``[B, Tmax, C, S, S]`` uint8 / int16 / uint16 (passed through as its bytes) / float32, ``dates`` int16 ``[B, Tmax, 3]``,
+    optional ``mask`` uint8 ``[B, Tmax, Cm, S, S]`` and ``scores`` float64 ``[B, Tmax]``: device tensors.  ``t_start`` / ``t_win``
+    are the HOST copies (CPU tensors or sequences) of the per-sample window plan: they are validated here, before anything is
+    launched, because the kernel trusts them; ``t_start_dev`` / ``t_win_dev`` are their int32 device copies (uploaded when None).
+    Returns ``(out [B, nd, C, S, S] f32, out_dates [B, nd, 3] i16, out_index [B, nd] i32)``."""
+    code = _RAW_CODE.get(raw.dtype)
+    if code is None:
+        raise HipExtensionError(f"select_dates: raw dtype {raw.dtype} (uint8, int16, uint16 or float32)")
+    if raw.dim() != 5 or raw.shape[-1] != raw.shape[-2] or not raw.is_contiguous():
+        raise HipExtensionError("select_dates: a contiguous [B, Tmax, C, S, S] raster expected")
+    B, Tmax, C, S, _ = raw.shape  # noqa: N806
+    nd = int(num_dates)
+    ts = torch.as_tensor(t_start).to("cpu", torch.int64).reshape(-1)
+    tw = torch.as_tensor(t_win).to("cpu", torch.int64).reshape(-1)
+    if ts.numel() != B or tw.numel() != B or nd < 1 or B < 1 or C * S * S < 1:
+        raise HipExtensionError(f"select_dates: t_start / t_win must hold one value per sample (B = {B}), num_dates >= 1")
+    if int(tw.min()) < 1 or int(tw.max()) > SELECT_MAX_WINDOW:
+        raise HipExtensionError(f"select_dates: windows of {int(tw.min())} ... {int(tw.max())} dates (1 ... {SELECT_MAX_WINDOW} are supported)")
+    if int(ts.min()) < 0 or int((ts + nd * tw).max()) > Tmax:
+        raise HipExtensionError(f"select_dates: a sample's {nd} windows reach outside its {Tmax} padded dates")
+    if dates.dtype != torch.int16 or tuple(dates.shape) != (B, Tmax, 3) or not dates.is_contiguous():
+        raise HipExtensionError(f"select_dates: dates must be a contiguous int16 [{B}, {Tmax}, 3] tensor")
+    Cm = 0  # noqa: N806
+    if mask is not None:
+        if mask.dtype != torch.uint8 or mask.dim() != 5 or tuple(mask.shape[:2]) + tuple(mask.shape[3:]) != (B, Tmax, S, S) \
+                or mask.shape[2] < 1 or not mask.is_contiguous():
+            raise HipExtensionError(f"select_dates: mask must be a contiguous uint8 [{B}, {Tmax}, Cm, {S}, {S}] tensor")
+        Cm = mask.shape[2]  # noqa: N806
+    if scores is not None and (scores.dtype != torch.float64 or tuple(scores.shape) != (B, Tmax) or not scores.is_contiguous()):
+        raise HipExtensionError(f"select_dates: scores must be a contiguous float64 [{B}, {Tmax}] tensor")
+    if norm_fac is not None and not float(norm_fac) > 0.0:
+        raise HipExtensionError(f"select_dates: norm_fac {norm_fac} (a positive number, or None for no division)")
+    dev = raw.device
+    if t_start_dev is None:
+        t_start_dev = ts.to(torch.int32).to(dev)
+    if t_win_dev is None:
+        t_win_dev = tw.to(torch.int32).to(dev)
+    for name, t in (("t_start_dev", t_start_dev), ("t_win_dev", t_win_dev)):
+        if t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous():
+            raise HipExtensionError(f"select_dates: {name} must be a contiguous int32 [{B}] tensor")
+    if out is None:
+        out = torch.empty((B, nd, C, S, S), dtype=torch.float32, device=dev)
+    if out_dates is None:
+        out_dates = torch.empty((B, nd, 3), dtype=torch.int16, device=dev)
+    if out_index is None:
+        out_index = torch.empty((B, nd), dtype=torch.int32, device=dev)
+    for name, t, shape, dt in (("out", out, (B, nd, C, S, S), torch.float32), ("out_dates", out_dates, (B, nd, 3), torch.int16),
+                               ("out_index", out_index, (B, nd), torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise HipExtensionError(f"select_dates: {name} must be a contiguous {dt} {list(shape)} tensor")
+    call("mh_select_dates", raw, _I(code), mask, _I(Cm), _I(int(mask_floor)), dates, t_start_dev, t_win_dev, _I(int(tw.max())),
+         scores, out, out_dates, out_index, _I(B), _I(Tmax), _I(nd), _L(C * S * S), _I(S * S), _I(int(bool(log_scale))),
+         _F(float(norm_fac) if norm_fac is not None else 0.0))
+    return out, out_dates, out_index
 
 
 # ---- probe / finetune heads (csrc/heads.hip)
