@@ -5,11 +5,26 @@
  * lines whose ATen/einops op sequence it replaces (paths relative to the reference root).
  *
  * Conventions (all entry points):
- *   - plain pointers + sizes, no torch types; every pointer is DEVICE memory owned by the caller unless noted;
+ *   - plain pointers + sizes, no torch types; every pointer is DEVICE memory owned by the caller unless noted (or its name
+ *     ends in _host);
  *   - asynchronous on `stream` (a hipStream_t passed as void*), never synchronises, allocates nothing, keeps no
  *     global mutable state, re-entrant across streams/threads; graph-capturable;
- *   - returns 0 on success, <0 for a bad argument, >0 = hipError_t; mh_last_error() gives a thread-local message;
+ *   - returns 0 on success, <0 for a bad argument (nothing is launched), >0 = hipError_t; mh_last_error() gives a thread-local
+ *     message;
  *   - bf16 = raw uint16 bits; "f32" = float; row-major with explicit leading dimensions (in elements).
+ *
+ * Two terms that several sections use:
+ *
+ * Deterministic forms (mh_reduce_ordered, mh_colsum_partial, the *_det entry points; DESIGN.md, "Deterministic mode"): an
+ * ordered fp32 reduction and the atomic-free first phases of the reductions of the pretraining step.  None of them issues a
+ * floating-point atomic: every output element is written by exactly one plain store per launch, so the bits of a result depend on
+ * the operands alone and not on the order in which the hardware runs the workgroups.
+ *
+ * "Partial rows" (the *_cs / *_ends entry points: the ends of the pretraining step's backward -- pixelify head, enc_to_dec,
+ * patch-embed; DESIGN.md section 4, "Step ends"): workgroup i of the producer stores the column sums of the rows it wrote to
+ * cs_partial[i, 0 .. cols) (f32, dense, plain stores, every element of every row written, zeros included; no atomics).  The sums
+ * are of the bf16-ROUNDED values the producer stores -- what a column sum over the stored tensor would read.  One job of
+ * mh_colsum_batched (rows = the *_cs_rows() value, cols, ld = cols) finishes them.
  */
 #ifndef MAESTRO_HIP_H
 #define MAESTRO_HIP_H
@@ -267,6 +282,27 @@ typedef struct {
     int rows, cols, ld, reserved;
 } MhColsumJob;
 int mh_colsum_batched(const MhColsumJob* jobs_device, int n_jobs, const uint64_t* blocks_device, int n_blocks, void* stream);
+/* The deterministic form: ordered column sums.  One job: src f32 [rows, ld] (cols <= ld), dst f32 [cols].  Jobs that share a
+ * `dst` are ADJACENT in the table and form a chain (same cols and flags throughout).
+ * The result is defined exactly; every operation is an IEEE fp32 round-to-nearest add, nothing is reassociated:
+ *   chunk_k[c]    = ((+0 + src[16k][c]) + src[16k+1][c]) + ...          over the chunk's rows (the last chunk may be short)
+ *   job_total[c]  = ((+0 + chunk_0[c]) + chunk_1[c]) + ...               in row order
+ *   dst[c]        = (ADD ? dst_old[c] : +0) + job_total_0[c] + job_total_1[c] + ...      in table order, left to right
+ * Exactly one plain store goes to each dst[c] per launch; no atomics.
+ * `blocks_device`: one work item per 256-thread workgroup, (index of the chain's first job) << 32 | column block (256 columns).
+ * The table lives in device memory, which the host cannot read without a synchronisation, so the call also takes the table's
+ * host copy (`jobs_host`, read during the call only) and checks it before anything is launched: null src / dst, rows or cols
+ * <= 0, cols > ld, a chain whose members differ in cols or flags, a chain that is split apart in the table (a dst that returns
+ * after another chain), n_jobs or n_blocks <= 0. */
+#define MH_ORDERED_ROWS 16        /* rows per chunk of the ordered reduction */
+#define MH_ORDERED_ADD 1          /* MhOrderedJob.flags bit 0: add to the value dst holds (default: overwrite) */
+typedef struct MhOrderedJob {
+    const float* src;
+    float* dst;
+    int rows, cols, ld, flags;
+} MhOrderedJob;
+int mh_reduce_ordered(const MhOrderedJob* jobs_host, const MhOrderedJob* jobs_device, int n_jobs, const uint64_t* blocks_device,
+                      int n_blocks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- attention
  * Fused softmax(Q K^T * scale) V, no mask, no dropout (vit_pytorch Attention.forward; call sites mae.py:135-174).
@@ -316,6 +352,27 @@ int mh_embed_finish(const float* y, const float* stats, const float* gamma, cons
 int mh_embed_finish_bwd(const float* dxg, const float* y, const float* stats, const float* gamma, void* dyc,
                         float* dgamma, float* dbeta, float* sums, int B, int D, int L, int E, int tok_off, int Lgroup,
                         void* stream);
+/* GroupNorm backward of the patch embedding, deterministic form.  Operands as mh_embed_finish_bwd, but pass 1 writes per
+ * workgroup: (S1, S2) to blk_sums [B*D, nblk, 2] and dgamma | dbeta to param_partial [B*D * nblk, 2 E] (dense), with
+ * nblk = mh_embed_bwd_partial_rows(1, L).  The per-image sums[B*D, 2] that pass 2 reads are finished inside the call by an
+ * ordered reduction of blk_sums (the order of mh_reduce_ordered); the parameter rows are left for mh_reduce_ordered
+ * (rows = mh_embed_bwd_partial_rows(B*D, L), cols = E, ld = 2 E; dbeta at column offset E). */
+int mh_embed_bwd_partial_rows(int BD, int L);
+int mh_embed_finish_bwd_det(const float* dxg, const float* y, const float* stats, const float* gamma, void* dyc,
+                            float* param_partial, float* blk_sums, float* sums, int B, int D, int L, int E, int tok_off, int Lgroup,
+                            void* stream);
+/* GroupNorm backward of the patch embedding, step-end form: as mh_embed_finish_bwd (same operands, same atomically accumulated dgamma / dbeta, same arithmetic per
+ * element), with two differences:
+ *  - the gradient of the group sequence is read through the position map: dx f32 [B, n_vis, E] holds the gradient of the VISIBLE
+ *    rows only and inv int32 [B, Lgroup] maps a group position to its visible row (< 0: masked).  Token (b, d, l) of the modality
+ *    sits at group position tok_off + d * L + l; a masked position is a zero gradient whose loads are skipped.  inv == NULL:
+ *    dx is the dense [B, Lgroup, E] gradient (n_vis is ignored).
+ *  - cs_partial f32 [mh_embed_bwd_cs_rows(B * D * L), E] receives the partial rows of colsum(dyc) (the conv bias gradient).
+ * E % 4 == 0, E <= 1024. */
+int mh_embed_bwd_cs_rows(long rows);
+int mh_embed_finish_bwd_ends(const float* dx, const int* inv, int n_vis, const float* y, const float* stats, const float* gamma,
+                             void* dyc, float* dgamma, float* dbeta, float* sums, float* cs_partial, int B, int D, int L, int E,
+                             int tok_off, int Lgroup, void* stream);
 /* Date features (maestro/layers/utils.py:128-167): dates int16 [B, D, 3] (year, day-of-year, hour), ref_date int16
  * [B, 1, 3] -> out f32 [B, rows, 8] rows [row_off, row_off + D): fac * [diff x4, sin/cos doy, sin/cos hour]. */
 int mh_date_features(const int16_t* dates, const int16_t* ref_date, float* out, int B, int D, int rows, int row_off,
@@ -329,6 +386,58 @@ int mh_resize(const float* in, float* out, long planes, int Hin, int Win, int Ho
  * elem_bytes-wide elements (1, 2, 4, 8), out of place; flags[b] bit0 = flip rows, bit1 = flip columns, bit2 = transpose.
  * Pure data movement: bit-exact. */
 int mh_dihedral(const void* in, void* out, const uint8_t* flags, int B, long planes, int S, int elem_bytes, void* stream);
+/* Input staging: the median-date selection of multi-temporal rasters that the reference does per sample on the CPU in
+ * maestro/dataset/dataset.py:188-220 (window cut 188-195, cloud mask 196-200, median and deviation 202-203, random_dates 204-206,
+ * mean / nanargmin / gather 208-213, float cast, log and norm_fac 215-220).  No atomics: the same call on the same operands
+ * writes the same bytes.
+ *
+ * One modality of one batch: out[b, j] = the date of window j of sample b that is closest to the window's per-pixel median.
+ *
+ *   raw        [B, Tmax, n_elem] of `raw_code` (n_elem = C * S * S, the raster of one date, dense)
+ *   mask       u8 [B, Tmax, Cm, n_pix] or null (n_pix = S * S; n_elem % n_pix == 0): cloud / snow cover per pixel
+ *   dates      i16 [B, Tmax, 3]
+ *   t_start, t_win   i32 [B]: window j of sample b is the raw dates t_start[b] + j * W_b ... + W_b - 1, W_b = t_win[b]
+ *              (dataset.py:92-104 and 189-190: t_start is the drawn start_mod_date, W_b = T_b / nd).  Samples are padded to Tmax;
+ *              padding and dates outside the nd windows are never read.
+ *   w_max      the largest W_b of the batch as the HOST knows it, 1 ... MH_SELECT_MAX_WINDOW: it sizes the workgroup's LDS.
+ *   scores     f64 [B, Tmax] or null: given per-date scores (random_dates, dataset.py:204-206)
+ *   out        f32 [B, nd, n_elem];  out_dates i16 [B, nd, 3];  out_index i32 [B, nd]: the chosen offset inside each window
+ *
+ * t_start / t_win live on the device and are TRUSTED: 0 <= t_start[b], 1 <= W_b <= w_max, t_start[b] + nd * W_b <= Tmax is the
+ * caller's to check from its host copies (maestro_amd/hip.py does).  As a safety net a workgroup that finds its window outside
+ * these limits reads and writes nothing but out_index[b, j] = -1.
+ *
+ * Per window (dataset.py:193-213):
+ *   - a pixel of a date is masked iff any of its Cm mask values is > mask_floor (for an integer m, m > mask_threshold <=>
+ *     m > floor(mask_threshold); the caller passes the floor, and no mask at all when mask_threshold >= 100, dataset.py:152);
+ *   - a date is dirty iff any of its pixels is masked; if every date of the window is dirty the mask is ignored for that window
+ *     (dataset.py:197-199);
+ *   - per element the median over the window's unmasked dates (even count: the mean of the two middle values a, b; odd: a = b);
+ *   - the score of a date is the sum over the elements of |x - median|; dirty dates are out, the lowest score wins, ties go to
+ *     the lowest index (nanargmin).  The reference divides by n_elem (a mean): the same order.
+ *   - integer raw data is exact: sum |2x - (a + b)| in int64 = 2 * n_elem * the reference's fp64 mean, which is itself exact
+ *     (half-integers far below 2^53), so the choice is the reference's, ties included.
+ *   - f32 raw data: median ((a + b) / 2 in fp32) and |x - median| in fp32 as numpy computes them; the score is summed in fp64 in
+ *     element order 0 ... n_elem - 1.  That is this entry point's DEFINED semantics.  DEVIATION: the reference sums in fp32,
+ *     pairwise, so the two can choose differently only when two scores agree to fp32 rounding (~1e-7 relative * sqrt(n_elem)).
+ *     W_b = 2 on float data is a structural tie (|a - m| and |m - b| differ by rounding alone): the reference's own choice is
+ *     rounding noise there, this one's is whatever the fp64 sums say, index 0 when they are equal.  f32 data inside the windows
+ *     must not hold NaN (the reference would treat it as masked; here it takes part in no comparison).
+ *   - scores given: median and score are skipped; the lowest given score among the clean dates wins (NaN scores are passed
+ *     over; if no date qualifies, index 0).
+ *   - output: the chosen date cast to f32; log_scale != 0: logf(x < 1e-10f ? 1e-10f : x); norm_fac > 0: one IEEE-rounded fp32
+ *     division by norm_fac (never a reciprocal multiply: bit-identical to numpy's `/=`); norm_fac <= 0 = the reference's None.
+ *
+ * One launch, one workgroup per (sample, output date); B * nd <= 2^31 - 1, 1 <= nd <= Tmax, n_elem <= 2^31 - 1. */
+/* element type of `raw` */
+#define MH_RAW_U8 0
+#define MH_RAW_I16 1
+#define MH_RAW_U16 2
+#define MH_RAW_F32 3
+#define MH_SELECT_MAX_WINDOW 64
+int mh_select_dates(const void* raw, int raw_code, const unsigned char* mask, int Cm, int mask_floor, const short* dates,
+                    const int* t_start, const int* t_win, int w_max, const double* scores, float* out, short* out_dates,
+                    int* out_index, int B, int Tmax, int nd, long n_elem, int n_pix, int log_scale, float norm_fac, void* stream);
 /* Elevation rescale copy (maestro/ssl/mim.py:433-436): out[:, c>=1] = 30 * (img[:, 0] - img[:, c]); out != img. */
 int mh_rescale_elev(const float* img, float* out, int BD, int C, int S, void* stream);
 /* Patch layout [BD*g*g, P*P*C] -> image [BD, C, S, S] ('(p1 p2 c) h w -> c (h p1) (w p2)', embed.py:153-160). */
@@ -345,6 +454,12 @@ int mh_mask_select(const float* noise, const uint8_t* struct_mask, int* visible_
  * dst_L rows per sample (x[batch, unmasked_indices], mae.py:261, fused with the joint-encoder concat). */
 int mh_gather_rows(const float* src, const int* idx, float* dst, int B, int src_L, int n_idx, int dim, int dst_L,
                    int dst_off, void* stream);
+/* dst16[b, j, :] = bf16(src[b, idx[b, j], :]) for j < n_idx: mh_gather_rows followed by its bf16 cast, in one
+ * pass and without the f32 intermediate (src f32 [B, src_L, dim], idx int32 [B, n_idx], dst16 bf16 [B * n_idx, dim] dense);
+ * cs_partial f32 [mh_gather_rows_cs_rows(B * n_idx), dim] receives the partial rows of colsum(dst16).  dim % 4 == 0, dim <= 1024. */
+int mh_gather_rows_cs_rows(long rows);
+int mh_gather_rows_bf16_cs(const float* src, const int* idx, void* dst16, float* cs_partial, int B, int src_L, int n_idx, int dim,
+                           void* stream);
 /* Transpose of mh_gather_rows into a ZEROED dsrc (indices unique per sample -> plain stores). */
 int mh_scatter_rows(const float* ddst, const int* idx, float* dsrc, int B, int src_L, int n_idx, int dim, int dst_L,
                     int dst_off, void* stream);
@@ -372,6 +487,15 @@ int mh_unmask_assemble_per_sample(const float* y, const int* inv, const float* m
                                   int B, int L, int n_vis, int Dd, void* stream);
 int mh_unmask_token_grad_per_sample(const float* dxdec, const uint8_t* mask, const int* tok_slot_bl, float* dmask_token, int B,
                                     int L, int Dd, int slot, void* stream);
+/* Mask-token gradient, first phase (the deterministic forms).  Operands as mh_unmask_token_grad / mh_unmask_token_grad_per_sample;
+ * workgroup i writes the sum of its rows to partial[i, 0 .. Dd) (f32 [mh_unmask_token_grad_partial_rows(n_rows), Dd] dense,
+ * 16-byte aligned; rows without a contributing token are written as zeros).  n_rows = B * (t_hi - t_lo), or B * L for the
+ * per-sample form. */
+int mh_unmask_token_grad_partial_rows(long n_rows);
+int mh_unmask_token_grad_det(const float* dxdec, const uint8_t* mask, const int* tok_slot, float* partial, int B, int L, int Dd,
+                             int slot, int t_lo, int t_hi, void* stream);
+int mh_unmask_token_grad_per_sample_det(const float* dxdec, const uint8_t* mask, const int* tok_slot_bl, float* partial, int B,
+                                        int L, int Dd, int slot, void* stream);
 /* out[0] = number of masked tokens of all samples in group positions [t_lo, t_hi) (one modality). */
 int mh_count_masked(const uint8_t* mask, int B, int L, int t_lo, int t_hi, int* out, void* stream);
 /* out[0] = (accumulate ? out[0] : 0) + mult * that count: the masked ELEMENTS of a modality whose band-groups have different
@@ -393,6 +517,26 @@ int mh_masked_loss(const float* rec, const float* target, const uint8_t* mask_gr
 int mh_masked_loss_bands(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems, float weight,
                          float* acc, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC, int p, int tgt_C, int tgt_c0,
                          int n_g, void* stream);
+/* Masked reconstruction loss, first phase (the deterministic forms).  Operands and `drec` (bit for bit) as mh_masked_loss /
+ * mh_masked_loss_bands; instead of adding to the loss word, workgroup i writes its weighted partial loss to loss_partial[i] (zero
+ * is written too; block 0 writes NaN for an empty selection, n_masked == 0).  loss_partial has mh_masked_loss_partial_size(B, Lm)
+ * elements; the modality's loss is their ordered sum. */
+int mh_masked_loss_partial_size(int B, int Lm);
+int mh_masked_loss_det(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked, float weight,
+                       float* loss_partial, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC, int p, void* stream);
+int mh_masked_loss_bands_det(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems, float weight,
+                             float* loss_partial, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC, int p, int tgt_C,
+                             int tgt_c0, int n_g, void* stream);
+/* Masked reconstruction loss, step-end forms.  Operands, the loss word and `drec` (bit for bit) as mh_masked_loss /
+ * mh_masked_loss_bands (`drec` is required here); cs_partial f32 [mh_masked_loss_cs_rows(B, Lm), PPC] receives the partial rows of
+ * colsum(drec).  PPC % 4 == 0, PPC <= 1024. */
+int mh_masked_loss_cs_rows(int B, int Lm);
+int mh_masked_loss_cs(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked, float weight,
+                      float* acc, void* drec, float* cs_partial, int B, int Lm, int Lgroup, int tok_off, int PPC, int p,
+                      void* stream);
+int mh_masked_loss_bands_cs(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems, float weight,
+                            float* acc, void* drec, float* cs_partial, int B, int Lm, int Lgroup, int tok_off, int PPC, int p,
+                            int tgt_C, int tgt_c0, int n_g, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- probe / finetune heads
  * (maestro/ssl/mim.py:343-394 compute_logits, maestro/layers/head.py, maestro/train/base.py:98-151)
@@ -434,10 +578,43 @@ int mh_ce_loss(const float* logits, const void* target, int target_bytes, long m
                void* dlogits, int dlogits_is_f32, int B, int g, int P, int C, int ld, void* stream);
 int mh_bce_loss(const float* logits, const float* target, float missing_val, float* acc, float* dlogits, int B, int C,
                 void* stream);
+/* Prediction metrics: the confusion matrices that maestro/train/metric.py keeps per target and stage (fed on every supervised
+ * step from maestro/train/base.py:143-146).  Results are integers: exact, and independent of the launch order (no float
+ * atomics; 32-bit LDS counters per workgroup, 64-bit integer atomics into `cm`).
+ *
+ * Mono-label confusion matrix (maestro/train/metric.py:63-77 "multiclass": argmax over the classes, then
+ * torchmetrics.functional.confusion_matrix; the selection of valid entries is maestro/train/base.py:120-138).
+ * Operands as mh_ce_loss (csrc/heads.hip): `logits` f32 at patch layout
+ * [B*g*g, ld >= P*P*C], columns (p1*P + p2)*C + c (PixelifyBands' '(p1 p2 c)', maestro/layers/embed.py:153-160); `target` the
+ * [B, S, S] raster, S = g*P, signed integers of `target_bytes` = 1, 2, 4 or 8 bytes; classification is g = P = 1.
+ *   for every pixel with t != missing_val && 0 <= t < C:   cm[t*C + argmax_c logits] += 1
+ * `cm` is int64 [C, C], rows = targets, columns = predictions (torchmetrics' orientation, metric.py:83-84); the call ADDS,
+ * the caller zeroes.  The arg-max is torch.argmax's: the lowest index among equal maxima; a NaN compares as the maximum and
+ * the first NaN wins.  One pass: every logit is read once, in memory order (16-byte loads when ld % 4 == 0 and `logits` is
+ * 16-byte aligned; any ld and 4-byte alignment are accepted); pad columns (ld > P*P*C) are never read.
+ * 2 <= C <= 128; ld >= P*P*C; g*P <= 46340. */
+int mh_confusion_ce(const float* logits, const void* target, int target_bytes, long missing_val, long long* cm, int B, int g,
+                    int P, int C, int ld, void* stream);
+/* Multilabel confusion matrices (maestro/train/metric.py:154-160 "multilabel", read at metric.py:164-166; also the binary
+ * 2x2 of "change_detect", metric.py:68-77, with C = 1).  Operands as mh_bce_loss: `logits`, `target` f32 [B, C]
+ * dense.  A row is used iff none of its targets equals missing_val (base.py:120-123); for every used (b, l)
+ *   cm[l][target > 0.5 ? 1 : 0][logit > logit_threshold ? 1 : 0] += 1,      cm int64 [C, 2, 2], the call ADDS.
+ * DEVIATION from the reference, which tests sigmoid(logit) > thr in fp32: the host passes logit_threshold =
+ * log(thr / (1 - thr)) (0 for the reference's 0.5).  The two forms differ only where the fp32 sigmoid rounds onto thr, i.e. for
+ * |logit - logit_threshold| below about 1e-7.
+ * 1 <= C <= 1024. */
+int mh_confusion_bce(const float* logits, const float* target, float missing_val, float logit_threshold, long long* cm, int B,
+                     int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- misc
  * column sums: out[n] += sum_m x[m, n]  (bias gradients); x bf16 or f32; atomically accumulated. */
 int mh_colsum(const void* x, int x_is_f32, float* out, int M, int N, int ld, void* stream);
+/* Column sums, first phase (the deterministic form: the arithmetic of mh_colsum without its final atomic add):
+ * x bf16 or f32 [M, ld] (N <= ld, N % 4 == 0, ld % 4 == 0); partial f32 [mh_colsum_partial_rows(M), N] dense, 16-byte aligned,
+ * every element written by a plain store.  Row block i sums rows [256 i, 256 i + 256) of x. */
+#define MH_COLSUM_PARTIAL_ROWS 256 /* rows per row block of mh_colsum_partial: a constant, so the partial layout depends on M alone */
+int mh_colsum_partial_rows(int M);
+int mh_colsum_partial(const void* x, int x_is_f32, float* partial, int M, int N, int ld, void* stream);
 /* Zero n_spans (offset, length) float ranges of one buffer (spans: device array of 2*n_spans longs; max_len = longest span).
  * Used to clear only the atomically accumulated gradient slots when the weight gradients are stored by the grouped GEMM. */
 int mh_zero_spans(float* base, const long* spans_device, int n_spans, long max_len, void* stream);

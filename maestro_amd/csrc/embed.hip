@@ -4,7 +4,6 @@
 #include "common.hpp"
 #include "reduce_det.hpp"
 #include "../../include/maestro_hip.h"
-#include "../../include/maestro_hip_ends.h"
 
 namespace {
 
@@ -268,9 +267,9 @@ constexpr int EB_ROWS = 8;
 // NV = ceil(E / 256) four-column chunks per lane (round 6): a lane owns the same columns in every row, so the dgamma / dbeta partial sums
 // of its EB_ROWS rows stay in registers and touch LDS once at the end (they used to be read-modify-written in LDS for every element:
 // two LDS round trips per element in a kernel that streams 8 bytes per element from HBM).  NV = 0: any E (the LDS form).
-// DET (deterministic mode, include/maestro_hip_det.h): no atomics -- the block writes its (S1, S2) to sums[bd, blockIdx.x, 2] and its
+// DET (deterministic mode, mh_embed_finish_bwd_det): no atomics -- the block writes its (S1, S2) to sums[bd, blockIdx.x, 2] and its
 // dgamma | dbeta row to dgamma[(bd * gridDim.x + blockIdx.x), 2 E] (dbeta unused); LDS then carries 8 more floats for the waves' sums.
-// MAP (include/maestro_hip_ends.h, NV > 0 only): dxg is the gradient of the VISIBLE rows [B, n_vis, E] and inv [B, Lgroup] maps a group
+// MAP (mh_embed_finish_bwd_ends, NV > 0 only): dxg is the gradient of the VISIBLE rows [B, n_vis, E] and inv [B, Lgroup] maps a group
 // position to its visible row (< 0: masked = a zero gradient).  A masked row adds nothing to any of the sums: the wave skips it
 // (the branch is wave-uniform) and issues none of its loads.
 template <int NV, bool DET, bool MAP = false>
@@ -415,7 +414,7 @@ __global__ __launch_bounds__(256) void embed_bwd_apply_kernel(const float* __res
     }
 }
 
-// ---- backward pass 2 with the conv bias gradient (include/maestro_hip_ends.h): the same arithmetic per element, EA_ROWS rows per wave, so
+// ---- backward pass 2 with the conv bias gradient (mh_embed_finish_bwd_ends): the same arithmetic per element, EA_ROWS rows per wave, so
 // that a lane owns the same columns in every row and the column sums of the bf16 values it stores stay in registers; the block's four
 // waves meet in LDS and store one partial row.  MAP: the gradient through the position map (see embed_bwd_stats_kernel); a masked
 // row is a zero gradient -- its dyc row still depends on yconv -- and its gradient loads are skipped.

@@ -1,7 +1,5 @@
 // Masked reconstruction loss at patch layout + its gradient, bias-gradient column sums, casts, fused AdamW.
 #include "gemm_common.hpp"
-#include "../../include/maestro_hip_det.h"
-#include "../../include/maestro_hip_ends.h"
 
 namespace {
 
@@ -10,9 +8,9 @@ namespace {
 // coef * de/drec for masked tokens, 0 elsewhere, with coef = weight / (n_masked_tokens * PPC).
 // One WAVE per token (4 tokens per block), 16-byte accesses; the block reduces its partial loss through LDS and issues one
 // atomic (32768 -> 8192 atomics for the aerial modality; blocks whose 4 tokens are all visible issue none).
-// DET (deterministic mode, include/maestro_hip_det.h): the same arithmetic, but the block's partial loss goes to acc[blockIdx.x]
+// DET (deterministic mode, mh_masked_loss_det): the same arithmetic, but the block's partial loss goes to acc[blockIdx.x]
 // with a plain store instead of being added to the loss word.
-// CS (include/maestro_hip_ends.h): the block also stores the column sums of the bf16 values it writes to drec -- the pixelify bias
+// CS (step ends, mh_masked_loss_cs): the block also stores the column sums of the bf16 values it writes to drec -- the pixelify bias
 // gradient -- to cs_partial[blockIdx.x, 0 .. PPC) (plain stores, zeros included), PPC <= 256 * LOSS_CS_NV.  A lane owns the same
 // columns in every row, so the sums stay in registers until the block's four waves meet in LDS.
 constexpr int LOSS_CS_NV = 4;
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
 // launch is bound by two things that pull in opposite directions -- memory-level parallelism (wants many resident waves) and the
 // same-address atomics of the final add (M / rows_per_block per column: wants few, fat blocks) -- so a block is 16 waves on up to
 // 1024 rows: 32768 x 768 bf16 31.7 -> see scripts/bench_small_reductions.py.
-// DET (include/maestro_hip_det.h): row block blockIdx.y stores its sums to out[blockIdx.y, :] instead of adding them to out[:].
+// DET (mh_colsum_partial): row block blockIdx.y stores its sums to out[blockIdx.y, :] instead of adding them to out[:].
 template <bool DET>
 __global__ __launch_bounds__(1024) void colsum_kernel(const void* __restrict__ x, int is_f32, float* __restrict__ out, int M,
                                                       int N, int ld, int rows_per_block) {

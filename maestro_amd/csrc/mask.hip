@@ -2,7 +2,6 @@
 // Integer/index work is bit-exact by construction (counting rank = stable argsort).
 #include "common.hpp"
 #include "../../include/maestro_hip.h"
-#include "../../include/maestro_hip_ends.h"
 
 namespace {
 
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 }
 
 // dst16[row, :] = bf16(src[b, idx[row], :]) and, per workgroup, the column sums of the bf16 values written (the enc_to_dec bias
-// gradient as partial rows, include/maestro_hip_ends.h).  GC_ROWS rows per wave: a lane owns the same columns in every row, the
+// gradient as partial rows, mh_gather_rows_bf16_cs).  GC_ROWS rows per wave: a lane owns the same columns in every row, the
 // wave's loads of all its rows go out before the first is used, the four waves meet in LDS once.
 constexpr int GC_ROWS = 8;
 template <int NV>
@@ -185,7 +184,7 @@ __global__ __launch_bounds__(256) void unmask_kernel(const float* __restrict__ y
 // Round 3: 1024 threads and 512 rows per block instead of 256 / 128 -- the launch was bound by its memory-level parallelism (two
 // row lanes x four loads per block) and by B*L/128 same-address atomics per column (36 MB in 46 us = 0.8 TB/s at 32768 x 512).
 constexpr int UM_ROWS = 512, UM_NT = 1024;
-// DET (include/maestro_hip_det.h): the block's sums go to row blockIdx.x of dmask_token [blocks, Dd] with plain stores.
+// DET (mh_unmask_token_grad_det): the block's sums go to row blockIdx.x of dmask_token [blocks, Dd] with plain stores.
 template <bool DET>
 __global__ __launch_bounds__(UM_NT) void unmask_bwd_token_kernel(const float* __restrict__ dxdec, const uint8_t* __restrict__ mask,
                                                                  const int* __restrict__ tok_slot, float* __restrict__ dmask_token,

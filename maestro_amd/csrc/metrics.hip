@@ -1,10 +1,10 @@
 // Prediction metrics of the probe / finetune branch (maestro/train/metric.py, fed from maestro/train/base.py:143-146): confusion
-// matrices counted on the device from the logits the loss kernels already read.  C ABI: include/maestro_hip_metrics.h.
+// matrices counted on the device from the logits the loss kernels already read.  C ABI: include/maestro_hip.h.
 //
 // Everything here is integer: LDS histograms of 32-bit counters per workgroup, flushed with 64-bit integer atomics (plain vector
 // memory).  The result does not depend on the launch order and there is no float atomic.
 #include "common.hpp"
-#include "../../include/maestro_hip_metrics.h"
+#include "../../include/maestro_hip.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// Ordered fp32 column sums (include/maestro_hip_det.h): the last hop of every reduction of the step in deterministic mode.
+// Ordered fp32 column sums (mh_reduce_ordered, include/maestro_hip.h): the last hop of every reduction of the step in deterministic mode.
 // One thread per destination column walks its chain of jobs in table order, every job in 16-row chunks; one plain store per
 // column, no atomics, so the bits are a function of the operands and the table alone.
 #include <algorithm>

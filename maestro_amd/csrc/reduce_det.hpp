@@ -1,8 +1,8 @@
-// The summation order of deterministic mode (include/maestro_hip_det.h): shared by mh_reduce_ordered (reduce_det.hip) and the
+// The summation order of deterministic mode (include/maestro_hip.h): shared by mh_reduce_ordered (reduce_det.hip) and the
 // entry points that finish a reduction of their own in that order (embed.hip).
 #pragma once
 #include "common.hpp"
-#include "../../include/maestro_hip_det.h"
+#include "../../include/maestro_hip.h"
 
 // job_total of one column: `src` points at the column's element of row 0.  The chunk's MH_ORDERED_ROWS loads go out together, the
 // adds keep their order.  Rows beyond the end are added as +0, which changes no bit: a running sum that started from +0 is

@@ -1,5 +1,5 @@
 // Input staging: the median-date selection of multi-temporal rasters (maestro/dataset/dataset.py:188-220), one launch per modality
-// per batch.  C ABI and the exact rule: include/maestro_hip_staging.h.
+// per batch.  C ABI and the exact rule: include/maestro_hip.h.
 //
 // One workgroup per (sample, output date).  The rasters are tiny (C * S * S = 360 ... 2560 elements, windows of at most 64 dates):
 // what costs is latency and launch count, not bandwidth.  A workgroup walks the raster in chunks of SD_CHUNK elements, one element
@@ -11,7 +11,7 @@
 #include <type_traits>
 
 #include "common.hpp"
-#include "../../include/maestro_hip_staging.h"
+#include "../../include/maestro_hip.h"
 
 namespace {
 

@@ -39,18 +39,20 @@ def lib() -> ctypes.CDLL:
                                     "would measure the default path (INTEGRATION.md, profiles/r05_experiments.md, r06_experiments.md)")
         _lib = ctypes.CDLL(str(_LIB_PATH))
         _lib.mh_last_error.restype = ctypes.c_char_p
-        vp, ci = ctypes.c_void_p, ctypes.c_int          # include/maestro_hip_metrics.h
+        _lib.mh_layernorm_bwd_workspace.restype = _lib.mh_gemm_sk_workspace.restype = ctypes.c_long     # the size calls that return long
+        _lib.mh_attn_reduce_partial_rows.restype = ctypes.c_long
+        vp, ci = ctypes.c_void_p, ctypes.c_int          # confusion matrices
         _lib.mh_confusion_ce.argtypes = [vp, vp, ci, ctypes.c_long, vp, ci, ci, ci, ci, ci, vp]
         _lib.mh_confusion_bce.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp, ci, ci, vp]
         _lib.mh_confusion_ce.restype = _lib.mh_confusion_bce.restype = ci
-        _lib.mh_reduce_ordered.argtypes = [vp, vp, ci, vp, ci, vp]          # include/maestro_hip_det.h
+        _lib.mh_reduce_ordered.argtypes = [vp, vp, ci, vp, ci, vp]          # deterministic forms
         _lib.mh_colsum_partial_rows.argtypes = [ci]
         _lib.mh_masked_loss_partial_size.argtypes = _lib.mh_embed_bwd_partial_rows.argtypes = [ci, ci]
         _lib.mh_unmask_token_grad_partial_rows.argtypes = [ctypes.c_long]
-        _lib.mh_masked_loss_cs_rows.argtypes = [ci, ci]                     # include/maestro_hip_ends.h
+        _lib.mh_masked_loss_cs_rows.argtypes = [ci, ci]                     # step ends
         _lib.mh_gather_rows_cs_rows.argtypes = _lib.mh_embed_bwd_cs_rows.argtypes = [ctypes.c_long]
         _lib.mh_select_dates.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ctypes.c_long, ci, ci,
-                                         ctypes.c_float, vp]               # include/maestro_hip_staging.h
+                                         ctypes.c_float, vp]               # input staging
         _lib.mh_select_dates.restype = ci
     return _lib
 
@@ -179,7 +181,6 @@ def sk_workspace(tile: int, grid: int) -> torch.Tensor:
     key = (torch.cuda.current_stream().cuda_stream, tile, grid)
     ws = _sk_ws.get(key)
     if ws is None:
-        lib().mh_gemm_sk_workspace.restype = ctypes.c_long
         nbytes = lib().mh_gemm_sk_workspace(_I(tile), _I(grid))
         if nbytes <= 0:
             raise HipExtensionError(f"mh_gemm_sk_workspace({tile}, {grid}) = {nbytes}")
@@ -389,9 +390,7 @@ def layernorm_fwd_mx(x, x_L, x_off, gamma, beta, y, y_L, y_off, mean, rstd, B, n
 
 
 def layernorm_bwd_workspace(rows, dim) -> int:
-    f = lib().mh_layernorm_bwd_workspace
-    f.restype = ctypes.c_long
-    return int(f(_I(rows), _I(dim)))
+    return int(lib().mh_layernorm_bwd_workspace(_I(rows), _I(dim)))
 
 
 def layernorm_bwd(dy, dy_L, dy_off, x, x_L, x_off, gamma, mean, rstd, dres, dx, dx_bf16, dgamma, dbeta, dcol, workspace,
@@ -445,7 +444,7 @@ class ColsumBatch:
         call("mh_colsum_batched", self.table, _I(self.n), self.blocks, _I(self.n_blocks))
 
 
-# ---- deterministic mode (include/maestro_hip_det.h): atomic-free first phases + the ordered reduction that finishes them
+# ---- deterministic mode (include/maestro_hip.h): atomic-free first phases + the ordered reduction that finishes them
 ORDERED_ROWS, ORDERED_ADD = 16, 1     # MH_ORDERED_ROWS, MH_ORDERED_ADD
 COLSUM_PARTIAL_ROWS = 256             # MH_COLSUM_PARTIAL_ROWS
 
@@ -557,7 +556,7 @@ def embed_finish_bwd_det(dxg, y, stats, gamma, dyc, param_partial, blk_sums, sum
          _I(tok_off), _I(Lgroup))
 
 
-# ---- step ends (include/maestro_hip_ends.h): producers that leave their bias gradient as partial rows for a ColsumBatch job
+# ---- step ends (include/maestro_hip.h): producers that leave their bias gradient as partial rows for a ColsumBatch job
 def masked_loss_cs_rows(B, Lm) -> int:  # noqa: N803
     return int(lib().mh_masked_loss_cs_rows(_I(B), _I(Lm)))
 
@@ -733,7 +732,7 @@ def dihedral(x, out, flags):
     call("mh_dihedral", x, out, flags, _I(B), _L(planes), _I(S), _I(x.element_size()))
 
 
-# ---- input staging: median-date selection (csrc/staging.hip, include/maestro_hip_staging.h)
+# ---- input staging: median-date selection (csrc/staging.hip, include/maestro_hip.h)
 RAW_U8, RAW_I16, RAW_U16, RAW_F32 = 0, 1, 2, 3
 SELECT_MAX_WINDOW = 64
 _RAW_CODE = {torch.uint8: RAW_U8, torch.int16: RAW_I16, torch.uint16: RAW_U16, torch.float32: RAW_F32}
@@ -810,7 +809,6 @@ def token_resize_bwd(dout, out_rows, out_off, din, in_rows, in_off, B, D, h, H, 
 
 
 def attn_reduce_partial_rows(n_seq: int) -> int:
-    lib().mh_attn_reduce_partial_rows.restype = ctypes.c_long
     return int(lib().mh_attn_reduce_partial_rows(_I(n_seq)))
 
 
@@ -852,7 +850,7 @@ def bce_loss(logits, target, missing_val, acc, dlogits, B, C):  # noqa: N803
 
 
 def confusion_ce(logits, target, missing_val, cm, B, g, P, C, ld=None):  # noqa: N803
-    """``cm[t, argmax]`` += 1 over the valid pixels (int64 ``[C, C]``; operands as ``ce_loss``; include/maestro_hip_metrics.h)."""
+    """``cm[t, argmax]`` += 1 over the valid pixels (int64 ``[C, C]``; operands as ``ce_loss``; include/maestro_hip.h)."""
     if cm.dtype != torch.int64 or cm.numel() != C * C or not cm.is_contiguous():
         raise HipExtensionError(f"confusion_ce: cm must be a contiguous int64 [{C}, {C}] tensor")
     call("mh_confusion_ce", logits, target, _I(target.element_size()), _L(int(missing_val)), cm, _I(B), _I(g), _I(P), _I(C),

@@ -3,7 +3,7 @@
 The reference keeps, per target and stage (``maestro/train/base.py:32-50``), a torchmetrics ``Metric`` whose ``update`` turns the
 selected logits into predictions and adds ``torchmetrics.functional.confusion_matrix`` to an int64 state (``metric.py:63-77`` and
 ``132-160``).  Here ``update`` is ONE kernel launch on logits that are already resident (``mh_confusion_ce`` / ``mh_confusion_bce``,
-``include/maestro_hip_metrics.h``): no host read, no synchronisation, no intermediate tensor.  ``compute`` is the reference's
+``include/maestro_hip.h``): no host read, no synchronisation, no intermediate tensor.  ``compute`` is the reference's
 arithmetic on that matrix, in fp64.  Like ``MeanMetric`` (``train/model.py``) the classes are ``nn.Module`` stand-ins: torchmetrics
 is not a dependency.  ``cm`` is a non-persistent buffer, so ``state_dict()`` keeps exactly the reference's keys (torchmetrics'
 states are not persistent either).

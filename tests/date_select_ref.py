@@ -1,6 +1,6 @@
 """Numpy restatements of the median-date selection for the tests (a plain helper module: no tests, no fixtures).
 
-Written from the rule in include/maestro_hip_staging.h, one sample at a time:
+Written from the rule in include/maestro_hip.h, one sample at a time:
 
 (a) ``select_reference``: the reference's form -- masked pixels become NaN, ``nanmedian`` over the window, ``mean`` of the
     absolute deviations over the raster, ``nanargmin`` over the window.

@@ -210,9 +210,10 @@ def bits_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
 
 # ---------------------------------------------------------------------------------------------------- the ledger
 # Every mh_* entry point of include/maestro_hip.h is in exactly one of GUARDED (called by a guard-band test: tests/
-# test_guard_bands_gpu.py, or the guard sections of test_fp8_gpu.py / test_mx_gpu.py) and EXEMPT; tests/test_abi.py enforces it,
-# so a new entry point cannot arrive without a decision.
-GUARD_TEST_FILES = ("test_guard_bands_gpu.py", "test_fp8_gpu.py", "test_mx_gpu.py")
+# test_guard_bands_gpu.py, or the guard section -- the text below the "guard bands (tests/guards.py)" banner -- of the other
+# files listed here) and EXEMPT; tests/test_abi.py enforces it, so a new entry point cannot arrive without a decision.
+GUARD_TEST_FILES = ("test_guard_bands_gpu.py", "test_fp8_gpu.py", "test_mx_gpu.py", "test_det_kernels_gpu.py",
+                    "test_step_ends_gpu.py", "test_metrics_gpu.py", "test_date_select_gpu.py")
 
 # name -> how a guard test reaches it when not by its own name or the hip.py wrapper of the same name (hip.<name without mh_>)
 VIA = {
@@ -223,6 +224,7 @@ VIA = {
     "mh_quant_batched": "hip.QuantBatch(",
     "mh_quant_mx_batched": "hip.QuantMxBatch(",
     "mh_transpose_u8_batched": "hip.TransposeBatch(",
+    "mh_reduce_ordered": "hip.OrderedReduce(",
 }
 
 GUARDED = {
@@ -240,6 +242,10 @@ GUARDED = {
     "mh_adamw", "mh_adamw_dev", "mh_scale_dev", "mh_zero_spans",
     "mh_gemm_fp8", "mh_gemm_mx", "mh_quant_batched", "mh_quant_mx_batched", "mh_transpose_u8_batched", "mh_fp8_update_scales",
     "mh_adamw_fp8",
+    "mh_reduce_ordered", "mh_colsum_partial", "mh_masked_loss_det", "mh_masked_loss_bands_det", "mh_unmask_token_grad_det",
+    "mh_unmask_token_grad_per_sample_det", "mh_embed_finish_bwd_det",
+    "mh_masked_loss_cs", "mh_masked_loss_bands_cs", "mh_gather_rows_bf16_cs", "mh_embed_finish_bwd_ends",
+    "mh_confusion_ce", "mh_confusion_bce", "mh_select_dates",
 }
 
 # The calls that touch no device buffer (sizes, version, error text) are exempt as such; at most MAX_OTHER_EXEMPT further names
@@ -253,5 +259,12 @@ EXEMPT = {
     "mh_groupnorm_partial_size": NO_DEVICE_BUFFER,
     "mh_layernorm_bwd_workspace": NO_DEVICE_BUFFER,
     "mh_attn_reduce_partial_rows": NO_DEVICE_BUFFER,
+    "mh_colsum_partial_rows": NO_DEVICE_BUFFER,
+    "mh_masked_loss_partial_size": NO_DEVICE_BUFFER,
+    "mh_embed_bwd_partial_rows": NO_DEVICE_BUFFER,
+    "mh_unmask_token_grad_partial_rows": NO_DEVICE_BUFFER,
+    "mh_masked_loss_cs_rows": NO_DEVICE_BUFFER,
+    "mh_gather_rows_cs_rows": NO_DEVICE_BUFFER,
+    "mh_embed_bwd_cs_rows": NO_DEVICE_BUFFER,
 }
 MAX_OTHER_EXEMPT = 6

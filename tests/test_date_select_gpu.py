@@ -1,4 +1,4 @@
-"""Median-date selection on the GPU (csrc/staging.hip, include/maestro_hip_staging.h) against the device-form numpy restatement
+"""Median-date selection on the GPU (csrc/staging.hip, include/maestro_hip.h) against the device-form numpy restatement
 of tests/date_select_ref.py and against the reference's recording (tests/golden/date_select.npz).
 
 Every call goes through ``run``: each operand sits in the middle of a poisoned allocation (tests/guards.py), the dates of a
@@ -44,6 +44,62 @@ def _guard_in(gs, arr, name):
     return gs.inp(torch.from_numpy(arr), name=name)
 
 
+def test_stager_selects_before_the_flips():
+    """``BatchStager.stage(batch, flags, select=...)`` on a two-modality batch = the selection followed by the reference's flips
+    (oracle.staging.transform_rasters) with the same flags; without ``select`` the call returns what it always did.  (Dense
+    operands: the one test of this file above the guard-band banner.)"""
+    from maestro_amd import hip
+    from maestro_amd.train.staging import BatchStager, DateSelect, window_plan
+    from oracle import staging as ost
+    dev = _dev()
+    rng = np.random.default_rng(21)
+    B = 4  # noqa: N806
+    s2 = make_batch(rng, np.uint16, 3, 8, 3, 5, 2)
+    s1 = make_batch(rng, np.float32, 2, 3, 2, 5, 0)
+    n_s2 = [s + 3 * w for s, w in zip(s2["t_start"], s2["t_win"])]
+    ts, tw = window_plan(n_s2, 3, s2["t_start"])
+    assert ts.tolist() == s2["t_start"] and tw.tolist() == s2["t_win"]
+    select = {"s2": DateSelect(3, mask_threshold=MASK_FLOOR + 0.5, norm_fac=5000.0), "s1": DateSelect(2, norm_fac=5.0)}
+    aerial = torch.rand(B, 1, 4, 12, 12)
+    batch = {"aerial": aerial, "aerial_dates": torch.zeros(B, 1, 3, dtype=torch.int16),
+             "s2": torch.from_numpy(s2["raw"].view(np.int16)).view(torch.uint16), "s2_dates": torch.from_numpy(s2["dates"]),
+             "s2_t_start": ts, "s2_t_win": tw, "s2_mask": torch.from_numpy(s2["mask"]),
+             "s1": torch.from_numpy(s1["raw"]), "s1_dates": torch.from_numpy(s1["dates"]),
+             "s1_t_start": torch.tensor(s1["t_start"], dtype=torch.int32), "s1_t_win": torch.tensor(s1["t_win"], dtype=torch.int32),
+             "label": torch.rand(B, 15)}
+    flags = torch.tensor([0, 3, 5, 7], dtype=torch.uint8)
+    stager = BatchStager(dev, rasters=["aerial", "s2", "s1"])
+    for _ in range(3):       # laps the pinned ring
+        out = stager.stage(batch, flags, select=select)
+    torch.cuda.synchronize()
+    assert set(out) == {"aerial", "aerial_dates", "s2", "s2_dates", "s1", "s1_dates", "label"}
+    want = {"s2": expect(s2, mask_floor=MASK_FLOOR, norm_fac=5000.0), "s1": expect(s1, norm_fac=5.0)}
+    for name, w in want.items():
+        assert out[name].dtype == torch.float32 and out[f"{name}_dates"].dtype == torch.int16
+        assert np.array_equal(out[f"{name}_dates"].cpu().numpy(), w[2]), name
+        for b in range(B):
+            flipped = ost.transform_rasters({name: w[1][b]}, int(flags[b]))[name]
+            assert out[name][b].cpu().numpy().tobytes() == flipped.tobytes(), (name, b)
+    # the wrapper on its own gives the un-flipped selection
+    direct, _, _ = hip.select_dates(batch["s1"].to(dev), batch["s1_dates"].to(dev), s1["t_start"], s1["t_win"], 2, norm_fac=5.0)
+    assert direct.cpu().numpy().tobytes() == want["s1"][1].tobytes()
+    for b in range(B):
+        assert np.array_equal(out["aerial"][b].cpu().numpy(), ost.transform_rasters({"a": aerial[b].numpy()}, int(flags[b]))["a"])
+    assert torch.equal(out["label"].cpu(), batch["label"])
+    # without `select`: today's behaviour, on a wire-format batch
+    wire = {"aerial": aerial, "aerial_dates": batch["aerial_dates"], "s1": torch.from_numpy(want["s1"][1]), "label": batch["label"]}
+    plain = stager.stage(wire, flags)
+    torch.cuda.synchronize()
+    assert set(plain) == set(wire)
+    for key in ("aerial", "s1"):
+        for b in range(B):
+            assert np.array_equal(plain[key][b].cpu().numpy(), ost.transform_rasters({"r": wire[key][b].numpy()}, int(flags[b]))["r"])
+    assert torch.equal(stager.stage(wire, None)["aerial"].cpu(), aerial) and torch.equal(plain["label"].cpu(), batch["label"])
+
+
+# ------------------------------------------------------------------------------------------------ guard bands (tests/guards.py)
+# The ledger of tests/guards.py counts the calls below this banner: every test below reaches the kernel through ``run``, whose
+# operands sit in a GuardSet.
 def run(dev, raw, dates, t_start, t_win, nd, mask=None, mask_floor=0, scores=None, log_scale=False, norm_fac=None):
     """hip.select_dates on guarded operands, bands checked -> (index, raster, dates) as numpy."""
     from maestro_amd import hip
@@ -318,55 +374,3 @@ def test_more_than_one_chunk_per_raster():
         want = expect(bt, mask_floor=MASK_FLOOR, norm_fac=10000.0)
         got = run(dev, bt["raw"], bt["dates"], bt["t_start"], bt["t_win"], 2, mask=bt["mask"], mask_floor=MASK_FLOOR, norm_fac=10000.0)
         assert np.array_equal(got[0], want[0]) and got[1].tobytes() == want[1].tobytes() and np.array_equal(got[2], want[2])
-
-
-def test_stager_selects_before_the_flips():
-    """``BatchStager.stage(batch, flags, select=...)`` on a two-modality batch = the selection followed by the reference's flips
-    (oracle.staging.transform_rasters) with the same flags; without ``select`` the call returns what it always did."""
-    from maestro_amd import hip
-    from maestro_amd.train.staging import BatchStager, DateSelect, window_plan
-    from oracle import staging as ost
-    dev = _dev()
-    rng = np.random.default_rng(21)
-    B = 4  # noqa: N806
-    s2 = make_batch(rng, np.uint16, 3, 8, 3, 5, 2)
-    s1 = make_batch(rng, np.float32, 2, 3, 2, 5, 0)
-    n_s2 = [s + 3 * w for s, w in zip(s2["t_start"], s2["t_win"])]
-    ts, tw = window_plan(n_s2, 3, s2["t_start"])
-    assert ts.tolist() == s2["t_start"] and tw.tolist() == s2["t_win"]
-    select = {"s2": DateSelect(3, mask_threshold=MASK_FLOOR + 0.5, norm_fac=5000.0), "s1": DateSelect(2, norm_fac=5.0)}
-    aerial = torch.rand(B, 1, 4, 12, 12)
-    batch = {"aerial": aerial, "aerial_dates": torch.zeros(B, 1, 3, dtype=torch.int16),
-             "s2": torch.from_numpy(s2["raw"].view(np.int16)).view(torch.uint16), "s2_dates": torch.from_numpy(s2["dates"]),
-             "s2_t_start": ts, "s2_t_win": tw, "s2_mask": torch.from_numpy(s2["mask"]),
-             "s1": torch.from_numpy(s1["raw"]), "s1_dates": torch.from_numpy(s1["dates"]),
-             "s1_t_start": torch.tensor(s1["t_start"], dtype=torch.int32), "s1_t_win": torch.tensor(s1["t_win"], dtype=torch.int32),
-             "label": torch.rand(B, 15)}
-    flags = torch.tensor([0, 3, 5, 7], dtype=torch.uint8)
-    stager = BatchStager(dev, rasters=["aerial", "s2", "s1"])
-    for _ in range(3):       # laps the pinned ring
-        out = stager.stage(batch, flags, select=select)
-    torch.cuda.synchronize()
-    assert set(out) == {"aerial", "aerial_dates", "s2", "s2_dates", "s1", "s1_dates", "label"}
-    want = {"s2": expect(s2, mask_floor=MASK_FLOOR, norm_fac=5000.0), "s1": expect(s1, norm_fac=5.0)}
-    for name, w in want.items():
-        assert out[name].dtype == torch.float32 and out[f"{name}_dates"].dtype == torch.int16
-        assert np.array_equal(out[f"{name}_dates"].cpu().numpy(), w[2]), name
-        for b in range(B):
-            flipped = ost.transform_rasters({name: w[1][b]}, int(flags[b]))[name]
-            assert out[name][b].cpu().numpy().tobytes() == flipped.tobytes(), (name, b)
-    # the wrapper on its own gives the un-flipped selection
-    direct, _, _ = hip.select_dates(batch["s1"].to(dev), batch["s1_dates"].to(dev), s1["t_start"], s1["t_win"], 2, norm_fac=5.0)
-    assert direct.cpu().numpy().tobytes() == want["s1"][1].tobytes()
-    for b in range(B):
-        assert np.array_equal(out["aerial"][b].cpu().numpy(), ost.transform_rasters({"a": aerial[b].numpy()}, int(flags[b]))["a"])
-    assert torch.equal(out["label"].cpu(), batch["label"])
-    # without `select`: today's behaviour, on a wire-format batch
-    wire = {"aerial": aerial, "aerial_dates": batch["aerial_dates"], "s1": torch.from_numpy(want["s1"][1]), "label": batch["label"]}
-    plain = stager.stage(wire, flags)
-    torch.cuda.synchronize()
-    assert set(plain) == set(wire)
-    for key in ("aerial", "s1"):
-        for b in range(B):
-            assert np.array_equal(plain[key][b].cpu().numpy(), ost.transform_rasters({"r": wire[key][b].numpy()}, int(flags[b]))["r"])
-    assert torch.equal(stager.stage(wire, None)["aerial"].cpu(), aerial) and torch.equal(plain["label"].cpu(), batch["label"])

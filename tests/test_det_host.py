@@ -1,4 +1,4 @@
-"""Deterministic mode without a GPU: the C ABI of include/maestro_hip_det.h (exports, argument checks of the ordered reduction),
+"""Deterministic mode without a GPU: the deterministic forms of include/maestro_hip.h (exports, argument checks of the ordered reduction),
 the numpy float32 emulation of its summation order -- shared with tests/test_det_kernels_gpu.py, and shown here to have teeth --
 and how the public surface resolves the ``deterministic`` switch."""
 
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.skipif(not LIB.exists(), reason="libmaestro_hip.so not 
 
 # ------------------------------------------------------------------------------------------------ the emulation
 def ordered_total(src: np.ndarray, chunk: int = ORDERED_ROWS, reverse: bool = False) -> np.ndarray:
-    """``job_total`` of include/maestro_hip_det.h for ``src`` float32 [rows, cols]: chunk sums (sequential, from +0) summed
+    """``job_total`` of mh_reduce_ordered (include/maestro_hip.h) for ``src`` float32 [rows, cols]: chunk sums (sequential, from +0) summed
     sequentially from +0, every add an IEEE float32 add (numpy float32 arrays add elementwise in float32).  ``chunk`` /
     ``reverse``: deliberately different orders, for the teeth tests."""
     src = np.ascontiguousarray(src, dtype=np.float32)
@@ -100,19 +100,16 @@ def lib():
     return handle
 
 
-def test_every_declared_entry_point_is_exported(lib):
-    header = (ROOT / "include" / "maestro_hip_det.h").read_text()
-    names = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", header))
-    assert {"mh_reduce_ordered", "mh_colsum_partial", "mh_colsum_partial_rows", "mh_masked_loss_det", "mh_masked_loss_bands_det",
-            "mh_masked_loss_partial_size", "mh_unmask_token_grad_det", "mh_unmask_token_grad_per_sample_det",
-            "mh_unmask_token_grad_partial_rows", "mh_embed_finish_bwd_det", "mh_embed_bwd_partial_rows"} <= names
-    missing = [n for n in sorted(names) if not hasattr(lib, n)]
-    assert not missing, f"declared in include/maestro_hip_det.h but not exported: {missing}"
+DET_NAMES = ("mh_reduce_ordered", "mh_colsum_partial", "mh_colsum_partial_rows", "mh_masked_loss_det", "mh_masked_loss_bands_det",
+             "mh_masked_loss_partial_size", "mh_unmask_token_grad_det", "mh_unmask_token_grad_per_sample_det",
+             "mh_unmask_token_grad_partial_rows", "mh_embed_finish_bwd_det", "mh_embed_bwd_partial_rows")
 
 
-def test_header_is_separate_from_the_guard_band_ledger():
-    main = (ROOT / "include" / "maestro_hip.h").read_text()
-    assert "mh_reduce_ordered" not in main and "_det(" not in main
+def test_det_entry_points_are_declared_and_exported(lib):
+    header = (ROOT / "include" / "maestro_hip.h").read_text()
+    assert set(DET_NAMES) <= set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", header))
+    missing = [n for n in DET_NAMES if not hasattr(lib, n)]
+    assert not missing, f"declared in include/maestro_hip.h but not exported: {missing}"
 
 
 def _table(rows):

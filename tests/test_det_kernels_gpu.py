@@ -1,4 +1,4 @@
-"""Deterministic-mode kernels on the GPU (include/maestro_hip_det.h): the ordered reduction bit for bit against the numpy
+"""Deterministic-mode kernels on the GPU (include/maestro_hip.h): the ordered reduction bit for bit against the numpy
 emulation of tests/test_det_host.py, and every atomic-free producer followed by its ordered reduce -- against fp64 under the
 fp32-accumulation bound of tests/numerics.py (``gemm_bound``: n addends in any order, 2^-23 per term on the sum of magnitudes),
 and bit-equal over three launches.  Operands sit between the poisoned guard bands of tests/guards.py.
@@ -62,6 +62,25 @@ def _three_launches(run, outputs):
             assert guards.bits_equal(a, b), "bits differ between launches"
 
 
+def test_ordered_reduce_descriptor_rejects_malformed_jobs(dev):
+    from maestro_amd import hip
+    src, dst = torch.zeros(8, 8, device=dev), torch.zeros(8, device=dev)
+    with pytest.raises(hip.HipExtensionError, match="does not fit"):
+        hip.OrderedReduce([(src, dst, 8, 8, 4)], dev)                     # cols > ld
+    with pytest.raises(hip.HipExtensionError, match="does not fit"):
+        hip.OrderedReduce([(src, dst, 9, 8, 8)], dev)                     # more rows than the buffer holds
+    with pytest.raises(hip.HipExtensionError, match="differ"):
+        hip.OrderedReduce([(src, dst, 8, 8, 8), (src, dst, 8, 4, 8)], dev)
+    with pytest.raises(hip.HipExtensionError, match="differ"):
+        hip.OrderedReduce([(src, dst, 8, 8, 8, False), (src, dst, 8, 8, 8, True)], dev)
+    with pytest.raises(hip.HipExtensionError, match="overlap"):
+        hip.OrderedReduce([(src, dst, 8, 8, 8), (src, dst[4:], 8, 4, 8)], dev)
+    with pytest.raises(hip.HipExtensionError, match="f32"):
+        hip.OrderedReduce([(src.to(BF16), dst, 8, 8, 8)], dev)
+
+
+# ------------------------------------------------------------------------------------------------ guard bands (tests/guards.py)
+# The ledger of tests/guards.py counts the calls below this banner: every test from here on keeps its operands in a GuardSet.
 # ------------------------------------------------------------------------------------------------ mh_reduce_ordered
 @pytest.mark.parametrize("rows,cols,ld", [(1, 4, 4), (16, 256, 256), (17, 260, 264), (33, 4, 12), (100, 516, 520)])
 def test_reduce_ordered_matches_the_emulation(dev, rows, cols, ld):
@@ -114,23 +133,6 @@ def test_reduce_ordered_two_chains_in_one_launch(dev):
     gs.check()
     assert np.array_equal(da[0].cpu().numpy().view(np.uint32), ordered_reduce_emulated(a).view(np.uint32))
     assert np.array_equal(db[0].cpu().numpy().view(np.uint32), ordered_reduce_emulated(b).view(np.uint32))
-
-
-def test_ordered_reduce_descriptor_rejects_malformed_jobs(dev):
-    from maestro_amd import hip
-    src, dst = torch.zeros(8, 8, device=dev), torch.zeros(8, device=dev)
-    with pytest.raises(hip.HipExtensionError, match="does not fit"):
-        hip.OrderedReduce([(src, dst, 8, 8, 4)], dev)                     # cols > ld
-    with pytest.raises(hip.HipExtensionError, match="does not fit"):
-        hip.OrderedReduce([(src, dst, 9, 8, 8)], dev)                     # more rows than the buffer holds
-    with pytest.raises(hip.HipExtensionError, match="differ"):
-        hip.OrderedReduce([(src, dst, 8, 8, 8), (src, dst, 8, 4, 8)], dev)
-    with pytest.raises(hip.HipExtensionError, match="differ"):
-        hip.OrderedReduce([(src, dst, 8, 8, 8, False), (src, dst, 8, 8, 8, True)], dev)
-    with pytest.raises(hip.HipExtensionError, match="overlap"):
-        hip.OrderedReduce([(src, dst, 8, 8, 8), (src, dst[4:], 8, 4, 8)], dev)
-    with pytest.raises(hip.HipExtensionError, match="f32"):
-        hip.OrderedReduce([(src.to(BF16), dst, 8, 8, 8)], dev)
 
 
 # ------------------------------------------------------------------------------------------------ K-slice slab GEMMs

@@ -1,6 +1,6 @@
 """The ends of the pretraining step's backward (pixelify head, final LayerNorms, enc_to_dec, patch embed) in their batched form:
 weight gradients as problems of the grouped TN launch, bias / LayerNorm side reductions as partial rows summed by one batched
-column sum, the patch-embed backward through the position map (include/maestro_hip_ends.h).
+column sum, the patch-embed backward through the position map (include/maestro_hip.h).
 
 Bounds are derived, not observed.  u = 2^-24 (fp32 unit roundoff), and:
   * an fp32 sum of n terms, in ANY order (wave tree, LDS, row chunks, atomics):  |err| <= 2 n u sum|term|, sum|term| in fp64
@@ -46,6 +46,8 @@ def _assert_colsum(name, got, stored, n_terms):
     assert bool((err <= bound).all()), (name, (err / bound).max().item())
 
 
+# ================================================================================================ guard bands (tests/guards.py)
+# The ledger of tests/guards.py counts the calls below this banner: the kernel tests from here on keep their operands in a GuardSet.
 # ================================================================================================ 1. LayerNorm backward, new forms
 def _ln_reference(dy, x, gamma, mean, rstd):
     """fp64 LayerNorm backward on the operands the kernel reads; rows = leading dimension.  Returns dx and its bound, the three
@@ -180,10 +182,14 @@ def test_masked_loss_leaves_its_bias_gradient_as_partial_rows(bands, all_visible
         rows = hip.masked_loss_cs_rows(B, Lm)
         cs = gs.out((rows, K), F32, name="cs_partial") if fused else None
         args = (B, Lm, Lgroup, tok_off, K, p) + ((tgt_C, tgt_c0, n_g) if bands else ())
-        if fused:
-            (hip.masked_loss_bands_cs if bands else hip.masked_loss_cs)(rec, tgt, msk, cnt, 0.7, acc, drec, cs, *args)
+        if fused and bands:
+            hip.masked_loss_bands_cs(rec, tgt, msk, cnt, 0.7, acc, drec, cs, *args)
+        elif fused:
+            hip.masked_loss_cs(rec, tgt, msk, cnt, 0.7, acc, drec, cs, *args)
+        elif bands:
+            hip.masked_loss_bands(rec, tgt, msk, cnt, 0.7, acc, drec, *args)
         else:
-            (hip.masked_loss_bands if bands else hip.masked_loss)(rec, tgt, msk, cnt, 0.7, acc, drec, *args)
+            hip.masked_loss(rec, tgt, msk, cnt, 0.7, acc, drec, *args)
         gs.check()
         outs.append((acc.clone(), drec.clone(), cs))
     (loss0, drec0, _), (loss1, drec1, cs) = outs

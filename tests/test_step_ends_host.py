@@ -1,7 +1,7 @@
 """Properties of the step-ends kernels that need no GPU: the straight-line LayerNorm backward forms for the final norms are in
 the library without scratch, issue every load of a wave before their first ``s_waitcnt vmcnt`` and never wait for ``vmcnt(0)``
-inside the pipeline (the helpers and the method are those of tests/test_kernel_resources.py); the new entry points are declared
-in their own header, exported by the library and bound."""
+inside the pipeline (the helpers and the method are those of tests/test_kernel_resources.py); the step-end entry points are declared
+in include/maestro_hip.h, exported by the library and bound."""
 
 import re
 import shutil
@@ -51,6 +51,10 @@ def test_final_layernorm_forms_issue_their_loads_before_the_first_wait():
             assert not any("s_waitcnt vmcnt(0)" in ln for ln in hits[0]), (nv, f32)
 
 
+ENDS_NAMES = ("mh_masked_loss_cs_rows", "mh_masked_loss_cs", "mh_masked_loss_bands_cs", "mh_gather_rows_cs_rows",
+              "mh_gather_rows_bf16_cs", "mh_embed_bwd_cs_rows", "mh_embed_finish_bwd_ends")
+
+
 def test_ends_entry_points_are_declared_exported_and_bound():
     import ctypes
 
@@ -58,14 +62,11 @@ def test_ends_entry_points_are_declared_exported_and_bound():
     from maestro_amd.csrc.build import LIB
     if not LIB.exists():
         pytest.skip("needs the built library")
-    header = (ROOT / "include" / "maestro_hip_ends.h").read_text()
-    names = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", header))
-    assert len(names) == 7
-    main = (ROOT / "include" / "maestro_hip.h").read_text()
+    declared = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", (ROOT / "include" / "maestro_hip.h").read_text()))
     handle = ctypes.CDLL(str(LIB))
     binding = (ROOT / "maestro_amd" / "hip.py").read_text()
-    for n in names:
+    for n in ENDS_NAMES:
+        assert n in declared, f"{n} is not declared in include/maestro_hip.h"
         assert hasattr(handle, n), n
-        assert n not in main, f"{n} belongs to maestro_hip_ends.h alone"
         assert n in binding, f"{n} is not bound in maestro_amd/hip.py"
     assert hip.COLSUM_ROWS == 16
