@@ -28,7 +28,7 @@ from torch import nn
 
 from maestro_amd import hip
 from maestro_amd.fp8 import mx_scale_cols, resolve_scaling
-from maestro_amd.layers.utils import draw_struct_masks
+from maestro_amd.layers.utils import check_device_mask_config, draw_struct_masks, mask_draw_jobs
 
 F32, BF16, I32, U8 = torch.float32, torch.bfloat16, torch.int32, torch.uint8
 _NEVER = object()
@@ -544,6 +544,16 @@ def resolve_deterministic(flag: bool | None = None) -> bool:
     return bool(flag)
 
 
+def resolve_mask_rng(mode: str | None = None) -> str:
+    """The ``mask_rng`` switch of the public surface: an explicit "host" / "device" wins; None reads ``MAESTRO_MASK_RNG`` (unset =
+    "host": the reference's draw order on the host generator).  Anything else is a ``ValueError``."""
+    if mode is None:
+        mode = os.environ.get("MAESTRO_MASK_RNG") or "host"
+    if mode not in ("host", "device"):
+        raise ValueError(f"mask_rng={mode!r}: expected 'host' or 'device'")
+    return mode
+
+
 def training_warm_passes() -> int:
     """Start-up passes a TRAINING entry point asks its engine for (see ``EngineBase.warm_passes``)."""
     return 0 if _PROCESS_WARMED else max(0, int(os.environ.get("MAESTRO_WARM_PASSES", "6")))
@@ -900,7 +910,8 @@ class EngineBase:
 # ======================================================================================= the engine
 class MAEEngine(EngineBase):
     def __init__(self, model, batch_size: int, device, loss: str = "l2_norm", dtype: str = "bf16",
-                 fp8_scaling: str | None = None, deterministic: bool = False) -> None:
+                 fp8_scaling: str | None = None, deterministic: bool = False, mask_rng: str | None = None,
+                 mask_seed: int = 0, row_base: int = 0) -> None:
         """``fp8_scaling`` (dtype "fp8" only): "tensor" (per-tensor delayed scaling) or "mx" (OCP MX block scales); None reads
         ``MAESTRO_FP8_SCALING`` (default "tensor").  A numeric-format choice like ``dtype`` (maestro_amd/fp8.py).
 
@@ -908,8 +919,20 @@ class MAEEngine(EngineBase):
         hence the parameters after AdamW) -- eager launches, capture runs and graph replays, one stream or several.  No
         floating-point atomics: every reduction of the step leaves partial rows in private buffers and one ordered reduce per
         phase (``hip.OrderedReduce``) finishes them in a fixed order; kernels and tiles are chosen from shapes alone
-        ("Deterministic mode").  Not with dtype "fp8", an overlapped optimizer or a gradient hook."""
+        ("Deterministic mode").  Not with dtype "fp8", an overlapped optimizer or a gradient hook.
+
+        ``mask_rng``: "host" (default; None reads ``MAESTRO_MASK_RNG``) draws the masks of a step on the host generator in the
+        reference's order and uploads them; "device" draws them with one ``mh_mask_draw`` launch as a pure function of
+        ``(mask_seed, mask_step, row_base + sample)`` (include/maestro_hip_rng.h): no host arithmetic, no upload, and the same
+        masks after a resume or under another split of the global batch.  ``mask_step`` is a public, settable int that every
+        drawing forward advances by one; ``row_base`` (settable too) is the global index of this rank's first sample.  A
+        forward that is handed ``noise=`` / ``struct=`` takes the host path for that call.  Not with ``tie_order="torch"``."""
         self.deterministic = bool(deterministic)
+        self.mask_rng = resolve_mask_rng(mask_rng)         # (the refusals come before the device check: ValueErrors on any machine)
+        self.mask_seed, self.mask_step, self.row_base = int(mask_seed), 0, int(row_base)
+        if not 0 <= self.mask_seed < 1 << 64:
+            raise ValueError(f"mask_seed={mask_seed!r}: an unsigned 64-bit value expected")
+        self._draw_depth = 0                                # > 0 inside the start-up passes of a drawing forward: same step, no advance
         if self.deterministic and dtype == "fp8":
             raise ValueError("deterministic=True is not available with dtype='fp8' (the amax / scale bookkeeping is not covered)")
         if loss not in ("l1", "l2", "l1_norm", "l2_norm"):
@@ -918,6 +941,10 @@ class MAEEngine(EngineBase):
             raise ValueError(f"Invalid compute dtype {dtype!r} (bf16, fp8)")
         scaling = resolve_scaling(fp8_scaling)         # (before the device check: a bad value is a ValueError on any machine)
         self.fp8_scaling = scaling if dtype == "fp8" else None
+        if self.mask_rng == "device":
+            if os.environ.get("MAESTRO_TIE_ORDER", "stable") == "torch":
+                raise ValueError("mask_rng='device' excludes tie_order='torch' (its two sorts are host sorts of host draws)")
+            check_device_mask_config(model.group_specs.values())
         device = torch.device(device)
         if device.type != "cuda":
             raise hip.HipExtensionError("MAEEngine needs a GPU device; the MAE hot path has no CPU fallback")
@@ -1153,11 +1180,23 @@ class MAEEngine(EngineBase):
                 segs.append((g.name, key, dt, off, n, (g.Beff, g.L)))
                 off += (n + 255) // 256 * 256
         self._mask_dev = torch.zeros(off, dtype=U8, device=self.device)
+        self._mask_segs = segs
+        for name, key, dt, o, n, shape in segs:
+            self.gb[name][key] = self._mask_dev[o: o + n].view(dt).view(shape)
+        self._mask_stage = self._mask_host = self._upload_stream = self._mask_draw = None
+        if self.mask_rng == "device":
+            # the live buffer only: mh_mask_draw writes it in place; the upload ring is built if a forward is ever handed host draws
+            self._mask_draw = hip.MaskDraw(mask_draw_jobs(self.groups, self.mods, self.B),
+                                           {g.name: (self.gb[g.name]["noise"], self.gb[g.name]["struct"]) for g in self.groups}, self.device)
+        else:
+            self._alloc_mask_ring()
+
+    def _alloc_mask_ring(self) -> None:
+        off = self._mask_dev.numel()
         self._mask_stage = [torch.zeros(off, dtype=U8, device=self.device) for _ in range(RING)]
         self._mask_host = [torch.zeros(off, dtype=U8).pin_memory() for _ in range(RING)]
         self._upload_stream = torch.cuda.Stream(device=self.device)
-        for name, key, dt, o, n, shape in segs:
-            self.gb[name][key] = self._mask_dev[o: o + n].view(dt).view(shape)
+        for name, key, dt, o, n, shape in self._mask_segs:
             self.gb[name][key + "_h"] = [h[o: o + n].view(dt).view(shape) for h in self._mask_host]
 
     def _pack_conv_weights(self, fp8_done: bool = False) -> None:
@@ -1243,16 +1282,33 @@ class MAEEngine(EngineBase):
             if self.fp8 is not None:
                 self.fp8._w_ready = False  # ... possibly wholesale: rebuild the e4m3 scales from scratch
             self._pack_conv_weights()
-        if noise is None or struct is None:
+        device_draw = self.mask_rng == "device" and noise is None and struct is None
+        if device_draw:
+            if self.tie_order == "torch":
+                raise ValueError("mask_rng='device' excludes tie_order='torch' (its two sorts are host sorts of host draws)")
+        elif noise is None or struct is None:
             n2, s2 = self.draw_masks()
             noise = noise if noise is not None else n2
             struct = struct if struct is not None else s2
 
         def one_pass():
-            self.forward(batch, noise=noise, struct=struct)
+            self._draw_depth += 1         # (device draws: the passes draw this step's masks again, mask_step does not move)
+            try:
+                self.forward(batch, noise=noise, struct=struct)
+            finally:
+                self._draw_depth -= 1
             self.zero_grad()
             self.backward()
         self._first_step_passes(one_pass)
+        if device_draw:
+            # one launch on the main stream ahead of the forward segment, eager: seed, step and row_base are arguments of THIS
+            # call, so a captured forward replays with whatever the launch in front of it drew
+            self._mask_draw.launch(self.mask_seed, self.mask_step, self.row_base)
+            if self._draw_depth == 0:
+                self.mask_step += 1
+        elif self._mask_host is None:
+            self._alloc_mask_ring()       # device mode handed host draws: today's path for this call
+        # (device draws keep the ring of EVENTS below and nothing else of it: the host stays at most RING steps ahead of the GPU)
         # host -> pinned ring slot -> device (outside any graph).  A slot is reused every RING steps; only then do we wait
         # for the async copies that last read it (the host may run several steps ahead of the GPU, but a per-step
         # hipEventSynchronize was measured to wake up ~10 ms late and starve the queue).
@@ -1262,7 +1318,7 @@ class MAEEngine(EngineBase):
             t0 = time.perf_counter()
             self._h2d_done[slot].synchronize()   # back-pressure: only blocks when the host runs >= RING steps ahead
             self.host_wait_s += time.perf_counter() - t0
-        for g in self.groups:
+        for g in () if device_draw else self.groups:
             gbuf = self.gb[g.name]
             nh, sh = gbuf["noise_h"][slot], gbuf["struct_h"][slot]
             n_g, s_g = self._rows_of(noise, g), self._rows_of(struct, g).reshape(g.Beff, g.L)
@@ -1274,13 +1330,14 @@ class MAEEngine(EngineBase):
         # waits for it with an event and moves it into the (graph-visible) mask buffers with one device -> device copy (round 5: one
         # pinned copy per step instead of two per group; end of step t -> first forward kernel of step t + 1: 28 -> 23 us by HIP
         # events, scripts/r05_boundary.py.  The ~90 us gap that rocprofv3 traces show at this boundary is the profiler's own).
-        main = torch.cuda.current_stream()
-        with torch.cuda.stream(self._upload_stream):
-            self._mask_stage[slot].copy_(self._mask_host[slot], non_blocking=True)
-            up = torch.cuda.Event()
-            up.record(self._upload_stream)
-        main.wait_event(up)
-        self._mask_dev.copy_(self._mask_stage[slot], non_blocking=True)
+        if not device_draw:
+            main = torch.cuda.current_stream()
+            with torch.cuda.stream(self._upload_stream):
+                self._mask_stage[slot].copy_(self._mask_host[slot], non_blocking=True)
+                up = torch.cuda.Event()
+                up.record(self._upload_stream)
+            main.wait_event(up)
+            self._mask_dev.copy_(self._mask_stage[slot], non_blocking=True)
         if self._opt is not None:      # overlapped optimizer: this step's scalars (or "nothing pending") ride the same ring
             hh = self._opt_hyper_h[slot]
             hh.copy_(torch.tensor(self._opt_pending if self._opt_pending is not None else [0.0] * 5, dtype=F32))
@@ -1289,6 +1346,9 @@ class MAEEngine(EngineBase):
         ev = torch.cuda.Event()
         ev.record()
         self._h2d_done[slot] = ev
+        return self._forward_segment(batch)
+
+    def _forward_segment(self, batch: dict) -> torch.Tensor:
         batch = self._stage_inputs(batch)
         with self._tuning_pass("forward"):
             # the loss launch writes the pixelify bias gradient's partial rows only where the backward will sum them (not under

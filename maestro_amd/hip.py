@@ -54,6 +54,8 @@ def lib() -> ctypes.CDLL:
         _lib.mh_select_dates.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ctypes.c_long, ci, ci,
                                          ctypes.c_float, vp]               # input staging
         _lib.mh_select_dates.restype = ci
+        _lib.mh_mask_draw.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_longlong, vp]   # device-side draws
+        _lib.mh_mask_draw.restype = ci                                      # (include/maestro_hip_rng.h)
     return _lib
 
 
@@ -504,6 +506,73 @@ class OrderedReduce:
                                        stream()), "mh_reduce_ordered")
         if ev is not None:
             ev[1].record()
+
+
+# ---- device-side mask draws (include/maestro_hip_rng.h)
+MASK_MAX_L, MASK_MAX_STREAMS = 8192, 4096     # MH_MASK_MAX_L, MH_MASK_MAX_STREAMS
+
+
+class _MhMaskSeg(ctypes.Structure):
+    _fields_ = [("tok_off", ctypes.c_int), ("D", ctypes.c_int), ("L", ctypes.c_int), ("gi", ctypes.c_int), ("G", ctypes.c_int),
+                ("stream", ctypes.c_int), ("p_mod", ctypes.c_float), ("p_bands", ctypes.c_float), ("p_dates", ctypes.c_float),
+                ("p_loc", ctypes.c_float)]
+
+
+class _MhMaskJob(ctypes.Structure):
+    _fields_ = [("noise", ctypes.c_void_p), ("strct", ctypes.c_void_p), ("Beff", ctypes.c_int), ("L", ctypes.c_int),
+                ("noise_stream", ctypes.c_int), ("noise_rpb", ctypes.c_int), ("struct_rpb", ctypes.c_int),
+                ("row_div", ctypes.c_int), ("row_mul", ctypes.c_int), ("row_add", ctypes.c_int), ("seg0", ctypes.c_int),
+                ("n_segs", ctypes.c_int)]
+
+
+class MaskDraw:
+    """Descriptor tables (built once: the mask buffers are static) for ``mh_mask_draw``: all groups' structural masks and noise
+    of a step in one launch.  ``jobs``: the dicts of ``layers.utils.mask_draw_jobs``; ``bufs``: ``{group: (noise f32 [Beff, L],
+    struct u8 [Beff, L])}``, dense device tensors.  ``launch(seed, step, row_base)``: by-value, nothing of a step is in the tables."""
+
+    def __init__(self, jobs, bufs, device) -> None:
+        if not jobs:
+            raise HipExtensionError("MaskDraw: no jobs")
+        n_segs = sum(len(j["segs"]) for j in jobs)
+        jarr, sarr, k = (_MhMaskJob * len(jobs))(), (_MhMaskSeg * max(n_segs, 1))(), 0
+        self.keep = []
+        for i, j in enumerate(jobs):
+            noise, struct = bufs[j["name"]]
+            shape = (j["Beff"], j["L"])
+            if not (isinstance(noise, torch.Tensor) and isinstance(struct, torch.Tensor)) or noise.dtype != torch.float32 \
+                    or struct.dtype != torch.uint8 or not noise.is_cuda or not struct.is_cuda:
+                raise HipExtensionError(f"MaskDraw job {i}: noise f32 and struct u8 device tensors expected")
+            if tuple(noise.shape) != shape or tuple(struct.shape) != shape or not noise.is_contiguous() or not struct.is_contiguous():
+                raise HipExtensionError(f"MaskDraw job {i}: dense [{shape[0]}, {shape[1]}] buffers expected")
+            if not 1 <= j["L"] <= MASK_MAX_L:
+                raise HipExtensionError(f"MaskDraw job {i}: L {j['L']} (1 ... {MASK_MAX_L})")
+            jarr[i] = _MhMaskJob(noise.data_ptr(), struct.data_ptr(), j["Beff"], j["L"], j["noise_stream"], j["noise_rpb"],
+                                 j["struct_rpb"], j["row_div"], j["row_mul"], j["row_add"], k, len(j["segs"]))
+            for s in j["segs"]:
+                sarr[k] = _MhMaskSeg(s["tok_off"], s["D"], s["L"], s["gi"], s["G"], s["stream"], *s["p"])
+                k += 1
+            self.keep += [noise, struct]                     # the descriptors hold raw pointers
+        self.jobs_host, self.segs_host = jarr, sarr
+        self.jobs = torch.frombuffer(bytearray(bytes(jarr)), dtype=torch.uint8).to(device)
+        self.segs = torch.frombuffer(bytearray(bytes(sarr)), dtype=torch.uint8).to(device)
+        self.n, self.n_segs = len(jobs), n_segs
+        self.nbytes = 5.0 * sum(j["Beff"] * j["L"] for j in jobs)      # algorithmic: f32 noise + u8 struct written
+
+    def launch(self, seed: int, step: int, row_base: int = 0) -> None:
+        if not 0 <= int(seed) < 1 << 64:
+            raise HipExtensionError(f"MaskDraw: seed {seed} is not an unsigned 64-bit value")
+        if not -(1 << 63) <= int(step) < 1 << 63 or not -(1 << 63) <= int(row_base) < 1 << 63:
+            raise HipExtensionError(f"MaskDraw: step {step} / row_base {row_base} out of range")
+        _check(lib().mh_mask_draw(ctypes.byref(self.jobs_host), ptr(self.jobs), _I(self.n), ctypes.byref(self.segs_host),
+                                  ptr(self.segs), _I(self.n_segs), ctypes.c_uint64(int(seed)), ctypes.c_longlong(int(step)),
+                                  ctypes.c_longlong(int(row_base)), stream()), "mh_mask_draw")
+
+
+def mask_draw_reference(groups, mods, B, seed, step, row_base=0):  # noqa: N803
+    """What ``MaskDraw.launch(seed, step, row_base)`` writes, computed in numpy on the host: ``(noise, struct)`` dicts shaped like
+    ``MAEEngine.draw_masks()`` (the restatement lives next to the host drawer, ``layers.utils.mask_draw_reference``)."""
+    from maestro_amd.layers.utils import mask_draw_reference as reference
+    return reference(groups, mods, B, seed, step, row_base)
 
 
 def colsum_partial_rows(M) -> int:  # noqa: N803

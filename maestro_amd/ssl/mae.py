@@ -234,30 +234,37 @@ class MAE(nn.Module):
 
     # ------------------------------------------------------------------------------------------ engine plumbing
     def engine(self, batch_size: int, device=None, loss: str = "l2_norm", dtype: str | None = None,
-               fp8_scaling: str | None = None, deterministic: bool | None = None):
+               fp8_scaling: str | None = None, deterministic: bool | None = None, mask_rng: str | None = None,
+               mask_seed: int | None = None):
         """Return (building on first use / batch-size change) the HIP step engine bound to these parameters.  ``dtype``:
         "bf16" (default) or "fp8" (e4m3 forward GEMMs, maestro_amd/fp8.py); None keeps the current engine's / MAESTRO_DTYPE.
         ``fp8_scaling`` (fp8 only): "tensor" or "mx"; None keeps the current fp8 engine's / MAESTRO_FP8_SCALING.
         ``deterministic``: bit-reproducible steps without floating-point atomics (``MAEEngine``); None reads
-        ``MAESTRO_DETERMINISTIC`` ("1" = on).  A change of the flag rebuilds the engine, as a change of ``dtype`` does."""
+        ``MAESTRO_DETERMINISTIC`` ("1" = on).  A change of the flag rebuilds the engine, as a change of ``dtype`` does.
+        ``mask_rng``: "host" or "device" (``MAEEngine``); None reads ``MAESTRO_MASK_RNG`` (unset = "host").  ``mask_seed``: the
+        64-bit seed of the device draws; None keeps the current engine's (0 for a new one).  A change of either rebuilds the engine."""
         import os
 
-        from maestro_amd.engine import MAEEngine, resolve_deterministic
+        from maestro_amd.engine import MAEEngine, resolve_deterministic, resolve_mask_rng
         from maestro_amd.fp8 import resolve_scaling
 
         device = torch.device(device) if device is not None else next(self.parameters()).device
         if dtype is None:
             dtype = self._engine.dtype if self._engine is not None else os.environ.get("MAESTRO_DTYPE", "bf16")
         det = resolve_deterministic(deterministic)
+        rng = resolve_mask_rng(mask_rng)
+        if mask_seed is None:
+            mask_seed = self._engine.mask_seed if self._engine is not None else 0
         scaling = None
         if dtype == "fp8":
             keep = self._engine is not None and self._engine.fp8_scaling is not None and fp8_scaling is None
             scaling = self._engine.fp8_scaling if keep else resolve_scaling(fp8_scaling)
         if self._engine is None or self._engine.B != batch_size or self._engine.loss != loss \
                 or self._engine.device != device or self._engine.dtype != dtype or self._engine.fp8_scaling != scaling \
-                or self._engine.deterministic != det:
+                or self._engine.deterministic != det or self._engine.mask_rng != rng or self._engine.mask_seed != int(mask_seed):
             self._sup_engine = None
-            self._engine = MAEEngine(self, batch_size, device, loss=loss, dtype=dtype, fp8_scaling=scaling, deterministic=det)
+            self._engine = MAEEngine(self, batch_size, device, loss=loss, dtype=dtype, fp8_scaling=scaling, deterministic=det,
+                                     mask_rng=rng, mask_seed=mask_seed)
         return self._engine
 
     def sup_engine(self, batch_size: int, device=None, phase: str = "finetune", deterministic: bool | None = None):

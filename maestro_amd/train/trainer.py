@@ -34,8 +34,13 @@ class PretrainLoop:
                  betas=(0.9, 0.99), weight_decay: float = 0.01, total_steps: int = 1000, world_size: int = 1,
                  final_factor: float = 1e7, bucket_mb: int = 64, exchange: bool | None = None,
                  accumulate: int = 1, overlap_optimizer: bool = False, bucket_dtype=None, dtype: str | None = None,
-                 exchange_mode: str | None = None, fp8_scaling: str | None = None, deterministic: bool | None = None) -> None:
-        """``deterministic``: bit-reproducible steps (``MAEEngine``; None reads ``MAESTRO_DETERMINISTIC``); excludes a gradient
+                 exchange_mode: str | None = None, fp8_scaling: str | None = None, deterministic: bool | None = None,
+                 mask_rng: str | None = None, mask_seed: int = 0, row_base: int | None = None) -> None:
+        """``mask_rng`` ("host" / "device"; None reads ``MAESTRO_MASK_RNG``), ``mask_seed``: where the masks of a step are drawn
+        (``MAEEngine``).  Device draws are a function of ``(mask_seed, step, row_base + sample)``: ``row_base`` is the global index
+        of this rank's first sample (default ``rank * batch_size``), and ``state_dict()`` carries ``mask_step`` / ``mask_seed`` so
+        that a resumed run sees the masks of the uninterrupted one.
+        ``deterministic``: bit-reproducible steps (``MAEEngine``; None reads ``MAESTRO_DETERMINISTIC``); excludes a gradient
         exchange, ``overlap_optimizer`` and ``dtype="fp8"``.  ``exchange_mode``: "all_reduce" (default; ``MAESTRO_EXCHANGE`` overrides) -- every bucket is all-reduced, every rank runs
         the whole AdamW; "rs_ag" -- every bucket is reduce-scattered, a rank updates its 1 / world share of every bucket and the
         updated fp32 masters are all-gathered (``GradSync`` / ``FusedAdamW.step_sharded``).  ``fp8_scaling`` (with
@@ -49,7 +54,12 @@ class PretrainLoop:
             if exchange or (exchange is None and world_size > 1):
                 raise ValueError("deterministic=True excludes a gradient exchange (the order of the cross-rank sum is the "
                                  "collective library's)")
-        self.engine = model.engine(batch_size, device, loss=loss, dtype=dtype, fp8_scaling=fp8_scaling, deterministic=deterministic)
+        self.engine = model.engine(batch_size, device, loss=loss, dtype=dtype, fp8_scaling=fp8_scaling, deterministic=deterministic,
+                                   mask_rng=mask_rng, mask_seed=mask_seed)
+        if row_base is None:
+            import torch.distributed as dist
+            row_base = (dist.get_rank() if dist.is_available() and dist.is_initialized() else 0) * batch_size
+        self.engine.row_base = int(row_base)
         self.engine.warm_passes = training_warm_passes()     # a training entry point: start-up passes on (engine.py: warm_passes)
         if overlap_optimizer and self.engine.fp8 is not None:
             raise ValueError("overlap_optimizer is not available with dtype='fp8' (the e4m3 weight shadows are rebuilt after the update)")
@@ -91,8 +101,11 @@ class PretrainLoop:
         ``if rank == 0: save(loop.state_dict())`` is safe.  Under ``rs_ag`` every rank calls ``gather_state()`` first; an
         ungathered sharded state is refused (``FusedAdamW.state_dict``) instead of hanging in a one-rank all-gather."""
         self.flush()
-        return {"optimizer": self.opt.state_dict(), "params": self.engine.store.flat.detach().clone(), "it": self.it,
-                "exchange_mode": self.exchange_mode, "world": self.world}
+        sd = {"optimizer": self.opt.state_dict(), "params": self.engine.store.flat.detach().clone(), "it": self.it,
+              "exchange_mode": self.exchange_mode, "world": self.world}
+        if self.engine.mask_rng == "device":      # the draws of step t are a function of these two (and of the row index)
+            sd.update(mask_step=self.engine.mask_step, mask_seed=self.engine.mask_seed)
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Restores moments, step counter and -- when the checkpoint carries them -- the fp32 masters with every derived copy
@@ -101,6 +114,8 @@ class PretrainLoop:
         from maestro_amd.train.ddp import resync_engine
         self.opt.load_state_dict(sd["optimizer"])
         self.it = sd["it"]
+        if self.engine.mask_rng == "device" and "mask_step" in sd:
+            self.engine.mask_step, self.engine.mask_seed = int(sd["mask_step"]), int(sd["mask_seed"])
         if sd.get("params") is not None:
             self.engine.store.flat.copy_(sd["params"])
             resync_engine(self.engine)
