@@ -295,30 +295,43 @@ extern "C" int mh_scale_dev(float* x, long n, const float* scale, void* stream) 
     return 0;
 }
 
+// Host side of the six masked-loss entries over masked_loss_kernel<DET, CS>: the shared checks, rows per wave, grid and launch.
+// ``name``: the entry's own name, for its messages.  ``pointers``: the entry's required pointers are all there.  ``ppc_cap``: > 0 in
+// the CS entries (a lane keeps its columns' sums in registers).  ``window`` = {tgt_C, tgt_c0, n_g}: the band window of the *_bands
+// entries, whose denominator counts elements; nullptr: the plain case.  The entries younger than the first two also refuse B, Lm <= 0.
+template <bool DET, bool CS>
+static int launch_masked_loss(const char* name, bool pointers, int ppc_cap, const int* window, const float* rec, const float* target,
+                              const uint8_t* mask_group, const int* n_masked, float weight, float* acc, void* drec, float* cs_partial,
+                              int B, int Lm, int Lgroup, int tok_off, int PPC, int p, void* stream) {
+    MH_CHECK_ARG(pointers, "%s: null pointer", name);
+    const bool ok = ((!DET && !CS) || (B > 0 && Lm > 0)) && (p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup;
+    if (ppc_cap > 0)
+        MH_CHECK_ARG(ok && PPC > 0 && PPC <= ppc_cap && tok_off >= 0, "%s: bad arguments (PPC %% 4 == 0, PPC <= %d)", name, ppc_cap);
+    MH_CHECK_ARG(ok, "%s: bad arguments", name);
+    const int tgt_C = window ? window[0] : 1, tgt_c0 = window ? window[1] : 0, n_g = window ? window[2] : 1;
+    MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "%s: band window [%d, %d) of %d", name, tgt_c0,
+                 tgt_c0 + n_g, tgt_C);
+    const int rpw = loss_rows_per_wave((long)B * Lm);
+    hipLaunchKernelGGL((masked_loss_kernel<DET, CS>), dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target,
+                       mask_group, n_masked, weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, window ? 1 : 0,
+                       rpw, cs_partial);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int mh_masked_loss(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked,
                               float weight, float* acc, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC, int p,
                               void* stream) {
-    MH_CHECK_ARG(rec && target && mask_group && n_masked && acc, "mh_masked_loss: null pointer");
-    MH_CHECK_ARG((p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss: bad arguments");
-    const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL(masked_loss_kernel<false>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target, mask_group, n_masked,
-                       weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, 1, 0, 1, 0, rpw);
-    MH_LAUNCH_CHECK();
-    return 0;
+    return launch_masked_loss<false, false>("mh_masked_loss", rec && target && mask_group && n_masked && acc, 0, nullptr, rec, target,
+                                            mask_group, n_masked, weight, acc, drec, nullptr, B, Lm, Lgroup, tok_off, PPC, p, stream);
 }
 
 extern "C" int mh_masked_loss_bands(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems,
                                     float weight, float* acc, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC, int p,
                                     int tgt_C, int tgt_c0, int n_g, void* stream) {
-    MH_CHECK_ARG(rec && target && mask_group && n_elems && acc, "mh_masked_loss_bands: null pointer");
-    MH_CHECK_ARG((p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss_bands: bad arguments");
-    MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "mh_masked_loss_bands: band window [%d, %d) of %d",
-                 tgt_c0, tgt_c0 + n_g, tgt_C);
-    const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL(masked_loss_kernel<false>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target, mask_group, n_elems,
-                       weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw);
-    MH_LAUNCH_CHECK();
-    return 0;
+    const int window[3] = {tgt_C, tgt_c0, n_g};
+    return launch_masked_loss<false, false>("mh_masked_loss_bands", rec && target && mask_group && n_elems && acc, 0, window, rec, target,
+                                            mask_group, n_elems, weight, acc, drec, nullptr, B, Lm, Lgroup, tok_off, PPC, p, stream);
 }
 
 extern "C" int mh_masked_loss_partial_size(int B, int Lm) {
@@ -329,27 +342,18 @@ extern "C" int mh_masked_loss_partial_size(int B, int Lm) {
 extern "C" int mh_masked_loss_det(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked,
                                   float weight, float* loss_partial, void* drec, int B, int Lm, int Lgroup, int tok_off, int PPC,
                                   int p, void* stream) {
-    MH_CHECK_ARG(rec && target && mask_group && n_masked && loss_partial, "mh_masked_loss_det: null pointer");
-    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss_det: bad arguments");
-    const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL(masked_loss_kernel<true>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target,
-                       mask_group, n_masked, weight, loss_partial, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, 1, 0, 1, 0, rpw);
-    MH_LAUNCH_CHECK();
-    return 0;
+    return launch_masked_loss<true, false>("mh_masked_loss_det", rec && target && mask_group && n_masked && loss_partial, 0, nullptr, rec,
+                                           target, mask_group, n_masked, weight, loss_partial, drec, nullptr, B, Lm, Lgroup, tok_off, PPC,
+                                           p, stream);
 }
 
 extern "C" int mh_masked_loss_bands_det(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems,
                                         float weight, float* loss_partial, void* drec, int B, int Lm, int Lgroup, int tok_off,
                                         int PPC, int p, int tgt_C, int tgt_c0, int n_g, void* stream) {
-    MH_CHECK_ARG(rec && target && mask_group && n_elems && loss_partial, "mh_masked_loss_bands_det: null pointer");
-    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC % 4 == 0 && tok_off + Lm <= Lgroup, "mh_masked_loss_bands_det: bad arguments");
-    MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "mh_masked_loss_bands_det: band window [%d, %d) of %d",
-                 tgt_c0, tgt_c0 + n_g, tgt_C);
-    const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL(masked_loss_kernel<true>, dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec, target,
-                       mask_group, n_elems, weight, loss_partial, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw);
-    MH_LAUNCH_CHECK();
-    return 0;
+    const int window[3] = {tgt_C, tgt_c0, n_g};
+    return launch_masked_loss<true, false>("mh_masked_loss_bands_det", rec && target && mask_group && n_elems && loss_partial, 0, window,
+                                           rec, target, mask_group, n_elems, weight, loss_partial, drec, nullptr, B, Lm, Lgroup, tok_off,
+                                           PPC, p, stream);
 }
 
 extern "C" int mh_masked_loss_cs_rows(int B, int Lm) { return mh_masked_loss_partial_size(B, Lm); }
@@ -357,30 +361,18 @@ extern "C" int mh_masked_loss_cs_rows(int B, int Lm) { return mh_masked_loss_par
 extern "C" int mh_masked_loss_cs(const float* rec, const float* target, const uint8_t* mask_group, const int* n_masked, float weight,
                                  float* acc, void* drec, float* cs_partial, int B, int Lm, int Lgroup, int tok_off, int PPC, int p,
                                  void* stream) {
-    MH_CHECK_ARG(rec && target && mask_group && n_masked && acc && drec && cs_partial, "mh_masked_loss_cs: null pointer");
-    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC > 0 && PPC % 4 == 0 && PPC <= 256 * LOSS_CS_NV && tok_off >= 0 &&
-                 tok_off + Lm <= Lgroup, "mh_masked_loss_cs: bad arguments (PPC %% 4 == 0, PPC <= %d)", 256 * LOSS_CS_NV);
-    const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL((masked_loss_kernel<false, true>), dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec,
-                       target, mask_group, n_masked, weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, 1, 0, 1, 0, rpw, cs_partial);
-    MH_LAUNCH_CHECK();
-    return 0;
+    return launch_masked_loss<false, true>("mh_masked_loss_cs", rec && target && mask_group && n_masked && acc && drec && cs_partial,
+                                           256 * LOSS_CS_NV, nullptr, rec, target, mask_group, n_masked, weight, acc, drec, cs_partial, B,
+                                           Lm, Lgroup, tok_off, PPC, p, stream);
 }
 
 extern "C" int mh_masked_loss_bands_cs(const float* rec, const float* target, const uint8_t* mask_group, const int* n_elems,
                                        float weight, float* acc, void* drec, float* cs_partial, int B, int Lm, int Lgroup, int tok_off,
                                        int PPC, int p, int tgt_C, int tgt_c0, int n_g, void* stream) {
-    MH_CHECK_ARG(rec && target && mask_group && n_elems && acc && drec && cs_partial, "mh_masked_loss_bands_cs: null pointer");
-    MH_CHECK_ARG(B > 0 && Lm > 0 && (p == 1 || p == 2) && PPC > 0 && PPC % 4 == 0 && PPC <= 256 * LOSS_CS_NV && tok_off >= 0 &&
-                 tok_off + Lm <= Lgroup, "mh_masked_loss_bands_cs: bad arguments (PPC %% 4 == 0, PPC <= %d)", 256 * LOSS_CS_NV);
-    MH_CHECK_ARG(n_g > 0 && PPC % n_g == 0 && tgt_c0 >= 0 && tgt_c0 + n_g <= tgt_C, "mh_masked_loss_bands_cs: band window [%d, %d) of %d",
-                 tgt_c0, tgt_c0 + n_g, tgt_C);
-    const int rpw = loss_rows_per_wave((long)B * Lm);
-    hipLaunchKernelGGL((masked_loss_kernel<false, true>), dim3(ceil_div((long)B * Lm, 4 * rpw)), dim3(256), 0, (hipStream_t)stream, rec,
-                       target, mask_group, n_elems, weight, acc, (bf16_t*)drec, B, Lm, Lgroup, tok_off, PPC, p, tgt_C, tgt_c0, n_g, 1, rpw,
-                       cs_partial);
-    MH_LAUNCH_CHECK();
-    return 0;
+    const int window[3] = {tgt_C, tgt_c0, n_g};
+    return launch_masked_loss<false, true>("mh_masked_loss_bands_cs", rec && target && mask_group && n_elems && acc && drec && cs_partial,
+                                           256 * LOSS_CS_NV, window, rec, target, mask_group, n_elems, weight, acc, drec, cs_partial, B,
+                                           Lm, Lgroup, tok_off, PPC, p, stream);
 }
 
 extern "C" int mh_colsum_partial_rows(int M) { return M > 0 ? ceil_div(M, MH_COLSUM_PARTIAL_ROWS) : 0; }

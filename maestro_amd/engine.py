@@ -458,19 +458,30 @@ class PatchEmbedEnd:
         hip.embed_finish(b["yconv"], b["gn_stats"], pe.norm.weight, pe.norm.bias, b["pos_enc"], gbuf["dates"], gbuf["n_dates"],
                          s.date_off, xg, s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
 
-    def backward(self, dxg: torch.Tensor, Lgroup: int, clear_dw: bool, defer_wgrad: bool = False) -> None:  # noqa: N803
+    def backward(self, dxg: torch.Tensor, Lgroup: int, clear_dw: bool, defer_wgrad: bool = False, visible=None) -> None:  # noqa: N803
         """``dxg`` [Beff, Lgroup, E]: gradient of the group sequence.  ``clear_dw``: the conv-gradient staging buffer (split-K
         atomics accumulate into it) was not cleared since the last backward.  ``defer_wgrad``: the conv weight gradient is
-        ``wgrad_problem()`` of the caller's grouped launch, with ``unpack_rows_add`` behind it."""
+        ``wgrad_problem()`` of the caller's grouped launch, with ``unpack_rows_add`` behind it.
+
+        The form is chosen here.  A deterministic engine: every reduction as partial rows (``_backward_det``).  ``visible`` =
+        ``(dx [Beff, n_vis, E], inv [Beff, Lgroup], n_vis)`` instead of ``dxg``: the gradient of the visible rows read through the
+        position map, the conv bias gradient left as partial rows (``cs_buffer``) for the caller's batched column sum.  Else the
+        plain launches with the column sum in line."""
         eng, s, b = self.eng, self.s, self.buf
         ps, E, pe, T = eng.store, eng.E, b["pe"], s.Beff * s.n_tok  # noqa: N806
         if getattr(eng, "deterministic", False):
             return self._backward_det(dxg, Lgroup)
-        hip.embed_finish_bwd(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight), ps.g(pe.norm.bias),
-                             b["gn_sums"], s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
+        if visible is not None:
+            dx, inv, n_vis = visible
+            hip.embed_finish_bwd_ends(dx, inv, n_vis, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight),
+                                      ps.g(pe.norm.bias), b["gn_sums"], self.cs_buffer(), s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
+        else:
+            hip.embed_finish_bwd(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight), ps.g(pe.norm.bias),
+                                 b["gn_sums"], s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
         if not defer_wgrad:
             self._wgrad_in_line(clear_dw)
-        hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
+        if visible is None:
+            hip.colsum(b["dyc"], ps.g(pe.conv.bias), T, E, E)
 
     def _wgrad_in_line(self, clear_dw: bool) -> None:
         """The conv weight gradient as a launch of its own: split-K atomics into the (cleared) padded staging buffer."""
@@ -488,23 +499,11 @@ class PatchEmbedEnd:
         return (b["dyc"], b["cols"], b["dw_conv"], E, s.Kpad, s.Beff * s.n_tok, E, s.Kpad, s.Kpad)
 
     def cs_buffer(self) -> torch.Tensor:
-        """Partial rows of colsum(dyc) -- the conv bias gradient -- written by ``backward_ends``."""
+        """Partial rows of colsum(dyc) -- the conv bias gradient -- written by the ``visible`` form of ``backward``."""
         b, s = self.buf, self.s
         if b.get("dyc_cs") is None:
             b["dyc_cs"] = torch.empty(hip.embed_bwd_cs_rows(s.Beff * s.n_tok), self.eng.E, dtype=F32, device=self.eng.device)
         return b["dyc_cs"]
-
-    def backward_ends(self, dx: torch.Tensor, inv, n_vis: int, Lgroup: int, defer_wgrad: bool, clear_dw: bool) -> None:  # noqa: N803
-        """The backward with its side reductions left to the segment's batched launches: ``dx`` is the gradient of the visible
-        rows [Beff, n_vis, E] read through the position map ``inv`` [Beff, Lgroup] (``inv`` None: the dense group-sequence
-        gradient), the conv bias gradient leaves as partial rows (``cs_buffer``), and with ``defer_wgrad`` the conv weight
-        gradient is ``wgrad_problem()`` of the caller's grouped launch (the caller also issues ``unpack_rows_add`` behind it)."""
-        eng, s, b = self.eng, self.s, self.buf
-        ps, E, pe = eng.store, eng.E, b["pe"]  # noqa: N806
-        hip.embed_finish_bwd_ends(dx, inv, n_vis, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], ps.g(pe.norm.weight),
-                                  ps.g(pe.norm.bias), b["gn_sums"], self.cs_buffer(), s.Beff, s.D, s.L, E, s.tok_off, Lgroup)
-        if not defer_wgrad:
-            self._wgrad_in_line(clear_dw)
 
     def _backward_det(self, dxg: torch.Tensor, Lgroup: int) -> None:  # noqa: N803
         """Deterministic mode: every reduction leaves partial rows in buffers private to this end; the engine's ordered reduce
@@ -520,7 +519,7 @@ class PatchEmbedEnd:
             return w, [(flat, ps.g(pe.norm.weight), rows, E, 2 * E), (flat[E:], ps.g(pe.norm.bias), rows, E, 2 * E),
                        (w["slabs"].view(-1), b["dw_conv"].view(-1), S, E * s.Kpad, E * s.Kpad),
                        (w["cs"].view(-1), ps.g(pe.conv.bias), cr, E, E)]
-        w = eng._det_site("bwd", ("embed", s.name), make)
+        w = eng.sites.get("bwd", ("embed", s.name), make)
         hip.embed_finish_bwd_det(dxg, b["yconv"], b["gn_stats"], pe.norm.weight, b["dyc"], w["gn"], w["blk"], b["gn_sums"], s.Beff,
                                  s.D, s.L, E, s.tok_off, Lgroup)
         hip.gemm_tn_slabs(E, s.Kpad, T, b["dyc"], E, b["cols"], s.Kpad, w["slabs"])
@@ -905,6 +904,49 @@ class EngineBase:
             for lo, hi in spans:
                 self.grad_hook(lo, hi)
 
+    def _ends_on(self) -> bool:
+        """Whether the ends of the backward leave their reductions to the segment's batched launches (``MAEEngine``)."""
+        return False
+
+
+# ======================================================================================= partial-row sites
+class PartialSites:
+    """Registry of the launch sites that leave a reduction as partial rows in buffers of their own, per phase ("fwd", "bwd"):
+    key -> (buffers, jobs ``(src, dst, rows, cols, ld)``), in the order of the sites' first launch -- the order of the Python
+    launch code: group, then modality -- which is the order of their totals inside an ordered-reduce chain.  A buffer is written
+    by one site only, once per step.  Who sums the rows is the caller's business: deterministic mode hands ``jobs(phase)`` to one
+    ``hip.OrderedReduce``, the deferred ends fetch their sites' jobs by key for the segment's ``hip.ColsumBatch``.  ``tables``:
+    the callers' reducers built from whole phases; (re)building a site of a phase drops that phase's entry."""
+
+    def __init__(self, capturing=torch.cuda.is_current_stream_capturing) -> None:
+        self._sites, self.tables, self._capturing = {}, {}, capturing
+
+    def get(self, phase: str, key, make, variant=None):
+        """The site's buffers.  ``make() -> (buffers, jobs)`` runs on the site's first launch (always an eager run: segments are
+        captured on their second run).  ``variant``: a site whose launch form changed (``tie_order``) is rebuilt IN PLACE -- same
+        key, same position -- so the buffer of the form that no longer runs leaves the job list instead of being summed."""
+        sites = self._sites.setdefault(phase, {})
+        site = sites.get(key)
+        if site is None or site[2] != variant:
+            if self._capturing():
+                raise hip.HipExtensionError(f"partial-row site {key} first launched inside a hipGraph capture")
+            site = sites[key] = (*make(), variant)
+            self.tables.pop(phase, None)            # (a table built earlier does not list this site)
+        return site[0]
+
+    def items(self, phase: str) -> list:
+        """``(key, buffers)`` of the sites of ``phase`` in first-launch order."""
+        return [(key, site[0]) for key, site in self._sites.get(phase, {}).items()]
+
+    def jobs(self, phase: str, keys=None) -> list:
+        """The jobs of every site of ``phase`` in first-launch order, or of the sites named by ``keys`` (same order)."""
+        return [j for key, site in self._sites.get(phase, {}).items() if keys is None or key in keys for j in site[1]]
+
+    def buffers(self):
+        """Every buffer the registry owns: what a test poisons between two steps."""
+        for sites in self._sites.values():
+            for bufs, _, _ in sites.values():
+                yield from (bufs.values() if isinstance(bufs, dict) else (bufs,))
 
 
 # ======================================================================================= the engine
@@ -967,18 +1009,15 @@ class MAEEngine(EngineBase):
             raise ValueError(f"MAESTRO_WGRAD={self.wgrad_mode!r}: expected auto, fused or deferred")
         self._wgrad_plans, self._zero_lists = {}, {}
         # The ends of the backward (pixelify head, final LayerNorms, enc_to_dec, patch embed) under a deferred plan, default path:
-        # "a" = their weight gradients join the segment's grouped launch, "b" = their bias / LayerNorm side reductions leave as
-        # partial rows for the segment's batched column sum, "c" = the patch-embed backward reads the encoder gradient through
-        # the position map (no expanded group-sequence gradient; needs "b": the same kernels).  MAESTRO_ENDS (A/B aid, default
-        # "abc") selects a subset; not in deterministic mode (its own launch list), not with fp8, not under the "fused" plan.
-        self.ends_parts = frozenset(os.environ.get("MAESTRO_ENDS", "abc")) if not self.deterministic and dtype != "fp8" else frozenset()
-        if not self.ends_parts <= frozenset("abc") or ("c" in self.ends_parts and "b" not in self.ends_parts):
-            raise ValueError(f"MAESTRO_ENDS={os.environ.get('MAESTRO_ENDS')!r}: a subset of 'abc' expected, 'c' only with 'b'")
+        # their weight gradients join the segment's grouped launch, their bias / LayerNorm side reductions leave as partial rows
+        # for the segment's batched column sum, and the patch-embed backward reads the encoder gradient through the position map
+        # (no expanded group-sequence gradient).  Not in deterministic mode (its own reducer), not with fp8; ``_ends_on`` adds the
+        # plan.  (Measured part by part in profiles/step_ends.md.)
+        self.ends_capable = not self.deterministic and dtype != "fp8"
         self._loss_cs = False       # the last forward's loss launches left the pixelify bias gradients as partial rows
-        self._ends_ws = {}          # site key -> private partial-row workspace (see _ends_buf)
-        # deterministic mode: per phase ("fwd", "bwd") the former atomic sites in the order of their first launch -- key ->
-        # (private buffers, ordered-reduce jobs) -- and the tables built from them (see _det_site)
-        self._det_sites, self._det_tables = {"fwd": {}, "bwd": {}}, {}
+        # the sites that leave partial rows in buffers of their own: the final LayerNorms of the deferred ends, every former atomic
+        # site of deterministic mode; ``_det_wgrad``: that mode's weight-gradient table (see _det_finish_backward)
+        self.sites, self._det_wgrad = PartialSites(), None
         self._h2d_done = [None] * RING   # per ring slot: event after the mask uploads that last used it
         self._opt = None                 # overlapped optimizer (attach_optimizer)
         self.host_wait_s = 0.0           # time the host spent blocked on that ring (diagnostic: not issue work)
@@ -1031,59 +1070,19 @@ class MAEEngine(EngineBase):
                              "collective library's, and the ready spans would have to move behind the ordered reduce")
         self._grad_hook = fn
 
-    def _det_site(self, phase: str, key, make, variant=None):
-        """Private buffers of one former atomic site: ``make() -> (buffers, jobs)`` runs on the site's first launch (always an
-        eager run: segments are captured on their second run) and registers its ordered-reduce jobs ``(src, dst, rows, cols,
-        ld)``.  Sites are listed in the order of their first launch -- the order of the Python launch code: group, then modality
-        -- which is the order of their totals inside a chain.  A buffer is written by one site only, once per step.
-        ``variant``: a site whose launch form changed (``tie_order``) is rebuilt IN PLACE -- same key, same position -- so the
-        buffer of the form that no longer runs leaves the table instead of being summed into the gradient."""
-        site = self._det_sites[phase].get(key)
-        if site is None or site[2] != variant:
-            if torch.cuda.is_current_stream_capturing():
-                raise hip.HipExtensionError(f"deterministic mode: site {key} first launched inside a hipGraph capture")
-            site = self._det_sites[phase][key] = (*make(), variant)
-            self._det_tables.pop(phase, None)       # (a table built earlier does not list this site)
-        return site[0]
-
     def _det_reduce(self, phase: str, extra_jobs=()) -> None:
         """One ordered-reduce launch for every site of ``phase`` (+ ``extra_jobs``, listed after them)."""
-        table = self._det_tables.get(phase)
+        table = self.sites.tables.get(phase)
         if table is None:
-            jobs = [j for _, site_jobs, _ in self._det_sites[phase].values() for j in site_jobs] + list(extra_jobs)
-            table = self._det_tables[phase] = hip.OrderedReduce(jobs, self.device)
+            table = self.sites.tables[phase] = hip.OrderedReduce(self.sites.jobs(phase) + list(extra_jobs), self.device)
         table.launch()
-
-    def _det_layernorm_bwd(self, key, dy, dy_L, dy_off, x, x_L, x_off, norm, mean, rstd, dx, dx16, bias_grad, B, n, dim) -> None:  # noqa: N803
-        """A final-LayerNorm backward outside the stacks: partial rows (dgamma | dbeta | colsum dx) into the site's own workspace."""
-        def make():
-            size = hip.layernorm_bwd_workspace(B * n, dim)
-            ws, rows, g = torch.empty(size, dtype=F32, device=self.device), size // (3 * dim), self.store.g
-            jobs = [(ws, g(norm.weight), rows, dim, 3 * dim), (ws[dim:], g(norm.bias), rows, dim, 3 * dim)]
-            if bias_grad is not None:
-                jobs.append((ws[2 * dim:], bias_grad, rows, dim, 3 * dim))
-            return ws, jobs
-        ws = self._det_site("bwd", key, make)
-        hip.layernorm_bwd_partial(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, ws, B, n, dim)
-
-    def _det_linear_grads(self, key, dy16, x16, M, N, K, weight_grad, bias_grad) -> None:  # noqa: N803
-        """Weight and bias gradient of a Linear outside the stacks (dW[M, N] = dy[K, M]^T x[K, N], db = colsum dy): K-slices into
-        private slabs and per-row-block column sums, both finished by the ordered reduce."""
-        def make():
-            e = lambda *sh: torch.empty(*sh, dtype=F32, device=self.device)  # noqa: E731
-            S, cr = hip.det_slices(K), hip.colsum_partial_rows(K)  # noqa: N806
-            w = dict(slabs=e(S, M, N), cs=e(cr, M))
-            return w, [(w["slabs"].view(-1), weight_grad.view(-1), S, M * N, M * N), (w["cs"].view(-1), bias_grad, cr, M, M)]
-        w = self._det_site("bwd", key, make)
-        hip.gemm_tn_slabs(M, N, K, dy16, M, x16, N, w["slabs"])
-        hip.colsum_partial(dy16, w["cs"], K, M, M)
 
     def _det_finish_backward(self) -> None:
         """End of the backward, on the main stream after the group streams have joined: the deferred weight gradients of every
         stack (plain stores; a weight written by several stacks -- a holder shared by groups -- gets one slab per writer), then
         ONE ordered reduce over every partial buffer of the backward, then the patch-embed conv gradients from their padded
         staging buffers (one add per element and launch, launches in modality order on this stream)."""
-        wg = self._det_tables.get("wgrad")
+        wg = self._det_wgrad
         if wg is None:
             probs = [p for st in self._all_stacks() for p in st.wgrad_problems()]
             n_writers: dict = {}                 # weight-gradient slot -> number of problems that write it
@@ -1108,7 +1107,7 @@ class MAEEngine(EngineBase):
                 except hip.HipExtensionError:
                     single.append(p)        # not eligible for the grouped kernel: a plain-store TN GEMM of its own
             stack_jobs = [j for st in self._all_stacks() for j in st.reduce_jobs()]
-            wg = self._det_tables["wgrad"] = (hip.GroupedTN(grouped, self.device) if grouped else None, single, stack_jobs + slab_jobs)
+            wg = self._det_wgrad = (hip.GroupedTN(grouped, self.device) if grouped else None, single, stack_jobs + slab_jobs)
         if wg[0] is not None:
             wg[0].launch()
         for (A, B, C, M, N, K, lda, ldb, ldc) in wg[1]:  # noqa: N806
@@ -1132,7 +1131,7 @@ class MAEEngine(EngineBase):
             self.mb[name].update(
                 target=first["target"] if first else e(T, s.C_src * s.P * s.P), hdec=e(T, Dd, dt=BF16), mean_f=e(T), rstd_f=e(T),
                 rec=e(T, s.K), drec=e(T, s.K, dt=BF16), dh=e(T, Dd, dt=BF16), cnt=first["cnt"] if first else z(1, dt=I32))
-            if "b" in self.ends_parts and s.K <= 1024:   # partial rows of colsum(drec), written by the loss launch itself
+            if self.ends_capable and s.K <= 1024:   # partial rows of colsum(drec), written by the loss launch itself
                 self.mb[name]["drec_cs"] = e(hip.masked_loss_cs_rows(s.Beff, s.n_tok), s.K)
         self.gb = {}
         self.enc, self.dec = {}, {}
@@ -1149,7 +1148,7 @@ class MAEEngine(EngineBase):
                 pos_dec=pos_dec.to(dev).contiguous(), tok_table=e(len(g.mods), Dd),
                 henc=e(Bn * N, E, dt=BF16), mean_e=e(Bn * N), rstd_e=e(Bn * N), y_e2d=e(Bn * N, Dd),
                 dy_e2d=e(Bn * N, Dd), dy_e2d16=e(Bn * N, Dd, dt=BF16), dhenc=e(Bn * N, E, dt=BF16),
-                e2d_cs=e(hip.gather_rows_cs_rows(Bn * N), Dd) if "b" in self.ends_parts and Dd <= 1024 else None,
+                e2d_cs=e(hip.gather_rows_cs_rows(Bn * N), Dd) if self.ends_capable and Dd <= 1024 else None,
                 mean_j=e(Bn * N), rstd_j=e(Bn * N))
             holder = m.encoder[g.model]
             self.enc[g.name] = Stack(self, holder, Bn, N, f"enc.{g.name}")
@@ -1353,7 +1352,7 @@ class MAEEngine(EngineBase):
         with self._tuning_pass("forward"):
             # the loss launch writes the pixelify bias gradient's partial rows only where the backward will sum them (not under
             # the "fused" plan: its launch list is the previous one); the form is part of the forward graph's key
-            self._loss_cs = "b" in self.ends_parts and self._wgrad_plan() != "fused"
+            self._loss_cs = self._ends_on()
             self._segment("forward" if self._opt is None else "forward:opt", (self._cur_key, self._loss_cs),
                           lambda: self._forward_launches(batch))
         if self._opt is not None:
@@ -1461,6 +1460,24 @@ class MAEEngine(EngineBase):
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
 
+    def _loss_launch(self, g, gbuf, s) -> None:
+        """The masked loss + d loss / d rec of one modality spec.  Deterministic mode: the workgroups' partial losses go to a site
+        of their own (``_det_reduce("fwd")`` sums them); ``_loss_cs``: the launch also leaves the pixelify bias gradient as partial
+        rows; a modality with several band-groups: the entry that reads this band-group's window of the modality's target."""
+        b = self.mb[s.name]
+        form, acc, cs = "", self.loss_acc, ()
+        if self.deterministic:
+            def make():
+                part = torch.empty(hip.masked_loss_partial_size(s.Beff, s.n_tok), dtype=F32, device=self.device)
+                return part, [(part, self.loss_acc, part.numel(), 1, 1)]
+            form, acc = "_det", self.sites.get("fwd", ("loss", s.name), make)
+        elif self._loss_cs and b.get("drec_cs") is not None:
+            form, cs = "_cs", (b["drec_cs"],)
+        bands = () if s.G == 1 else (s.C_src, s.c0, s.C)
+        getattr(hip, f"masked_loss{'_bands' if bands else ''}{form}")(
+            b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], acc, b["drec"], *cs, s.Beff, s.n_tok, g.L, s.tok_off,
+            s.K, self.p_loss, *bands)
+
     def _forward_launches(self, batch: dict) -> None:
         m, E, Dd = self.model, self.E, self.Dd  # noqa: N806
         self.loss_acc.zero_()
@@ -1532,32 +1549,7 @@ class MAEEngine(EngineBase):
                 if s.G == 1:
                     hip.count_masked(gbuf["mask"], g.Beff, g.L, s.tok_off, s.tok_off + s.n_tok, b["cnt"])
             for s in g.mods:    # (several band-groups: counted by count_band_group_elems, before any decoder side starts)
-                b = self.mb[s.name]
-                if self.deterministic:
-                    def make(s=s):
-                        part = torch.empty(hip.masked_loss_partial_size(s.Beff, s.n_tok), dtype=F32, device=self.device)
-                        return part, [(part, self.loss_acc, part.numel(), 1, 1)]
-                    part = self._det_site("fwd", ("loss", s.name), make)
-                    if s.G == 1:
-                        hip.masked_loss_det(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], part,
-                                            b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
-                    else:
-                        hip.masked_loss_bands_det(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], part,
-                                                  b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss, s.C_src, s.c0, s.C)
-                elif self._loss_cs and b.get("drec_cs") is not None:   # the same launch also leaves the pixelify bias gradient as partial rows
-                    if s.G == 1:
-                        hip.masked_loss_cs(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
-                                           b["drec"], b["drec_cs"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
-                    else:
-                        hip.masked_loss_bands_cs(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
-                                                 b["drec"], b["drec_cs"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss,
-                                                 s.C_src, s.c0, s.C)
-                elif s.G == 1:
-                    hip.masked_loss(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
-                                    b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss)
-                else:
-                    hip.masked_loss_bands(b["rec"], b["target"], gbuf["mask"], b["cnt"], self.loss_w[s.src], self.loss_acc,
-                                          b["drec"], s.Beff, s.n_tok, g.L, s.tok_off, s.K, self.p_loss, s.C_src, s.c0, s.C)
+                self._loss_launch(g, gbuf, s)
 
         self._run_parallel([head(g) for g in self.groups])
         if self.joint is not None:
@@ -1614,7 +1606,7 @@ class MAEEngine(EngineBase):
             # of one torch fill each inside the backward
             # (a buffer that the grouped launch STORES -- _ends_deferred -- needs no clearing)
             for name, b in self.mb.items():
-                if b.get("dw_conv") is not None and not self._ends_deferred(self.embed[name].wgrad_problem(), plan):
+                if b.get("dw_conv") is not None and not self._ends_deferred(self.embed[name].wgrad_problem()):
                     spans.append(((b["dw_conv"].data_ptr() - base) // 4, b["dw_conv"].numel()))
             dev = torch.tensor([v for sp in spans for v in sp], dtype=torch.int64, device=self.device)
             z = self._zero_lists[plan] = (dev, len(spans), max(n for _, n in spans))
@@ -1720,7 +1712,7 @@ class MAEEngine(EngineBase):
             sfx += ":nz"     # no zero_grad since the last backward: this launch list clears the conv-gradient staging buffers itself
         if self.fp8 is not None and self.fp8.dgrad:
             sfx += ":f8" if self.fp8.grad_ready else ":cal"       # (the first backward calibrates the gradient scales in bf16)
-        if self._ends("b") and not self._loss_cs:
+        if self._ends_on() and not self._loss_cs:
             sfx += ":nolcs"
         cuts = self._enc_cuts()
         # (name, launches, deferred weight gradients of the segment, ends whose reductions the segment produces)
@@ -1743,24 +1735,24 @@ class MAEEngine(EngineBase):
             self.fp8.end_of_backward()      # next step's e5m2 gradient scales from this backward's absmax values
 
     # ------------------------------------------------------------------------------------------ the ends of the backward
-    def _ends(self, part: str, plan: str | None = None) -> bool:
-        """Whether part "a" / "b" / "c" of the ends' launch structure (see ``ends_parts``) is in force under ``plan``."""
-        return part in self.ends_parts and (self._plan if plan is None else plan) in ("all", "enc", "ovl")
+    def _ends_on(self) -> bool:
+        """The ends of the backward leave their reductions to the segment's batched launches: non-deterministic, not fp8, a
+        deferred weight-gradient plan."""
+        return self.ends_capable and self._wgrad_plan() in ("all", "enc", "ovl")
 
     def _ends_tags(self, *tags) -> tuple:
-        """The ends tags of a segment, or none under the "fused" plan.  "dec:nolcs": the forward ran before the plan became a
+        """The ends tags of a segment, or none where the ends are off.  "dec:nolcs": the forward ran before the plan became a
         deferred one (a gradient hook or ``wgrad_mode`` set between forward and backward) and left no partial rows of the
         pixelify bias gradient: that backward takes the column sums of ``drec`` itself, with tables and graphs of its own."""
-        if not self.ends_parts or self._plan == "fused":
+        if not self._ends_on():
             return ()
-        stale = self._ends("b") and not self._loss_cs
-        return tuple("dec:nolcs" if t == "dec" and stale else t for t in tags)
+        return tuple("dec:nolcs" if t == "dec" and not self._loss_cs else t for t in tags)
 
-    def _ends_deferred(self, prob, plan: str | None = None) -> bool:
-        """Part "a": this weight gradient of an end joins the segment's grouped launch.  A problem the grouped kernel cannot
-        address (``GroupedTN.check``: in practice an operand beyond its 2 GiB descriptor range, the M, N % 8 rule being the split-K
+    def _ends_deferred(self, prob) -> bool:
+        """This weight gradient of an end joins the segment's grouped launch.  A problem the grouped kernel cannot address
+        (``GroupedTN.check``: in practice an operand beyond its 2 GiB descriptor range, the M, N % 8 rule being the split-K
         launch's own as well) keeps its split-K launch."""
-        if not self._ends("a", plan):
+        if not self._ends_on():
             return False
         try:
             hip.GroupedTN.check(0, prob)
@@ -1768,39 +1760,69 @@ class MAEEngine(EngineBase):
         except hip.HipExtensionError:
             return False
 
-    def _embed_cs(self) -> bool:
-        """The patch-embed backward runs in its ends form (``PatchEmbedEnd.backward_ends``: conv bias gradient as partial rows,
-        optionally through the position map); its kernels keep a row's columns in registers, hence the width limit."""
-        return self._ends("b") and self.E <= 1024
-
-    def _ends_buf(self, key, *shape) -> torch.Tensor:
-        """Private fp32 partial-row workspace of one site of the ends, allocated on the site's first launch (an eager run)."""
-        buf = self._ends_ws.get(key)
-        if buf is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise hip.HipExtensionError(f"ends workspace {key} first needed inside a hipGraph capture")
-            buf = self._ends_ws[key] = torch.empty(*shape, dtype=F32, device=self.device)
-        return buf
+    def _embed_mapped(self) -> bool:
+        """The patch-embed backward reads the visible rows' gradient through the position map and leaves the conv bias gradient as
+        partial rows (``PatchEmbedEnd.backward``, ``visible``); its kernels keep a row's columns in registers, hence the width limit."""
+        return self._ends_on() and self.E <= 1024
 
     def _final_layernorm_bwd(self, key, gbuf, dy, dy_L, dy_off, x, x_L, x_off, norm, mean, rstd, dx, dx16, bias_grad, B, n, dim) -> None:  # noqa: N803
-        """Backward of a final LayerNorm (no residual gradient).  Part "b": partial rows (dgamma | dbeta | colsum dx) into the
-        site's own workspace, summed by the segment's batched column sum (``_ends_ln_jobs``); else the two-launch form with
-        the group's shared workspace."""
-        if self._ends("b"):
-            ws = self._ends_buf(key, hip.layernorm_bwd_workspace(B * n, dim))
-            hip.layernorm_bwd_partial(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, ws, B, n, dim)
-        else:
-            g = self.store.g
+        """Backward of a final LayerNorm (no residual gradient).  Deterministic mode and the deferred ends: partial rows (dgamma |
+        dbeta | colsum dx) into the site's own workspace, summed by the ordered reduce / the segment's batched column sum
+        (``_ends_table``); else the two-launch form with the group's shared workspace."""
+        g = self.store.g
+        if not (self.deterministic or self._ends_on()):
             hip.layernorm_bwd(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, g(norm.weight), g(norm.bias),
                               bias_grad, gbuf["ln_ws"], B, n, dim)
+            return
 
-    def _ends_ln_jobs(self, key, norm, bias_grad, dim) -> list:
-        ws, g = self._ends_ws[key], self.store.g
-        rows = ws.numel() // (3 * dim)
-        jobs = [(ws, g(norm.weight), rows, dim, 3 * dim), (ws[dim:], g(norm.bias), rows, dim, 3 * dim)]
-        if bias_grad is not None:
-            jobs.append((ws[2 * dim:], bias_grad, rows, dim, 3 * dim))
-        return jobs
+        def make():
+            size = hip.layernorm_bwd_workspace(B * n, dim)
+            ws, rows = torch.empty(size, dtype=F32, device=self.device), size // (3 * dim)
+            jobs = [(ws, g(norm.weight), rows, dim, 3 * dim), (ws[dim:], g(norm.bias), rows, dim, 3 * dim)]
+            if bias_grad is not None:
+                jobs.append((ws[2 * dim:], bias_grad, rows, dim, 3 * dim))
+            return ws, jobs
+        ws = self.sites.get("bwd", key, make)
+        hip.layernorm_bwd_partial(dy, dy_L, dy_off, x, x_L, x_off, norm.weight, mean, rstd, None, dx, dx16, ws, B, n, dim)
+
+    def _linear_grads(self, key, prob, bias_grad, cs_done: bool) -> None:
+        """Weight and bias gradient of a Linear outside the stacks; ``prob`` = its weight gradient dW[M, N] = dy[K, M]^T x[K, N] as
+        a ``hip.GroupedTN`` entry, db = colsum dy.  Deterministic mode: K-slices into private slabs and per-row-block column sums,
+        both finished by the ordered reduce.  Else split-K atomics and a column sum in line -- unless the problem joins the
+        segment's grouped launch (``_ends_deferred``), unless a producer already left the column sums as partial rows
+        (``cs_done``)."""
+        dy16, x16, dw, M, N, K = prob[:6]  # noqa: N806
+        if self.deterministic:
+            def make():
+                e = lambda *sh: torch.empty(*sh, dtype=F32, device=self.device)  # noqa: E731
+                S, cr = hip.det_slices(K), hip.colsum_partial_rows(K)  # noqa: N806
+                w = dict(slabs=e(S, M, N), cs=e(cr, M))
+                return w, [(w["slabs"].view(-1), dw.view(-1), S, M * N, M * N), (w["cs"].view(-1), bias_grad, cr, M, M)]
+            w = self.sites.get("bwd", key, make)
+            hip.gemm_tn_slabs(M, N, K, dy16, M, x16, N, w["slabs"])
+            hip.colsum_partial(dy16, w["cs"], K, M, M)
+            return
+        if not self._ends_deferred(prob):
+            hip.gemm(hip.GEMM_TN, M, N, K, dy16, M, x16, N, dw, N, hip.OUT_F32 | hip.ATOMIC)
+        if not cs_done:
+            hip.colsum(dy16, bias_grad, K, M, M)
+
+    def _mask_token_grad(self, g, gbuf, s, dx0) -> None:
+        """Gradient of one modality spec's mask token from the masked rows of ``dx0``; ``tie_order`` "torch": through the
+        per-sample slot map.  Deterministic mode: per-workgroup rows into a site of its own (rebuilt when the form changes)."""
+        Dd, per_sample, det = self.Dd, self.tie_order == "torch", "_det" if self.deterministic else ""  # noqa: N806
+        dst = self.store.g(self.model.mask_token[s.src]).view(s.G, Dd)[s.gi]
+        if self.deterministic:
+            def make(token_grad=dst):
+                rows = hip.unmask_token_grad_partial_rows(g.Beff * (g.L if per_sample else s.n_tok))
+                part = torch.empty(rows, Dd, dtype=F32, device=self.device)
+                return part, [(part.view(-1), token_grad, rows, Dd, Dd)]
+            dst = self.sites.get("bwd", ("tok", s.name), make, variant=per_sample)
+        if per_sample:
+            getattr(hip, "unmask_token_grad_per_sample" + det)(dx0, gbuf["mask"], gbuf["tok_slot_ps"], dst, g.Beff, g.L, Dd, s.slot)
+        else:
+            getattr(hip, "unmask_token_grad" + det)(dx0, gbuf["mask"], gbuf["tok_slot"], dst, g.Beff, g.L, Dd, s.slot, s.tok_off,
+                                                    s.tok_off + s.n_tok)
 
     def _rec_wgrad(self, s) -> tuple:
         """Pixelify conv weight gradient dW[K, Dd] = drec[T, K]^T hdec[T, Dd] of one modality spec as a ``hip.GroupedTN`` entry."""
@@ -1815,37 +1837,34 @@ class MAEEngine(EngineBase):
     def _ends_table(self, tag: str):
         """What the ends produced by one backward segment add to its two batched launches: ``(grouped problems, column-sum
         jobs, launches that must follow the grouped one, modules whose gradients are final after it)``.  Built with the
-        segment's table, i.e. after the segment's first (eager) run has allocated the sites' workspaces."""
+        segment's table, i.e. after the segment's first (eager) run has registered the sites of its final LayerNorms."""
         m, ps, E, Dd = self.model, self.store, self.E, self.Dd  # noqa: N806
         probs, jobs, after, ready = [], [], [], []
+        ln_jobs = lambda *key: self.sites.jobs("bwd", (key,))  # noqa: E731
         if tag in ("dec", "dec:nolcs"):
             for g in self.groups:
-                gbuf, st = self.gb[g.name], self.dec[g.name]
+                gbuf = self.gb[g.name]
                 for s in g.mods:
                     b = self.mb[s.name]
                     conv = m.embed_to_rec[s.embed].pixelify_bands[s.gi].conv
                     if self._ends_deferred(self._rec_wgrad(s)):
                         probs.append(self._rec_wgrad(s))
-                    if self._ends("b"):
-                        if tag == "dec" and b.get("drec_cs") is not None:
-                            jobs.append((b["drec_cs"].view(-1), ps.g(conv.bias), b["drec_cs"].shape[0], s.K, s.K))
-                        jobs += self._ends_ln_jobs(("ln_dec", s.name), st.t.norm, st.top_bias_grad(), Dd)
+                    if tag == "dec" and b.get("drec_cs") is not None:
+                        jobs.append((b["drec_cs"].view(-1), ps.g(conv.bias), b["drec_cs"].shape[0], s.K, s.K))
+                    jobs += ln_jobs("ln_dec", s.name)
                     ready.append(m.embed_to_rec[s.embed])
-                ready.append(st.t.norm)
+                ready.append(self.dec[g.name].t.norm)
                 if not self.e2d_identity:
                     if self._ends_deferred(self._e2d_wgrad(g)):
                         probs.append(self._e2d_wgrad(g))
-                    if self._ends("b") and gbuf["e2d_cs"] is not None:
+                    if gbuf["e2d_cs"] is not None:
                         jobs.append((gbuf["e2d_cs"].view(-1), ps.g(m.enc_to_dec[g.model].bias), gbuf["e2d_cs"].shape[0], Dd, Dd))
                     ready.append(m.enc_to_dec[g.model])
-                if self.joint is not None and self._ends("b"):
-                    jobs += self._ends_ln_jobs(("ln_joint", g.name), self.joint.t.norm, self.joint.top_bias_grad(), E)
+                jobs += ln_jobs("ln_joint", g.name)        # (none without a joint encoder)
         elif tag == "enc_first":
             for g in self.groups:
-                st = self.enc[g.name]
-                if self._ends("b"):
-                    jobs += self._ends_ln_jobs(("ln_enc", g.name), st.t.norm, st.top_bias_grad(), E)
-                ready.append(st.t.norm)
+                jobs += ln_jobs("ln_enc", g.name)
+                ready.append(self.enc[g.name].t.norm)
         elif tag == "enc_last":
             for g in self.groups:
                 for s in g.mods:
@@ -1853,7 +1872,7 @@ class MAEEngine(EngineBase):
                     if self._ends_deferred(end.wgrad_problem()):
                         probs.append(end.wgrad_problem())
                         after.append(lambda b=b, s=s: hip.unpack_rows_add(b["dw_conv"], ps.g(b["pe"].conv.weight), E, s.K, s.Kpad))
-                    if self._embed_cs():
+                    if self._embed_mapped():
                         jobs.append((end.cs_buffer().view(-1), ps.g(b["pe"].conv.bias), end.cs_buffer().shape[0], E, E))
         else:
             raise ValueError(tag)
@@ -1861,9 +1880,8 @@ class MAEEngine(EngineBase):
 
     def _bwd_decoder_side(self) -> None:
         m, E, Dd, ps = self.model, self.E, self.Dd, self.store  # noqa: N806
-        AT = hip.OUT_F32 | hip.ATOMIC  # noqa: N806
         ends = self._ends_tags("dec")       # set: the ends' modules are reported ready behind the launch that finishes them
-        loss_cs = ends == ("dec",) and self._ends("b")      # the forward's loss launches left the pixelify bias partial rows
+        loss_cs = ends == ("dec",)          # the forward's loss launches left the pixelify bias partial rows
 
         def side(g):
             def run():
@@ -1876,16 +1894,8 @@ class MAEEngine(EngineBase):
                     conv = m.embed_to_rec[s.embed].pixelify_bands[s.gi].conv
                     w16 = ps.h(conv.weight).view(s.K, Dd)
                     hip.gemm(hip.GEMM_NN, T, Dd, s.K, b["drec"], s.K, w16, Dd, b["dh"], Dd)
-                    if self.deterministic:
-                        self._det_linear_grads(("rec", s.name), b["drec"], b["hdec"], s.K, Dd, T, ps.g(conv.weight), ps.g(conv.bias))
-                        self._det_layernorm_bwd(("ln_dec", s.name), b["dh"], s.n_tok, 0, st.x_last, g.L, s.tok_off, nrm, b["mean_f"],
-                                                b["rstd_f"], dx, dx16, st.top_bias_grad(), s.Beff, s.n_tok, Dd)
-                        self._grads_ready(m.embed_to_rec[s.embed])
-                        continue
-                    if not self._ends_deferred(self._rec_wgrad(s)):
-                        hip.gemm(hip.GEMM_TN, s.K, Dd, T, b["drec"], s.K, b["hdec"], Dd, ps.g(conv.weight).view(s.K, Dd), Dd, AT)
-                    if not (loss_cs and b.get("drec_cs") is not None):   # (else: partial rows left by the loss launch)
-                        hip.colsum(b["drec"], ps.g(conv.bias), T, s.K, s.K)
+                    # (the column sums of drec: partial rows left by the loss launch, where there are any)
+                    self._linear_grads(("rec", s.name), self._rec_wgrad(s), ps.g(conv.bias), loss_cs and b.get("drec_cs") is not None)
                     self._final_layernorm_bwd(("ln_dec", s.name), gbuf, b["dh"], s.n_tok, 0, st.x_last, g.L, s.tok_off, nrm, b["mean_f"],
                                               b["rstd_f"], dx, dx16, st.top_bias_grad(), s.Beff, s.n_tok, Dd)
                     if not ends:
@@ -1898,33 +1908,14 @@ class MAEEngine(EngineBase):
             if not ends:
                 self._grads_ready(st.t.norm)
             # unmask backward: visible rows -> enc_to_dec output grad; masked rows -> mask-token grads
-            # (part "b": the gather writes the bf16 operand of the enc_to_dec GEMMs directly, with its column sums as partial rows)
-            e2d_cs = gbuf["e2d_cs"] if self._ends("b") and not self.e2d_identity else None
+            # (the deferred ends: the gather writes the bf16 operand of the enc_to_dec GEMMs directly, with its column sums as partial rows)
+            e2d_cs = gbuf["e2d_cs"] if ends and not self.e2d_identity else None
             if e2d_cs is not None:
                 hip.gather_rows_bf16_cs(dx0, gbuf["vis"], gbuf["dy_e2d16"], e2d_cs, g.Beff, g.L, g.N, Dd)
             else:
                 hip.gather_rows(dx0, gbuf["vis"], gbuf["dy_e2d"], g.Beff, g.L, g.N, Dd, g.N, 0)
             for s in g.mods:
-                if self.deterministic:
-                    per_sample = self.tie_order == "torch"
-                    n_rows = g.Beff * (g.L if per_sample else s.n_tok)
-
-                    def make(s=s, n_rows=n_rows):
-                        rows = hip.unmask_token_grad_partial_rows(n_rows)
-                        part = torch.empty(rows, Dd, dtype=F32, device=self.device)
-                        return part, [(part.view(-1), ps.g(m.mask_token[s.src]).view(s.G, Dd)[s.gi], rows, Dd, Dd)]
-                    part = self._det_site("bwd", ("tok", s.name), make, variant=per_sample)
-                    if per_sample:
-                        hip.unmask_token_grad_per_sample_det(dx0, gbuf["mask"], gbuf["tok_slot_ps"], part, g.Beff, g.L, Dd, s.slot)
-                    else:
-                        hip.unmask_token_grad_det(dx0, gbuf["mask"], gbuf["tok_slot"], part, g.Beff, g.L, Dd, s.slot, s.tok_off,
-                                                  s.tok_off + s.n_tok)
-                elif self.tie_order == "torch":
-                    hip.unmask_token_grad_per_sample(dx0, gbuf["mask"], gbuf["tok_slot_ps"],
-                                                     ps.g(m.mask_token[s.src]).view(s.G, Dd)[s.gi], g.Beff, g.L, Dd, s.slot)
-                else:
-                    hip.unmask_token_grad(dx0, gbuf["mask"], gbuf["tok_slot"], ps.g(m.mask_token[s.src]).view(s.G, Dd)[s.gi], g.Beff,
-                                          g.L, Dd, s.slot, s.tok_off, s.tok_off + s.n_tok)
+                self._mask_token_grad(g, gbuf, s, dx0)
                 self._ready_spans.append(ps.span([m.mask_token[s.src]]))
             M = g.Beff * g.N  # noqa: N806
             lin = m.enc_to_dec[g.model]
@@ -1932,25 +1923,14 @@ class MAEEngine(EngineBase):
                 if e2d_cs is None:
                     hip.cast_bf16(gbuf["dy_e2d"], gbuf["dy_e2d16"], M * Dd)
                 hip.gemm(hip.GEMM_NN, M, E, Dd, gbuf["dy_e2d16"], Dd, ps.h(lin.weight), E, gbuf["dhenc"], E)
-                if self.deterministic:
-                    self._det_linear_grads(("e2d", g.name), gbuf["dy_e2d16"], gbuf["henc"], Dd, E, M, ps.g(lin.weight), ps.g(lin.bias))
-                else:
-                    if not self._ends_deferred(self._e2d_wgrad(g)):
-                        hip.gemm(hip.GEMM_TN, Dd, E, M, gbuf["dy_e2d16"], Dd, gbuf["henc"], E, ps.g(lin.weight), E, AT)
-                    if e2d_cs is None:
-                        hip.colsum(gbuf["dy_e2d16"], ps.g(lin.bias), M, Dd, Dd)
+                self._linear_grads(("e2d", g.name), self._e2d_wgrad(g), ps.g(lin.bias), e2d_cs is not None)
                 if not ends:
                     self._grads_ready(lin)
             if self.joint is not None:   # final LN of the joint encoder, this group's rows
                 jt = self.joint
-                jn = jt.t.norm
-                dy = gbuf["dy_e2d" if self.e2d_identity else "dhenc"]
-                if self.deterministic:
-                    self._det_layernorm_bwd(("ln_joint", g.name), dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn, gbuf["mean_j"],
-                                            gbuf["rstd_j"], jt.dxa, jt.top16, jt.top_bias_grad(), g.Beff, g.N, E)
-                else:
-                    self._final_layernorm_bwd(("ln_joint", g.name), gbuf, dy, g.N, 0, jt.x_last, m.joint_N, g.joint_off, jn, gbuf["mean_j"],
-                                              gbuf["rstd_j"], jt.dxa, jt.top16, jt.top_bias_grad(), g.Beff, g.N, E)
+                self._final_layernorm_bwd(("ln_joint", g.name), gbuf, gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0, jt.x_last,
+                                          m.joint_N, g.joint_off, jt.t.norm, gbuf["mean_j"], gbuf["rstd_j"], jt.dxa, jt.top16,
+                                          jt.top_bias_grad(), g.Beff, g.N, E)
 
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":
@@ -1974,14 +1954,7 @@ class MAEEngine(EngineBase):
                 gbuf, st = self.gb[g.name], self.enc[g.name]
                 nrm = st.t.norm
                 s_hi, s_lo = min(hi, st.depth), min(lo, st.depth)
-                if first and self.deterministic:
-                    dy, dy_L, dy_off = ((self._djoint, m.joint_N, g.joint_off) if self.joint is not None else  # noqa: N806
-                                        (gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0))
-                    self._det_layernorm_bwd(("ln_enc", g.name), dy, dy_L, dy_off, st.x_last, g.N, 0, nrm, gbuf["mean_e"], gbuf["rstd_e"],
-                                            st.dxa, st.top16, st.top_bias_grad(), g.Beff, g.N, E)
-                    self._grads_ready(nrm)
-                    self._enc_state[g.name] = (st.dxa, st.top16)
-                elif first:
+                if first:
                     dy, dy_L, dy_off = ((self._djoint, m.joint_N, g.joint_off) if self.joint is not None else  # noqa: N806
                                         (gbuf["dy_e2d" if self.e2d_identity else "dhenc"], g.N, 0))
                     self._final_layernorm_bwd(("ln_enc", g.name), gbuf, dy, dy_L, dy_off, st.x_last, g.N, 0, nrm, gbuf["mean_e"],
@@ -1996,24 +1969,16 @@ class MAEEngine(EngineBase):
             return run
 
         def side_post(g, gbuf, st):
-            dx0 = self._enc_state[g.name][0]
-            if self._ends("c") and self._embed_cs():
-                # the patch-embed backward reads the visible rows' gradient through the position map: no expanded copy
-                for s in g.mods:
-                    end = self.embed[s.name]
-                    end.backward_ends(dx0, gbuf["inv"], g.N, g.L, self._ends_deferred(end.wgrad_problem()), not self._dw_conv_clear)
-                return
-            # back to the full group sequence (masked tokens get zero: every row is written, no memset), then the
-            # patch-embed backward per modality
-            if gbuf.get("dxg") is None:      # (first needed in an eager run: segments are captured on their second run)
-                gbuf["dxg"] = torch.empty(g.Beff, g.L, E, dtype=F32, device=self.device)
-            hip.expand_rows(dx0, gbuf["inv"], gbuf["dxg"], g.Beff, g.L, g.N, E)
-            for s in g.mods:
+            dx0, visible, clear_dw = self._enc_state[g.name][0], None, not self._dw_conv_clear
+            if self._embed_mapped():     # the patch-embed backward reads the visible rows' gradient through the position map
+                visible = (dx0, gbuf["inv"], g.N)
+            else:   # back to the full group sequence (masked tokens get zero: every row is written, no memset)
+                if gbuf.get("dxg") is None:      # (first needed in an eager run: segments are captured on their second run)
+                    gbuf["dxg"] = torch.empty(g.Beff, g.L, E, dtype=F32, device=self.device)
+                hip.expand_rows(dx0, gbuf["inv"], gbuf["dxg"], g.Beff, g.L, g.N, E)
+            for s in g.mods:    # (the staging buffer is normally cleared by zero_grad's span launch)
                 end = self.embed[s.name]
-                if self._embed_cs():
-                    end.backward_ends(gbuf["dxg"], None, 0, g.L, self._ends_deferred(end.wgrad_problem()), not self._dw_conv_clear)
-                else:       # (the staging buffer is normally cleared by zero_grad's span launch)
-                    end.backward(gbuf["dxg"], g.L, not self._dw_conv_clear, self._ends_deferred(end.wgrad_problem()))
+                end.backward(gbuf.get("dxg"), g.L, clear_dw, self._ends_deferred(end.wgrad_problem()), visible)
 
         self._run_parallel([side(g) for g in self.groups])
         if self._plan == "enc":      # this segment's layers of every group encoder

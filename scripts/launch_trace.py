@@ -6,10 +6,10 @@ checkouts.  Host-side refactors of the engines must leave it byte-identical (pro
 
 Sequence (eager launches, MAESTRO_GRAPHS=0): forward, zero_grad, backward; the same again; forward, backward without a
 zero_grad.  A record holds the stream (numbered by first appearance) and either the C entry name with every scalar argument
-(``hip.call`` / ``hip._gemm_tile``), the problem list handed to a ``GroupedTN`` / ``ColsumBatch`` constructor, or a torch
-operator touching device memory (``TorchDispatchMode``; views are not device operations and are left out).  Tensors are
-described by dtype, shape, strides, storage offset and their storage numbered by first appearance: addresses differ
-between runs, the order in which buffers are first used does not.
+(``hip.call`` / ``hip._gemm_tile`` / an ``OrderedReduce`` launch), the problem list handed to a ``GroupedTN`` / ``ColsumBatch`` /
+``OrderedReduce`` constructor, or a torch operator touching device memory (``TorchDispatchMode``; views are not device operations
+and are left out).  Tensors are described by dtype, shape, strides, storage offset and their storage numbered by first appearance:
+addresses differ between runs, the order in which buffers are first used does not.
 """
 
 from __future__ import annotations
@@ -96,11 +96,18 @@ def install(trace: Trace) -> None:
         return gemm_tile(*args)
 
     hip.call, hip._gemm_tile = traced_call, traced_gemm_tile
-    for cls in (hip.GroupedTN, hip.ColsumBatch):
+    for cls in (hip.GroupedTN, hip.ColsumBatch, hip.OrderedReduce):
         def init(self, problems, device, _cls=cls, _init=cls.__init__):
             trace.write(ctor=_cls.__name__, problems=[trace.value(p) for p in problems])
             _init(self, problems, device)
         cls.__init__ = init
+    launch = hip.OrderedReduce.launch           # (binds the library itself, not hip.call)
+
+    def traced_launch(self):
+        trace.write(entry="mh_reduce_ordered", args=[trace.value(a) for a in (self.table, self.n, self.blocks, self.n_blocks)])
+        return launch(self)
+
+    hip.OrderedReduce.launch = traced_launch
 
 
 def pretrain_case(name: str, dev):

@@ -146,7 +146,7 @@ def test_gradients_agree_with_default_mode(golden_dir, name):
         # the slab sites really have two slices here.  Their two weight gradients are also compared one by one, as a GROSS-error
         # check: a lost, doubled or misplaced K-slice changes half of a weight gradient's addends (relative error of order 1) and
         # could hide in the flat buffer's norm, while a reordered fp32 sum moves it by about 1e-6; 1e-2 only has to separate the two.
-        sites = {key: site[0]["slabs"].shape[0] for key, site in eng._det_sites["bwd"].items() if key[0] in ("rec", "embed")}
+        sites = {key: bufs["slabs"].shape[0] for key, bufs in eng.sites.items("bwd") if key[0] in ("rec", "embed")}
         assert sites[("rec", "aerial")] == 2 and sites[("embed", "aerial")] == 2, sites
         st, m, checked = eng.store, eng.model, 0
         for s in eng.mods.values():
@@ -178,11 +178,11 @@ def test_changing_tie_order_rebuilds_the_mask_token_site(golden_dir):
     eng = model.engine(B, dev, loss="l2_norm", deterministic=True)
     eng.use_graphs = False
     step(eng)
-    n_sites = len(eng._det_sites["bwd"])
+    n_sites = len(eng.sites.items("bwd"))
     eng.tie_order = "torch"
     with pytest.warns(RuntimeWarning):
         switched = step(eng)
-    assert len(eng._det_sites["bwd"]) == n_sites and not [k for k in eng._det_sites["bwd"] if k[0] == "tok" and len(k) != 2]
+    assert len(eng.sites.items("bwd")) == n_sites and not [k for k, _ in eng.sites.items("bwd") if k[0] == "tok" and len(k) != 2]
     model._engine = None
     fresh = model.engine(B, dev, loss="l2_norm", deterministic=True)
     fresh.use_graphs, fresh.tie_order = False, "torch"

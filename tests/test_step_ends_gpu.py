@@ -477,7 +477,7 @@ def _poison_partials(eng) -> int:
     """NaN into every partial-row buffer of the ends: a launch that a later step (a graph replay) leaves out, or a job that reads
     a row nobody wrote, then shows up as NaN in a gradient instead of repeating the previous step's value."""
     bufs = [b.get(k) for b in eng.mb.values() for k in ("drec_cs", "dyc_cs")] + [gb.get("e2d_cs") for gb in eng.gb.values()]
-    bufs = [t for t in bufs + list(eng._ends_ws.values()) if t is not None]
+    bufs = [t for t in bufs + list(eng.sites.buffers()) if t is not None]
     for t in bufs:
         t.fill_(float("nan"))
     return len(bufs)
@@ -525,8 +525,8 @@ def test_ends_gradients_match_deterministic_mode(golden_dir, name):
     batch, B = {k: v.to(dev) for k, v in batch.items()}, case["B"]  # noqa: N806
     want = _det_reference(model, B, dev, batch, noise, struct)
     eng = model.engine(B, dev, loss="l2_norm", deterministic=False)
-    assert not eng.deterministic and eng.ends_parts == frozenset("abc")
     eng.wgrad_mode = "deferred"
+    assert not eng.deterministic and eng._ends_on()
     for step in range(3):
         eng.forward(batch, noise=noise, struct=struct)
         eng.zero_grad()
