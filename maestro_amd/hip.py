@@ -905,11 +905,22 @@ def head_linear_bwd(x, W, dout, dx, dW, db, B, C, E):  # noqa: N803
     call("mh_head_linear_bwd", x, W, dout, dx, dW, db, _I(B), _I(C), _I(E))
 
 
+def integer_targets(target: torch.Tensor) -> torch.Tensor:
+    """Class-id targets as the kernels read them: signed integers of 1, 2, 4 or 8 bytes (``load_int`` sign-extends, so a ``uint8``
+    id of 128 or more, or ``missing_val = 255``, would arrive negative).  Signed tensors pass without a copy; unsigned, bool and
+    anything else are widened with ``.long()``, the reference's own cast (``base.py:113-118``)."""
+    if target.dtype in (torch.int8, torch.int16, torch.int32, torch.int64):
+        return target.contiguous()
+    return target.long().contiguous()
+
+
 def count_valid(target, missing_val, count):
+    target = integer_targets(target)
     call("mh_count_valid", target, _I(target.element_size()), _L(target.numel()), _L(int(missing_val)), count)
 
 
 def ce_loss(logits, target, missing_val, n_valid, acc, dlogits, B, g, P, C, ld=None):  # noqa: N803
+    target = integer_targets(target)
     call("mh_ce_loss", logits, target, _I(target.element_size()), _L(int(missing_val)), n_valid, acc, dlogits,
          _I(1 if dlogits.dtype == torch.float32 else 0), _I(B), _I(g), _I(P), _I(C), _I(P * P * C if ld is None else ld))
 
@@ -922,6 +933,7 @@ def confusion_ce(logits, target, missing_val, cm, B, g, P, C, ld=None):  # noqa:
     """``cm[t, argmax]`` += 1 over the valid pixels (int64 ``[C, C]``; operands as ``ce_loss``; include/maestro_hip.h)."""
     if cm.dtype != torch.int64 or cm.numel() != C * C or not cm.is_contiguous():
         raise HipExtensionError(f"confusion_ce: cm must be a contiguous int64 [{C}, {C}] tensor")
+    target = integer_targets(target)
     call("mh_confusion_ce", logits, target, _I(target.element_size()), _L(int(missing_val)), cm, _I(B), _I(g), _I(P), _I(C),
          _I(P * P * C if ld is None else ld))
 

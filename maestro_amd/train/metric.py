@@ -60,11 +60,7 @@ def _gathered_rows(rows: torch.Tensor) -> torch.Tensor:
     return torch.cat([p[:n] for p, n in zip(parts, lens)])
 
 
-def _integer_targets(targets: torch.Tensor) -> torch.Tensor:
-    """Signed integers of 1, 2, 4 or 8 bytes for the kernel (``targets.long()``, ``base.py:113-118``, only where needed)."""
-    if targets.dtype in (torch.int8, torch.int16, torch.int32, torch.int64):
-        return targets.contiguous()
-    return targets.long().contiguous()
+_integer_targets = hip.integer_targets     # the one widening rule, shared with hip.count_valid / ce_loss / confusion_ce
 
 
 class MonoLabelMetric(nn.Module):

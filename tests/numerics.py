@@ -13,6 +13,9 @@ tests/test_numerics_gpu.py (the HIP kernels against the same bounds).  Nothing h
   reduction in wave order, ``wave_two_pass_stats``) against fp64 on the very inputs of the case.
 * Attention (``attn_bounds``): a first-order propagation of every rounding of csrc/attn.hip through softmax and its gradient; the
   derivation stands in front of the function, the measured slack in profiles/attn_numerics.md.
+* AdamW (``adamw_bounds``): a first-order propagation of the roundings of ``adamw_update`` (csrc/loss.hip) through the moments, the
+  square root and the quotient; used by tests/test_adamw_numerics_gpu.py, checked on the CPU by tests/test_step_end_selfcheck.py,
+  measured in profiles/step_end_numerics.md.
 """
 
 from __future__ import annotations
@@ -510,3 +513,161 @@ def attn_criterion_b(got, emulated, want64, bound):
     e_got = float((got.double() - want64).norm())
     e_emu = float((emulated.double().to(want64.device) - want64).norm())
     return e_emu >= B_FLOOR * float(bound.norm()), e_got, e_emu
+
+
+# ------------------------------------------------------------------------------------------------ AdamW
+# One step of csrc/loss.hip's adamw_update on fp32 p, g, m, v with fp32 scalars (the ABI takes floats):
+#   g' = g gs;  p1 = p (1 - lr wd);  m' = b1 m + (1 - b1) g';  v' = b2 v + (1 - b2) g'^2
+#   denom = sqrt(v') / bc2_sqrt + eps;  step = (lr / bc1) (m' / denom);  p' = p1 - step
+# Error model (u = 2^-24, FL = 2^-126; correctly rounded / and sqrtf: hipcc's default, build.py passes no fast-math flag):
+#   m'     two products of an fp32 g' (one rounding inside), one sum, fused or not: 4u on the magnitudes        -> dm
+#   v'     g'^2 carries 2u from g', the products and the sum three more: 5u v' (all terms are non-negative)      -> dv
+#   sqrt   |sqrt(a) - sqrt(b)| <= min(|a - b| / (2 sqrt b), sqrt |a - b|), and one rounding                     -> dsqrt
+#   denom  the division by bc2_sqrt and the sum with eps                                                        -> ddenom
+#   step   first order in dm and ddenom; lr / bc1, m' / denom and their product round once each                 -> dstep
+#   p'     1 - lr wd (two roundings) and the product: 3u |p|; the final subtraction: u |p'|                     -> dp
+# FL wherever an fp32 result may underflow (g'^2 at |g'| of order 1e-25 does).
+ADAMW_KINDS = ("unit", "tiny", "huge", "zero", "cancel", "bigp", "p0", "under")
+ADAMW_STEPS = ((1, 0.999), (2, 0.95), (1000, 0.999), (100000, 0.999))      # (step, b2)
+ADAMW_HYPER = dict(lr=1e-3, b1=0.9, eps=1e-8, wd=0.05, grad_scale=1.0 / 3.0)
+ADAMW_WRONG_BC = ("eps_inside_div", "no_bc1", "no_bc2")   # forms that differ from the honest one through a bias correction only
+ADAMW_WRONG = ADAMW_WRONG_BC + ("eps_in_sqrt", "wd_after", "wd_l2")
+
+
+def f32(x: float) -> float:
+    """The fp32 value a C float argument receives."""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def adamw_inputs(kind: str, n: int, b1: float = 0.9, grad_scale: float = 1.0 / 3.0, seed: int = 0):
+    """fp32 CPU ``(p, g, m, v)`` [n].  kinds: ``unit``; ``tiny`` (g gs, m of order 1e-6: sqrt(v) is of the order of eps); ``huge``
+    (1e4); ``zero`` (g = m = v = 0); ``cancel`` (b1 m = -(1 - b1) g gs up to 2^-10 relative); ``bigp`` (|p| of order 1e3); ``p0``
+    (p = 0: the bound on p is the bound on the step); ``under`` (|g| of order 1e-25: g^2 underflows)."""
+    gen = torch.Generator().manual_seed(6700417 * seed + n + 101 * ADAMW_KINDS.index(kind))
+    r = lambda: torch.randn(n, generator=gen)  # noqa: E731
+    p, g, m, v = r(), r() / grad_scale, 0.3 * r(), r() ** 2 + 0.01
+    if kind == "tiny":
+        g, m, v = 1e-6 * g, 1e-6 * m, 1e-12 * v
+    elif kind == "huge":
+        g, m, v = 1e4 * g, 1e4 * m, 1e8 * v
+    elif kind == "zero":
+        g, m, v = torch.zeros(n), torch.zeros(n), torch.zeros(n)
+    elif kind == "cancel":
+        g = -(b1 * m) / ((1.0 - b1) * grad_scale) * (1.0 + 2.0 ** -10 * r())
+    elif kind == "bigp":
+        p = 1e3 * p
+    elif kind == "p0":
+        p = torch.zeros(n)
+    elif kind == "under":
+        g, m, v = 1e-25 * g, 1e-25 * m, torch.zeros(n)
+    elif kind != "unit":
+        raise ValueError(kind)
+    return p.float().contiguous(), g.float().contiguous(), m.float().contiguous(), v.float().contiguous()
+
+
+def adamw_step64(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale):
+    """fp64 arithmetic on the fp32-valued inputs and the fp32-rounded scalars; returns the dict p, m, v, step, denom, p1."""
+    lr, b1, b2, eps, wd, bc1, bc2_sqrt, gs = (f32(x) for x in (lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale))
+    p, g, m, v = (t.double() for t in (p, g, m, v))
+    gg = g * gs
+    p1 = p * (1.0 - lr * wd)
+    m1 = b1 * m + (1.0 - b1) * gg
+    v1 = b2 * v + (1.0 - b2) * gg * gg
+    denom = torch.sqrt(v1) / bc2_sqrt + eps
+    step = (lr / bc1) * (m1 / denom)
+    return dict(p=p1 - step, m=m1, v=v1, step=step, denom=denom, p1=p1, bm=(b1 * m).abs() + ((1.0 - b1) * gg).abs(), p0=p,
+                lr_bc1=lr / bc1, bc2_sqrt=bc2_sqrt)
+
+
+def adamw_bounds(ref):
+    """Elementwise bounds (dict: p, m, v, step) for ``ref = adamw_step64(...)``; the derivation stands above."""
+    u, FL = U_F32, FLUSH_F32  # noqa: N806
+    dm = 4 * u * ref["bm"] + FL
+    dv = 5 * u * ref["v"] + FL
+    sq = torch.sqrt(ref["v"])
+    dsqrt = torch.minimum(dv / (2 * sq), torch.sqrt(dv)) + u * sq
+    denom = ref["denom"]
+    ddenom = dsqrt / ref["bc2_sqrt"] + 2 * u * denom
+    dstep = ref["lr_bc1"] * (dm / denom + ref["m"].abs() * ddenom / denom ** 2) + 3 * u * ref["step"].abs() + FL
+    dp = 3 * u * ref["p0"].abs() + dstep + u * ref["p"].abs() + FL
+    return dict(p=dp, m=dm, v=dv, step=dstep)
+
+
+def adamw_emulated(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, fma: bool = False, form: str = "honest"):
+    """fp32 torch written as ``adamw_update`` (csrc/loss.hip) is; returns ``(p, m, v)``.  ``fma``: the moments and the final
+    subtraction as the compiler may contract them (one rounding for a product and its sum).  ``form``: "honest", or one of
+    ADAMW_WRONG -- eps inside the division by bc2_sqrt, eps inside the square root, a missing bc1 or bc2, weight decay applied
+    after the step, weight decay on the gradient (L2)."""
+    assert form == "honest" or form in ADAMW_WRONG, form
+    t = lambda x: torch.tensor(x, dtype=torch.float32)  # noqa: E731
+    lr, b1, b2, eps, wd, bc1, bc2_sqrt, gs = (t(x) for x in (lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale))
+    one = t(1.0)
+    p, g, m, v = p.float(), g.float() * gs, m.float(), v.float()
+    if form == "wd_l2":
+        g = g + wd * p
+    elif form != "wd_after":
+        p = p * (one - lr * wd)
+    if fma:
+        m = _fma32(b1.expand_as(m), m, -((one - b1) * g))
+        v = _fma32((one - b2) * g, g, -(b2 * v))
+    else:
+        m = b1 * m + (one - b1) * g
+        v = b2 * v + (one - b2) * g * g
+    if form == "no_bc1":
+        bc1 = one
+    if form == "no_bc2":
+        bc2_sqrt = one
+    if form == "eps_inside_div":
+        denom = (torch.sqrt(v) + eps) / bc2_sqrt
+    elif form == "eps_in_sqrt":
+        denom = torch.sqrt(v / (bc2_sqrt * bc2_sqrt) + eps)
+    else:
+        denom = torch.sqrt(v) / bc2_sqrt + eps
+    q = m / denom
+    p = -_fma32((lr / bc1).expand_as(q), q, p) if fma else p - (lr / bc1) * q
+    if form == "wd_after":
+        p = p * (one - lr * wd)
+    return p, m, v
+
+
+ADAMW_TRAJ_STEPS = 20
+
+
+def adamw_trajectory_case(n: int = 4100, steps: int = ADAMW_TRAJ_STEPS):
+    """``steps`` AdamW steps from zero moments on a fixed gradient sequence that shrinks from 1 to 1e-6 (grad_scale 1, the other
+    scalars of ADAMW_HYPER, b2 = 0.999).  Returns the dict: ``p0`` [n], ``grads`` [steps, n] (fp32 CPU), ``hyper``, the fp64
+    trajectory's end ``ref`` = (p, m, v), and the ends of three fp32 trajectories: ``torch`` (torch.optim.AdamW on the CPU),
+    ``emulated`` and ``emulated_fma`` (``adamw_emulated``)."""
+    from maestro_amd import hip
+    gen = torch.Generator().manual_seed(271828)
+    p0 = torch.randn(n, generator=gen)
+    shape = torch.randn(n, generator=gen)
+    grads = torch.stack([shape * 10.0 ** (-6.0 * t / (steps - 1)) * (1.0 + 0.25 * torch.randn(n, generator=gen)) for t in range(steps)])
+    h = dict(ADAMW_HYPER, b2=0.999, grad_scale=1.0)
+    bcs = [hip.adamw_bias_corrections(h["b1"], h["b2"], t + 1) for t in range(steps)]
+    args = lambda t: (h["lr"], h["b1"], h["b2"], h["eps"], h["wd"], bcs[t][0], bcs[t][1], 1.0)  # noqa: E731
+    z = torch.zeros(n)
+    ref = (p0.double(), z.double(), z.double())
+    emu, emu_fma = (p0.clone(), z.clone(), z.clone()), (p0.clone(), z.clone(), z.clone())
+    for t in range(steps):
+        r = adamw_step64(*ref[:1], grads[t], *ref[1:], *args(t))
+        ref = (r["p"], r["m"], r["v"])
+        emu = adamw_emulated(emu[0], grads[t], emu[1], emu[2], *args(t))
+        emu_fma = adamw_emulated(emu_fma[0], grads[t], emu_fma[1], emu_fma[2], *args(t), fma=True)
+    pt = torch.nn.Parameter(p0.clone())
+    opt = torch.optim.AdamW([pt], lr=h["lr"], betas=(h["b1"], h["b2"]), eps=h["eps"], weight_decay=h["wd"], foreach=False)
+    for t in range(steps):
+        pt.grad = grads[t].clone()
+        opt.step()
+    st = opt.state[pt]
+    return dict(p0=p0, grads=grads, hyper=h, steps=steps, ref=ref, torch=(pt.detach(), st["exp_avg"], st["exp_avg_sq"]),
+                emulated=emu, emulated_fma=emu_fma)
+
+
+def adamw_trajectory_errors(case, got):
+    """``{p, m, v: (max |got - fp64|, norm_ceiling of the two references' errors)}``."""
+    out = {}
+    for i, k in enumerate("pmv"):
+        want = case["ref"][i]
+        out[k] = (max_abs_err(got[i].cpu(), want), norm_ceiling(max_abs_err(case["torch"][i], want), max_abs_err(case["emulated"][i], want)))
+    return out

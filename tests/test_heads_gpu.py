@@ -140,6 +140,50 @@ def test_cross_entropy_patch_layout(B, g, P, C, missing, tdtype):  # noqa: N803
     assert cnt.item() == 0 and acc.item() == 0.0 and float(d.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("C,missing", [(130, -1), (19, 255)], ids=["ids_to_129", "missing_255"])
+def test_cross_entropy_unsigned_byte_targets(C, missing):  # noqa: N803
+    """``uint8`` rasters whose bytes have the top bit set: class ids up to 129, or ``missing_val = 255``.  The kernels read a
+    1-byte target as signed (include/maestro_hip.h), so the wrappers widen unsigned tensors first; the reference is
+    ``F.cross_entropy`` on the widened targets.  Signed tensors still reach the kernel as they are."""
+    from maestro_amd import hip
+    dev = _dev()
+    B, g, P = 3, 2, 4  # noqa: N806
+    S = g * P  # noqa: N806
+    gen = torch.Generator().manual_seed(C + 7)
+    patch = torch.randn(B * g * g, P * P * C, generator=gen) * 2
+    target = torch.randint(0, C, (B, S, S), generator=gen)
+    target.view(-1)[:C] = torch.arange(C)                       # every id is there, 128 and 129 too where C = 130
+    if missing >= 0:
+        target[torch.rand(B, S, S, generator=gen) < 0.25] = missing
+    t8 = target.to(torch.uint8)
+    assert torch.equal(t8.long(), target) and int(t8.max()) >= (128 if missing < 0 else 255)
+    img = patch.reshape(B, g, g, P, P, C).permute(0, 5, 1, 3, 2, 4).reshape(B, C, S, S).clone().requires_grad_(True)
+    lg, tg = img.permute(0, 2, 3, 1).reshape(-1, C), target.reshape(-1)
+    idx = (tg != missing).nonzero().squeeze(1)
+    want = F.cross_entropy(lg.index_select(0, idx), tg.index_select(0, idx))
+    want.backward()
+    ref = img.grad.reshape(B, C, g, P, g, P).permute(0, 2, 4, 3, 5, 1).reshape(B * g * g, P * P * C)
+    t_dev = t8.to(dev)
+    cnt, acc = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, device=dev)
+    hip.count_valid(t_dev, missing, cnt)
+    assert cnt.item() == len(idx)
+    d = torch.full((B * g * g, P * P * C), float("nan"), device=dev)
+    hip.ce_loss(patch.to(dev), t_dev, missing, cnt, acc, d, B, g, P, C)
+    assert abs(acc.item() - want.item()) < 1e-4 * abs(want.item())
+    assert (d.cpu() - ref).abs().max() <= 1e-6
+    if missing == 255:      # (mh_confusion_ce takes at most 128 classes) missing pixels stay out of the confusion matrix too
+        cm = torch.zeros(C, C, dtype=torch.int64, device=dev)
+        hip.confusion_ce(patch.to(dev), t_dev, missing, cm, B, g, P, C)
+        want_cm = torch.zeros(C, C, dtype=torch.int64)
+        want_cm.index_put_((tg[idx], lg.detach()[idx].argmax(1)), torch.ones(len(idx), dtype=torch.int64), accumulate=True)
+        assert torch.equal(cm.cpu(), want_cm)
+    # widening: unsigned and bool tensors are copied to int64, signed ones pass through as the same storage
+    assert hip.integer_targets(t_dev).dtype == torch.int64 and hip.integer_targets(t_dev.bool()).dtype == torch.int64
+    for dt in (torch.int8, torch.int16, torch.int32, torch.int64):
+        s = torch.zeros(4, dtype=dt, device=dev)
+        assert hip.integer_targets(s).data_ptr() == s.data_ptr()
+
+
 def test_bce_with_missing_rows():
     from maestro_amd import hip
     dev = _dev()
