@@ -56,6 +56,12 @@ def lib() -> ctypes.CDLL:
         _lib.mh_select_dates.restype = ci
         _lib.mh_mask_draw.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_longlong, vp]   # device-side draws
         _lib.mh_mask_draw.restype = ci                                      # (include/maestro_hip_rng.h)
+        cl, cf = ctypes.c_long, ctypes.c_float                              # gradient guard (include/maestro_hip_guard.h)
+        _lib.mh_grad_sumsq_partial_rows.argtypes = [cl]
+        _lib.mh_grad_sumsq_partial_rows.restype = cl
+        _lib.mh_grad_sumsq_partial.argtypes = [vp, cl, vp, vp, vp]
+        _lib.mh_grad_guard_finish.argtypes = [vp, vp, cl, cf, cf, ci, cf, cf, cf, vp, vp, vp]
+        _lib.mh_grad_sumsq_partial.restype = _lib.mh_grad_guard_finish.restype = ci
     return _lib
 
 
@@ -573,6 +579,109 @@ def mask_draw_reference(groups, mods, B, seed, step, row_base=0):  # noqa: N803
     ``MAEEngine.draw_masks()`` (the restatement lives next to the host drawer, ``layers.utils.mask_draw_reference``)."""
     from maestro_amd.layers.utils import mask_draw_reference as reference
     return reference(groups, mods, B, seed, step, row_base)
+
+
+# ---- gradient guard (include/maestro_hip_guard.h)
+GUARD_CHUNK = 16384     # MH_GUARD_CHUNK
+
+
+class _MhGuardState(ctypes.Structure):
+    _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("finite", ctypes.c_int), ("bad", ctypes.c_uint),
+                ("t", ctypes.c_longlong), ("skipped", ctypes.c_longlong)]
+
+
+def grad_sumsq_partial_rows(n) -> int:
+    return int(lib().mh_grad_sumsq_partial_rows(_L(n)))
+
+
+def grad_sumsq_partial(g, n, partial, bad):
+    """First phase of the guard: ``partial[i]`` = sum of squares, ``bad[i]`` = inf / NaN count of chunk ``i`` of ``g[:n]`` (f32,
+    16-byte aligned, ``n % 4 == 0``); ``partial`` f32 / ``bad`` int32 of ``grad_sumsq_partial_rows(n)`` rows, plain stores."""
+    _hbm_call("grad_sumsq", 4.0 * n, "mh_grad_sumsq_partial", g, _L(n), partial, bad)
+
+
+def grad_guard_finish(partial, bad, rows, grad_scale, max_norm, skip_nonfinite, lr, b1, b2, hyper, state):
+    """Second phase: the partials -> ``hyper`` (the five device scalars of ``adamw_dev``) and the 32-byte ``MhGuardState``."""
+    call("mh_grad_guard_finish", partial, bad, _L(rows), _F(grad_scale), _F(max_norm), _I(1 if skip_nonfinite else 0), _F(lr), _F(b1),
+         _F(b2), hyper, state)
+
+
+class GradGuard:
+    """Device-side global gradient norm, clipping coefficient and non-finite skip over a flat f32 gradient of ``n`` elements
+    (include/maestro_hip_guard.h).  Owns the partial rows, the five scalars ``hyper`` that ``adamw_dev`` reads and the device
+    ``MhGuardState`` (Adam's step count ``t`` lives THERE: a skipped step does not advance it).  ``launch`` issues the two
+    kernels; ``norm`` / ``coef`` / ``hyper`` are device views, nothing on the step path reads them on the host.  ``max_norm``
+    None or <= 0: no clipping.  No atomics and one fixed order of additions: the same gradient gives the same bits."""
+
+    def __init__(self, n: int, device, max_norm: float | None = None, skip_nonfinite: bool = True) -> None:
+        n = int(n)
+        if n <= 0 or n % 4:
+            raise HipExtensionError(f"GradGuard: n {n} must be positive and a multiple of 4")
+        if torch.device(device).type != "cuda":
+            raise HipExtensionError("GradGuard needs a GPU (no CPU fallback)")
+        self.n, self.max_norm, self.skip_nonfinite = n, float(max_norm or 0.0), bool(skip_nonfinite)
+        self.rows = grad_sumsq_partial_rows(n)
+        self.partial = torch.zeros(self.rows, dtype=torch.float32, device=device)
+        self.bad = torch.zeros(self.rows, dtype=torch.int32, device=device)
+        self.hyper = torch.zeros(5, dtype=torch.float32, device=device)
+        self.state = torch.zeros(ctypes.sizeof(_MhGuardState), dtype=torch.uint8, device=device)
+        self.norm = self.state[0:4].view(torch.float32)
+        self.coef = self.state[4:8].view(torch.float32)
+        self._counters = self.state[16:32].view(torch.int64)      # t, skipped
+
+    def launch(self, grad, lr: float, b1: float, b2: float, grad_scale: float = 1.0) -> None:
+        if grad.dtype != torch.float32 or grad.numel() != self.n or not grad.is_contiguous():
+            raise HipExtensionError(f"GradGuard.launch: a dense f32 gradient of {self.n} elements expected")
+        grad_sumsq_partial(grad, self.n, self.partial, self.bad)
+        grad_guard_finish(self.partial, self.bad, self.rows, grad_scale, self.max_norm, self.skip_nonfinite, lr, b1, b2,
+                          self.hyper, self.state)
+
+    def stats(self) -> dict:
+        """ONE host read (synchronises): the state of the last launch."""
+        s = _MhGuardState.from_buffer_copy(bytes(self.state.cpu().numpy()))
+        return {"norm": float(s.norm), "coef": float(s.coef), "finite": bool(s.finite), "bad": int(s.bad), "t": int(s.t),
+                "skipped": int(s.skipped)}
+
+    def state_dict(self) -> dict:
+        t, skipped = self._counters.tolist()
+        return {"t": int(t), "skipped": int(skipped)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """``t`` and, when given, ``skipped`` (otherwise the count stays)."""
+        skipped = int(sd["skipped"]) if "skipped" in sd else int(self._counters[1])
+        self._counters.copy_(torch.tensor([int(sd["t"]), skipped], dtype=torch.int64))
+
+
+def grad_guard_reference(g, grad_scale, max_norm, skip_nonfinite, lr, b1, b2, t, skipped):
+    """The contract of ``mh_grad_sumsq_partial`` + ``mh_grad_guard_finish`` restated in numpy / fp64 (runs on any machine; the
+    tests compare the kernels against it).  ``g``: the flat gradient (array or CPU tensor); ``t`` / ``skipped``: the state's
+    counters before the call.  Returns ``partial`` (fp64, per chunk, exact up to fp64), ``bad_rows``, ``S`` (the sum of the
+    partials AS f32 rows: a chunk whose sum overflows fp32 is inf, as on the device), ``norm`` / ``coef`` (float32), ``bad``,
+    ``finite``, ``apply``, ``t`` / ``skipped`` after the call and ``hyper`` (float32[5])."""
+    import numpy as np
+    g = g.detach().cpu().numpy() if isinstance(g, torch.Tensor) else np.asarray(g)
+    g = g.astype(np.float32).ravel()
+    f32, f64 = np.float32, np.float64
+    rows = -(-g.size // GUARD_CHUNK)
+    pad = np.zeros(rows * GUARD_CHUNK, dtype=f64)
+    with np.errstate(all="ignore"):
+        pad[: g.size] = g.astype(f64) ** 2
+        partial = pad.reshape(rows, GUARD_CHUNK).sum(axis=1)
+        bad_rows = np.zeros(rows * GUARD_CHUNK, dtype=np.int64)
+        bad_rows[: g.size] = ~np.isfinite(g)
+        bad_rows = bad_rows.reshape(rows, GUARD_CHUNK).sum(axis=1)
+        S = partial.astype(f32).astype(f64).sum()  # noqa: N806
+        norm = f32(abs(f64(f32(grad_scale))) * np.sqrt(S))
+        bad = int(min(int(bad_rows.sum()), 0xFFFFFFFF))
+        finite = bool(np.isfinite(norm)) and bad == 0
+        max_norm = f32(max_norm or 0.0)
+        coef = min(f32(1.0), f32(max_norm / f32(norm + f32(1e-6)))) if (max_norm > 0 and finite) else f32(1.0)
+    apply = finite or not skip_nonfinite
+    t, skipped = (int(t) + 1, int(skipped)) if apply else (int(t), int(skipped) + 1)
+    hyper = np.array([f32(lr), f32(1.0 - f64(f32(b1)) ** t), f32(np.sqrt(1.0 - f64(f32(b2)) ** t)), f32(grad_scale) * f32(coef),
+                      1.0 if apply else 0.0], dtype=f32)
+    return {"partial": partial, "bad_rows": bad_rows, "S": S, "norm": norm, "coef": f32(coef), "bad": bad, "finite": finite,
+            "apply": apply, "t": t, "skipped": skipped, "hyper": hyper}
 
 
 def colsum_partial_rows(M) -> int:  # noqa: N803

@@ -311,6 +311,30 @@ class SSLModule(_Base):
         return {"optimizer": optimizer,
                 "lr_scheduler": {"scheduler": scheduler, "interval": "step", "name": f"{tr.ssl_phase}_AdamW_lr"}}
 
+    def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning's hook behind ``Trainer(gradient_clip_val=...)``.  The "norm" algorithm (Lightning's default), when an engine
+        owns the parameters and their gradients are the slices of its flat buffer, is ``optim.clip_grad_norm_``: two guard
+        launches + one scaling pass over the flat buffer instead of torch's multi-tensor norm over every parameter view; returns
+        the total norm as a device tensor.  Anything else -- "value", no engine yet, gradients that are not the flat buffer's --
+        falls back to ``torch.nn.utils.clip_grad_norm_`` / ``clip_grad_value_`` on the optimizer's parameters.  The non-finite
+        skip is NOT available here: the optimizer step on this surface is torch's to call."""
+        if gradient_clip_val is None or float(gradient_clip_val) <= 0:
+            return None
+        algorithm = "norm" if gradient_clip_algorithm is None else getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm)
+        params = [p for g in optimizer.param_groups for p in g["params"]]
+        if algorithm != "norm":
+            return torch.nn.utils.clip_grad_value_(params, float(gradient_clip_val))
+        eng = getattr(self.model, "_engine", None) or getattr(self.model, "_sup_engine", None)
+        if eng is not None and not getattr(eng.store, "fresh", True):
+            st = eng.store
+            lo, hi = getattr(eng, "trainable_span", (0, st.total))
+            inside = {id(p) for p in st.params if lo <= st.offset[id(p)] < hi}
+            if all(p.grad is not None and p.grad.data_ptr() == st.g(p).data_ptr() for p in st.params if id(p) in inside) \
+                    and not any(p.grad is not None for p in params if id(p) not in inside):
+                from maestro_amd.train.optim import clip_grad_norm_
+                return clip_grad_norm_(eng, float(gradient_clip_val))
+        return torch.nn.utils.clip_grad_norm_(params, float(gradient_clip_val))
+
     # ------------------------------------------------------------------ steps
     def _ssl_phase(self) -> str:
         return getattr(getattr(self, "trainer", None), "ssl_phase", "pretrain")

@@ -39,8 +39,46 @@ class OneCycle:
         return self._cos(self.max_lr, self.min_lr, (step_num - self.end1) / (self.end2 - self.end1))
 
 
+def resolve_grad_guard(max_grad_norm: float | None = None, skip_nonfinite: bool | None = None) -> tuple[float | None, bool]:
+    """The gradient-guard switches of the loops: explicit values win; None reads ``MAESTRO_MAX_GRAD_NORM`` (a positive float;
+    unset / empty / 0 = no clipping) and ``MAESTRO_SKIP_NONFINITE`` ("1" = on).  Returns ``(max_norm or None, skip)``: a guard
+    exists iff either is set.  A negative or non-finite norm is a ``ValueError``."""
+    import os
+    if max_grad_norm is None:
+        text = os.environ.get("MAESTRO_MAX_GRAD_NORM", "").strip()
+        max_grad_norm = float(text) if text else None
+    if skip_nonfinite is None:
+        skip_nonfinite = os.environ.get("MAESTRO_SKIP_NONFINITE", "0") == "1"
+    if max_grad_norm is not None:
+        max_grad_norm = float(max_grad_norm)
+        if not math.isfinite(max_grad_norm) or max_grad_norm < 0:
+            raise ValueError(f"max_grad_norm={max_grad_norm!r}: expected a finite number >= 0 (0 = no clipping)")
+    return (max_grad_norm or None), bool(skip_nonfinite)
+
+
+def refuse_guard_conflicts(guarded: bool, overlap_optimizer: bool = False, dtype: str | None = None,
+                           exchange_mode: str = "all_reduce") -> None:
+    """What a gradient guard excludes, as ``ValueError``s raised before anything is built."""
+    if not guarded:
+        return
+    if overlap_optimizer:
+        raise ValueError("a gradient guard (max_grad_norm / skip_nonfinite) excludes overlap_optimizer: the update waits for the "
+                         "norm of the whole gradient")
+    if dtype == "fp8":
+        raise ValueError("a gradient guard (max_grad_norm / skip_nonfinite) is not available with dtype='fp8': mh_adamw_fp8 has "
+                         "no device-scalar form")
+    if exchange_mode == "rs_ag":
+        raise ValueError("a gradient guard (max_grad_norm / skip_nonfinite) excludes exchange_mode='rs_ag': a rank holds only "
+                         "its chunks of the reduced gradient there")
+
+
 class FusedAdamW:
-    """One ``mh_adamw`` launch over all trainable parameters; also refreshes the bf16 weight shadows."""
+    """One ``mh_adamw`` launch over all trainable parameters; also refreshes the bf16 weight shadows.
+
+    ``guard`` (a ``hip.GradGuard`` over the trainable span, attribute or ``step`` argument; default None = exactly the launches
+    above): the step becomes norm + finish + ONE ``mh_adamw_dev`` that reads its scalars -- clipping coefficient folded into the
+    gradient scale, ``active`` = 0 on a skipped step -- from the guard; Adam's step count then lives in the guard's device
+    state (``t`` property, ``state_dict``)."""
 
     def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.01) -> None:
         import torch
@@ -53,15 +91,45 @@ class FusedAdamW:
         self.m = torch.zeros(self.hi - self.lo, dtype=st.flat.dtype, device=st.flat.device)
         self.v = torch.zeros_like(self.m)
         self.t = 0
+        self.guard = None
 
-    def step(self, lr: float | None = None, grad_scale: float = 1.0, split: int = 0, between=None) -> None:
+    def _step_guarded(self, guard, lr: float, grad_scale: float, between) -> None:
+        st, lo, hi = self.engine.store, self.lo, self.hi
+        if getattr(self.engine, "fp8", None) is not None:
+            raise ValueError("FusedAdamW.step: a gradient guard is not available with dtype='fp8' (mh_adamw_fp8 has no "
+                             "device-scalar form)")
+        if guard.n != hi - lo:
+            raise hip.HipExtensionError(f"FusedAdamW.step: guard over {guard.n} elements, trainable span of {hi - lo}")
+        self.guard = guard
+        if between is not None:
+            between()
+        guard.launch(st.grad[lo:hi], lr, self.betas[0], self.betas[1], grad_scale)
+        hip.adamw_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], hi - lo, self.betas[0], self.betas[1],
+                      self.eps, self.wd, guard.hyper)
+        st.mark_synced()
+        self.engine._pack_conv_weights()
+
+    def step(self, lr: float | None = None, grad_scale: float = 1.0, split: int = 0, between=None, guard=None) -> None:
         """``split`` / ``between``: update ``[split, hi)`` first, call ``between()`` (e.g. wait for the last gradient bucket),
-        then update ``[lo, split)`` -- the data-parallel loop hides its exposed all-reduce under the first launch."""
+        then update ``[lo, split)`` -- the data-parallel loop hides its exposed all-reduce under the first launch.
+
+        ``guard`` (default: ``self.guard``): ``between()`` runs FIRST -- the norm needs the whole reduced gradient, so the
+        tail-bucket overlap is given up --, then ``guard.launch`` over ``grad[lo:hi]`` and one ``mh_adamw_dev`` over ``[lo, hi)``
+        with ``guard.hyper``.  The gradient buffer is NOT rewritten: the clipping coefficient rides in ``hyper[3]`` next to
+        ``grad_scale``; on a skipped step (``hyper[4] == 0``) the kernel returns before it touches memory, and the shadows and
+        packed weights that are rebuilt afterwards are rebuilt from unchanged masters.  ``ValueError`` with an fp8 plan."""
         import os
         import torch
         roctx = os.environ.get("MAESTRO_ROCTX", "0") == "1"
         if roctx:
             torch.cuda.nvtx.range_push("maestro:adamw")
+        guard = self.guard if guard is None else guard
+        if guard is not None:
+            try:
+                return self._step_guarded(guard, self.lr if lr is None else lr, grad_scale, between)
+            finally:
+                if roctx:
+                    torch.cuda.nvtx.range_pop()
         st = self.engine.store
         self.t += 1
         lr = self.lr if lr is None else lr
@@ -139,6 +207,8 @@ class FusedAdamW:
         # chunks gathered from other ranks go stale), and a deferred / asynchronous checkpoint writer holding them would save a
         # mixed-step Adam state without any error.  ("t" stamps the step the copies belong to.)
         m, v = (self.m.clone(), self.v.clone()) if sharded else (self.m, self.v)
+        if self.guard is not None:     # Adam's step count lives in the guard's device state (a skipped step does not advance it)
+            self.t = self.guard.state_dict()["t"]
         return {"m": m, "v": v, "t": self.t, "lr": self.lr, "span": (self.lo, self.hi),
                 "exchange_mode": "rs_ag" if sharded else "all_reduce", "world": getattr(self, "_sharded_world", 1)}
 
@@ -148,7 +218,27 @@ class FusedAdamW:
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.t, self.lr = sd["t"], sd["lr"]
+        if self.guard is not None:
+            self.guard.load_state_dict({"t": self.t})
         self._gathered = True      # full moments on this rank: under rs_ag the next step simply keeps using its own chunks
+
+
+def clip_grad_norm_(engine, max_norm: float) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` (L2) over the engine's trainable span of the flat gradient buffer, without torch's
+    multi-tensor norm over several hundred views: the two guard launches, then ``mh_scale_dev`` of the span by the device
+    coefficient ``min(1, max_norm / (norm + 1e-6))``.  Returns the total norm as a 0-dim DEVICE tensor (no host read).  This is
+    the one place where the gradient buffer itself is scaled: ``torch.optim`` semantics (the optimizer reads ``p.grad``) demand
+    it; the built-in loops fold the coefficient into AdamW's gradient scale instead.  A non-finite norm leaves the gradients as
+    they are (coefficient 1)."""
+    st = engine.store
+    lo, hi = getattr(engine, "trainable_span", (0, st.total))
+    guard = getattr(engine, "_clip_guard", None)
+    if guard is None or guard.n != hi - lo:
+        guard = engine._clip_guard = hip.GradGuard(hi - lo, st.grad.device, skip_nonfinite=False)
+    guard.max_norm = float(max_norm)
+    guard.launch(st.grad[lo:hi], 0.0, 0.0, 0.0, 1.0)
+    hip.scale_dev(st.grad[lo:hi], hi - lo, guard.coef)
+    return guard.norm.reshape(())
 
 
 class EngineAdamW(torch.optim.AdamW):

@@ -12,7 +12,7 @@ import torch
 
 from maestro_amd.engine import training_warm_passes
 from maestro_amd.train.ddp import GradSync, broadcast_parameters
-from maestro_amd.train.optim import FusedAdamW, OneCycle, scaled_lr
+from maestro_amd.train.optim import FusedAdamW, OneCycle, refuse_guard_conflicts, resolve_grad_guard, scaled_lr
 
 
 def synthetic_batch(dataset, B: int, device, seed: int = 0) -> dict:  # noqa: N803
@@ -29,14 +29,49 @@ def synthetic_batch(dataset, B: int, device, seed: int = 0) -> dict:  # noqa: N8
     return batch
 
 
-class PretrainLoop:
+def _make_guard(opt, device, max_norm, skip):
+    """The loops' gradient guard over the optimizer's trainable span, attached to the optimizer (its ``state_dict`` then takes
+    Adam's step count from the guard's device counter)."""
+    from maestro_amd import hip
+    opt.guard = hip.GradGuard(opt.hi - opt.lo, device, max_norm=max_norm, skip_nonfinite=skip)
+    return opt.guard
+
+
+class _GuardSurface:
+    """``grad_norm`` / ``skipped_steps`` of a loop with a ``guard`` attribute (None: the loop was built without one)."""
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """|grad_scale| * ||g||_2 of the last step's reduced gradient as a 1-element DEVICE tensor (no host read)."""
+        if self.guard is None:
+            raise RuntimeError("grad_norm: the loop has no gradient guard (max_grad_norm / skip_nonfinite)")
+        return self.guard.norm
+
+    @property
+    def skipped_steps(self) -> int:
+        """Number of optimizer steps skipped for a non-finite gradient (ONE host read; 0 without a guard)."""
+        return 0 if self.guard is None else self.guard.stats()["skipped"]
+
+
+class PretrainLoop(_GuardSurface):
     def __init__(self, model, batch_size: int, device, loss: str = "l2_norm", base_lr: float = 3e-5,
                  betas=(0.9, 0.99), weight_decay: float = 0.01, total_steps: int = 1000, world_size: int = 1,
                  final_factor: float = 1e7, bucket_mb: int = 64, exchange: bool | None = None,
                  accumulate: int = 1, overlap_optimizer: bool = False, bucket_dtype=None, dtype: str | None = None,
                  exchange_mode: str | None = None, fp8_scaling: str | None = None, deterministic: bool | None = None,
-                 mask_rng: str | None = None, mask_seed: int = 0, row_base: int | None = None) -> None:
-        """``mask_rng`` ("host" / "device"; None reads ``MAESTRO_MASK_RNG``), ``mask_seed``: where the masks of a step are drawn
+                 mask_rng: str | None = None, mask_seed: int = 0, row_base: int | None = None,
+                 max_grad_norm: float | None = None, skip_nonfinite: bool | None = None) -> None:
+        """``max_grad_norm`` / ``skip_nonfinite`` (None reads ``MAESTRO_MAX_GRAD_NORM`` / ``MAESTRO_SKIP_NONFINITE``, "1" = on): the
+        gradient guard (``hip.GradGuard``, include/maestro_hip_guard.h) -- the global L2 norm of the reduced gradient is taken on
+        the device, the clipping coefficient ``min(1, max_grad_norm / (norm + 1e-6))`` rides in AdamW's gradient scale, and with
+        ``skip_nonfinite`` a step whose gradient holds an inf / NaN (or whose norm overflows) leaves weights, moments and Adam's
+        step count untouched (what Lightning's ``GradScaler`` does under the reference's ``precision="16-mixed"``); the OneCycle
+        position still advances, as Lightning steps its scheduler.  Off by default: without either the step is launch for launch
+        the unguarded one and nothing is allocated.  Excludes ``overlap_optimizer``, ``dtype="fp8"`` and
+        ``exchange_mode="rs_ag"``; allowed in deterministic mode (no atomics, one order of additions).  With the all-reduce exchange the
+        guard waits for every bucket (``sync.finish()``, no split tail); every rank then sees the same reduced buffer and takes the
+        same decision without a collective of its own.  ``loop.grad_norm`` (device tensor), ``loop.skipped_steps`` (one host read).
+        ``mask_rng`` ("host" / "device"; None reads ``MAESTRO_MASK_RNG``), ``mask_seed``: where the masks of a step are drawn
         (``MAEEngine``).  Device draws are a function of ``(mask_seed, step, row_base + sample)``: ``row_base`` is the global index
         of this rank's first sample (default ``rank * batch_size``), and ``state_dict()`` carries ``mask_step`` / ``mask_seed`` so
         that a resumed run sees the masks of the uninterrupted one.
@@ -47,6 +82,9 @@ class PretrainLoop:
         ``dtype="fp8"``): "tensor" or "mx" (maestro_amd/fp8.py); None reads ``MAESTRO_FP8_SCALING``."""
         import os
         self.exchange_mode = exchange_mode or os.environ.get("MAESTRO_EXCHANGE", "all_reduce")
+        max_norm, skip = resolve_grad_guard(max_grad_norm, skip_nonfinite)
+        guarded = max_norm is not None or skip
+        refuse_guard_conflicts(guarded, overlap_optimizer, dtype or os.environ.get("MAESTRO_DTYPE", "bf16"), self.exchange_mode)
         from maestro_amd.engine import resolve_deterministic
         if resolve_deterministic(deterministic):     # refused before anything is built
             if overlap_optimizer:
@@ -61,6 +99,7 @@ class PretrainLoop:
             row_base = (dist.get_rank() if dist.is_available() and dist.is_initialized() else 0) * batch_size
         self.engine.row_base = int(row_base)
         self.engine.warm_passes = training_warm_passes()     # a training entry point: start-up passes on (engine.py: warm_passes)
+        refuse_guard_conflicts(guarded, dtype="fp8" if self.engine.fp8 is not None else "bf16")   # (dtype=None kept an fp8 engine)
         if overlap_optimizer and self.engine.fp8 is not None:
             raise ValueError("overlap_optimizer is not available with dtype='fp8' (the e4m3 weight shadows are rebuilt after the update)")
         broadcast_parameters(self.engine)   # every rank starts from rank 0's weights (what Lightning's DDP wrap does)
@@ -68,6 +107,7 @@ class PretrainLoop:
         self.sched = OneCycle(lr, max(total_steps, 2), pct_start=0.2, div_factor=1000.0,
                               final_div_factor=final_factor / 1000.0)
         self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay)
+        self.guard = _make_guard(self.opt, device, max_norm, skip) if guarded else None
         exchange = world_size > 1 if exchange is None else exchange   # True at world_size 1: one-rank rehearsal of the launch plan
         st = self.engine.store
         # the buffer handed to the exchange ends with the scalar slot that carries the step's loss (first bucket)
@@ -105,6 +145,8 @@ class PretrainLoop:
               "exchange_mode": self.exchange_mode, "world": self.world}
         if self.engine.mask_rng == "device":      # the draws of step t are a function of these two (and of the row index)
             sd.update(mask_step=self.engine.mask_step, mask_seed=self.engine.mask_seed)
+        if self.guard is not None:                # Adam's step count (also in the optimizer's "t") and the skipped steps
+            sd["guard"] = self.guard.state_dict()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -116,6 +158,8 @@ class PretrainLoop:
         self.it = sd["it"]
         if self.engine.mask_rng == "device" and "mask_step" in sd:
             self.engine.mask_step, self.engine.mask_seed = int(sd["mask_step"]), int(sd["mask_seed"])
+        if self.guard is not None and sd.get("guard") is not None:
+            self.guard.load_state_dict(sd["guard"])
         if sd.get("params") is not None:
             self.engine.store.flat.copy_(sd["params"])
             resync_engine(self.engine)
@@ -132,7 +176,7 @@ class PretrainLoop:
                 wait_tail()
             self.engine.defer_step(lr, scale)
         else:
-            self.opt.step(lr=lr, grad_scale=scale, split=split, between=wait_tail)
+            self.opt.step(lr=lr, grad_scale=scale, split=split, between=wait_tail, guard=self.guard)
 
     def step(self, batch) -> torch.Tensor:
         """One optimizer step.  ``batch``: a batch dict, or a list of micro-batch dicts (gradient accumulation, the
@@ -151,6 +195,8 @@ class PretrainLoop:
         eng.backward()
         if self.sync is not None and self.sync.mode == "rs_ag":
             self.opt.step_sharded(self.sync, lr=self.sched.lr(self.it), grad_scale=self.sync.finish())
+        elif self.sync is not None and self.guard is not None:   # the norm needs every bucket: no split tail under a guard
+            self._optimizer_step(self.sync.finish())
         elif self.sync is not None:   # the last bucket (encoder head + patch embed) is reduced under the first AdamW launch
             scale, split, wait_tail = self.sync.finish_split()
             self._optimizer_step(scale, split, wait_tail)
@@ -202,13 +248,17 @@ class PretrainLoop:
         return loss
 
 
-class SupervisedLoop:
+class SupervisedLoop(_GuardSurface):
     """Probe / finetune counterpart of :class:`PretrainLoop` (reference ``base.py:185-224`` around the optimizer step):
-    engine forward (+ ``loss_pred``) -> backward (probe: heads only) -> all-reduce -> fused AdamW on the trainable slice."""
+    engine forward (+ ``loss_pred``) -> backward (probe: heads only) -> all-reduce -> fused AdamW on the trainable slice.
+    ``max_grad_norm`` / ``skip_nonfinite``: the gradient guard of :class:`PretrainLoop`, over the trainable span (probe: the heads
+    only -- what lies below the span is neither normed nor looked at)."""
 
     def __init__(self, model, batch_size: int, device, phase: str = "finetune", base_lr: float = 3e-5, betas=(0.9, 0.99),
                  weight_decay: float = 0.01, total_steps: int = 1000, world_size: int = 1, final_factor: float = 1e7,
-                 bucket_mb: int = 64, exchange: bool | None = None, bucket_dtype=None) -> None:
+                 bucket_mb: int = 64, exchange: bool | None = None, bucket_dtype=None, max_grad_norm: float | None = None,
+                 skip_nonfinite: bool | None = None) -> None:
+        max_norm, skip = resolve_grad_guard(max_grad_norm, skip_nonfinite)      # (refused before anything is built)
         self.engine = model.sup_engine(batch_size, device, phase)
         self.engine.warm_passes = training_warm_passes()
         broadcast_parameters(self.engine)
@@ -216,6 +266,7 @@ class SupervisedLoop:
         self.sched = OneCycle(lr, max(total_steps, 2), pct_start=0.2, div_factor=1000.0,
                               final_div_factor=final_factor / 1000.0)
         self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay)
+        self.guard = _make_guard(self.opt, device, max_norm, skip) if (max_norm is not None or skip) else None
         lo, hi = self.engine.trainable_span
         st = self.engine.store
         exchange = world_size > 1 if exchange is None else exchange
@@ -242,11 +293,13 @@ class SupervisedLoop:
             eng.store.extra[:1].copy_(loss)
             self.sync.begin()
         eng.backward()
-        if self.sync is not None:      # the head of the buffer (reduced last) is exchanged under the first AdamW launch
+        if self.sync is not None and self.guard is not None:      # the norm needs every bucket: no split tail under a guard
+            self.opt.step(lr=self.sched.lr(self.it), grad_scale=self.sync.finish(), guard=self.guard)
+        elif self.sync is not None:      # the head of the buffer (reduced last) is exchanged under the first AdamW launch
             scale, split, wait_tail = self.sync.finish_split()
             self.opt.step(lr=self.sched.lr(self.it), grad_scale=scale, split=split + self.lo if split else 0, between=wait_tail)
         else:
-            self.opt.step(lr=self.sched.lr(self.it), grad_scale=scale)
+            self.opt.step(lr=self.sched.lr(self.it), grad_scale=scale, guard=self.guard)
         self.it += 1
         return loss
 
