@@ -1,5 +1,6 @@
 // Masked reconstruction loss at patch layout + its gradient, bias-gradient column sums, casts, fused AdamW.
 #include "gemm_common.hpp"
+#include "../../include/maestro_hip_optim.h"
 
 namespace {
 
@@ -270,6 +271,40 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, c
     adamw_update(p, g, m, v, pb, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], hyper[3]);
 }
 
+// Parameter groups (include/maestro_hip_optim.h): group_of[i >> 6] names the group of element i, lr_scale / wd are 256-entry
+// tables, so every value of the map byte indexes inside them.  A lane's four elements lie in one 64-element block, a wave spans
+// four blocks: the group is per lane, not per wave.  The map (1 byte per 64 parameters) and the tables (2 KiB) are re-read by every
+// workgroup beside 30 bytes per parameter of nontemporal traffic: PLAIN loads, which the vector L1 serves (nontemporal loads
+// bypass it), while the streams above leave no line behind that could displace them.  lr_g is one explicitly rounded product:
+// what follows in adamw_update sees the float mh_adamw would have been handed for this group.
+__device__ __forceinline__ void adamw_group_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, bf16_t* __restrict__ pb,
+                                                   const uint8_t* __restrict__ group_of, const float* __restrict__ lr_scale,
+                                                   const float* __restrict__ wd, long n, float lr, float b1, float b2, float eps,
+                                                   float bc1, float bc2_sqrt, float gscale) {
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;                      // before the map is read: its last byte is the one of element n - 1
+    const unsigned grp = group_of[i >> 6];
+    const float lr_g = __fmul_rn(lr, lr_scale[grp]);
+    adamw_update(p, g, m, v, pb, n, lr_g, b1, b2, eps, wd[grp], bc1, bc2_sqrt, gscale);
+}
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, bf16_t* __restrict__ pb,
+                                                           const uint8_t* __restrict__ group_of, const float* __restrict__ lr_scale,
+                                                           const float* __restrict__ wd, long n, float lr, float b1, float b2,
+                                                           float eps, float bc1, float bc2_sqrt, float gscale) {
+    adamw_group_update(p, g, m, v, pb, group_of, lr_scale, wd, n, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+}
+__global__ __launch_bounds__(256) void adamw_groups_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ pb,
+                                                               const uint8_t* __restrict__ group_of,
+                                                               const float* __restrict__ lr_scale, const float* __restrict__ wd,
+                                                               long n, float b1, float b2, float eps,
+                                                               const float* __restrict__ hyper) {
+    if (hyper[4] == 0.f) return;
+    adamw_group_update(p, g, m, v, pb, group_of, lr_scale, wd, n, hyper[0], b1, b2, eps, hyper[1], hyper[2], hyper[3]);
+}
+
 // x *= *scale, skipped when the device scalar is exactly 1 (loss.backward() with autograd's default ones gradient): the
 // Lightning bridge scales the flat gradient buffer by d loss without reading the scalar on the host.
 __global__ __launch_bounds__(256) void scale_dev_kernel(float* __restrict__ x, long n, const float* __restrict__ scale) {
@@ -456,6 +491,36 @@ extern "C" int mh_adamw_dev(float* p, const float* g, float* m, float* v, void* 
     MH_CHECK_ARG(p && g && m && v && hyper && n > 0 && n % 4 == 0, "mh_adamw_dev: bad arguments (n %% 4 == 0)");
     hipLaunchKernelGGL(adamw_dev_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
                        n, b1, b2, eps, wd, hyper);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+static bool adamw_groups_aligned(const void* p, const void* g, const void* m, const void* v, const void* p_bf16) {
+    return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16) == 0 && ((uintptr_t)p_bf16 % 8) == 0;
+}
+
+extern "C" int mh_adamw_groups(float* p, const float* g, float* m, float* v, void* p_bf16, const unsigned char* group_of,
+                               const float* lr_scale, const float* wd, long n, float lr, float b1, float b2, float eps, int step,
+                               float grad_scale, void* stream) {
+    MH_CHECK_ARG(p && g && m && v && n > 0 && n % 4 == 0 && step >= 1, "mh_adamw_groups: bad arguments (n %% 4 == 0, step >= 1)");
+    MH_CHECK_ARG(group_of && lr_scale && wd, "mh_adamw_groups: the group map and both tables are required (null pointer)");
+    MH_CHECK_ARG(adamw_groups_aligned(p, g, m, v, p_bf16), "mh_adamw_groups: p, g, m, v must be 16-byte, p_bf16 8-byte aligned");
+    const float bc1 = 1.f - powf(b1, (float)step);
+    const float bc2_sqrt = sqrtf(1.f - powf(b2, (float)step));
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
+                       group_of, lr_scale, wd, n, lr, b1, b2, eps, bc1, bc2_sqrt, grad_scale);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_adamw_groups_dev(float* p, const float* g, float* m, float* v, void* p_bf16, const unsigned char* group_of,
+                                   const float* lr_scale, const float* wd, long n, float b1, float b2, float eps,
+                                   const float* hyper, void* stream) {
+    MH_CHECK_ARG(p && g && m && v && hyper && n > 0 && n % 4 == 0, "mh_adamw_groups_dev: bad arguments (n %% 4 == 0)");
+    MH_CHECK_ARG(group_of && lr_scale && wd, "mh_adamw_groups_dev: the group map and both tables are required (null pointer)");
+    MH_CHECK_ARG(adamw_groups_aligned(p, g, m, v, p_bf16), "mh_adamw_groups_dev: p, g, m, v must be 16-byte, p_bf16 8-byte aligned");
+    hipLaunchKernelGGL(adamw_groups_dev_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16_t*)p_bf16, group_of, lr_scale, wd, n, b1, b2, eps, hyper);
     MH_LAUNCH_CHECK();
     return 0;
 }

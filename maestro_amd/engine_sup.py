@@ -21,6 +21,21 @@ from maestro_amd import hip
 from maestro_amd.engine import BF16, F32, I32, EngineBase, ParamStore, Stack
 
 
+def ordered_parameters(m):
+    """``(ordered, head_params)``: the named parameters of the probe / finetune model in the order of the flat store -- patch
+    embeds, per-modality / per-group encoders, the joint encoder, heads last -- and the heads' entries alone.  The names are
+    those of ``model.named_parameters()``; the layer rule of ``train/optim.py`` reads them."""
+    ordered = []
+    for name in m.patch_embed:
+        ordered += [(f"patch_embed.{name}.{k}", p) for k, p in m.patch_embed[name].named_parameters()]
+    for name in m.encoder:
+        ordered += [(f"encoder.{name}.{k}", p) for k, p in m.encoder[name].named_parameters()]
+    if m.encoder_inter is not None:
+        ordered += [(f"encoder_inter.{k}", p) for k, p in m.encoder_inter.named_parameters()]
+    head_params = [(f"heads.{t}.{k}", p) for t in m.heads for k, p in m.heads[t].named_parameters()]
+    return ordered + head_params, head_params
+
+
 class SupervisedEngine(EngineBase):
     def __init__(self, model, batch_size: int, device, phase: str = "finetune", deterministic: bool = False) -> None:
         if phase not in ("probe", "finetune"):
@@ -54,15 +69,7 @@ class SupervisedEngine(EngineBase):
             off += self.Lb[g.name]
         self.JL = off
         # ---- flat parameter store: encoder side first, heads last (probe trains the contiguous tail only)
-        ordered = []
-        for name in m.patch_embed:
-            ordered += [(f"patch_embed.{name}.{k}", p) for k, p in m.patch_embed[name].named_parameters()]
-        for name in m.encoder:
-            ordered += [(f"encoder.{name}.{k}", p) for k, p in m.encoder[name].named_parameters()]
-        if m.encoder_inter is not None:
-            ordered += [(f"encoder_inter.{k}", p) for k, p in m.encoder_inter.named_parameters()]
-        head_params = [(f"heads.{t}.{k}", p) for t in m.heads for k, p in m.heads[t].named_parameters()]
-        ordered += head_params
+        ordered, head_params = ordered_parameters(m)
         self.store = ParamStore(ordered, device)
         lo, _ = self.store.span([p for _, p in head_params])
         self.trainable_span = (lo, self.store.total) if phase == "probe" else (0, self.store.total)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from pathlib import Path
 
@@ -62,6 +63,9 @@ def lib() -> ctypes.CDLL:
         _lib.mh_grad_sumsq_partial.argtypes = [vp, cl, vp, vp, vp]
         _lib.mh_grad_guard_finish.argtypes = [vp, vp, cl, cf, cf, ci, cf, cf, cf, vp, vp, vp]
         _lib.mh_grad_sumsq_partial.restype = _lib.mh_grad_guard_finish.restype = ci
+        _lib.mh_adamw_groups.argtypes = [vp] * 8 + [cl, cf, cf, cf, cf, ci, cf, vp]     # parameter groups (include/maestro_hip_optim.h)
+        _lib.mh_adamw_groups_dev.argtypes = [vp] * 8 + [cl, cf, cf, cf, vp, vp]
+        _lib.mh_adamw_groups.restype = _lib.mh_adamw_groups_dev.restype = ci
     return _lib
 
 
@@ -1120,6 +1124,90 @@ def adamw_bias_corrections(b1: float, b2: float, step: int) -> tuple[float, floa
 def adamw_dev(p, g, m, v, p_bf16, n, b1, b2, eps, wd, hyper):
     """AdamW with {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale, active} read from the device tensor ``hyper`` (graph-capturable)."""
     _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_dev", p, g, m, v, p_bf16, _L(n), _F(b1), _F(b2), _F(eps), _F(wd), hyper)
+
+
+# ---- AdamW parameter groups (include/maestro_hip_optim.h)
+GROUP_BLOCK, GROUP_TABLE = 64, 256      # MH_ADAMW_GROUP_BLOCK, MH_ADAMW_GROUP_TABLE
+
+
+def _check_groups(what, group_of, lr_scale, wd, n):
+    """The sizes the kernel relies on: one map byte per 64-element block of ``[0, n)`` and two tables of 256 floats."""
+    if group_of.dtype != torch.uint8 or not group_of.is_contiguous() or group_of.numel() < -(-int(n) // GROUP_BLOCK):
+        raise HipExtensionError(f"{what}: the group map must be a dense uint8 tensor of at least ceil(n / {GROUP_BLOCK}) = "
+                                f"{-(-int(n) // GROUP_BLOCK)} bytes")
+    for name, t in (("lr_scale", lr_scale), ("wd", wd)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != GROUP_TABLE:
+            raise HipExtensionError(f"{what}: {name} must be a dense f32 table of exactly {GROUP_TABLE} entries")
+
+
+def adamw_groups(p, g, m, v, p_bf16, group_of, lr_scale, wd, n, lr, b1, b2, eps, step, grad_scale=1.0):
+    """``adamw`` with per-group hyper-parameters: element ``i`` is updated with ``lr * lr_scale[group_of[i // 64]]`` (one fp32
+    product) and ``wd[group_of[i // 64]]``; ``group_of`` uint8 (``p`` starts on a 64-element block of the layout the map was
+    built for), ``lr_scale`` / ``wd`` f32 tables of 256 entries (``ParamGroups`` owns all three)."""
+    _check_groups("adamw_groups", group_of, lr_scale, wd, n)
+    _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_groups", p, g, m, v, p_bf16, group_of, lr_scale, wd, _L(n), _F(lr),
+              _F(b1), _F(b2), _F(eps), _I(step), _F(grad_scale))
+
+
+def adamw_groups_dev(p, g, m, v, p_bf16, group_of, lr_scale, wd, n, b1, b2, eps, hyper):
+    """``adamw_groups`` with {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale, active} read from the device tensor ``hyper``."""
+    _check_groups("adamw_groups_dev", group_of, lr_scale, wd, n)
+    _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_groups_dev", p, g, m, v, p_bf16, group_of, lr_scale, wd, _L(n),
+              _F(b1), _F(b2), _F(eps), hyper)
+
+
+class ParamGroups:
+    """Per-group ``(lr_scale, wd)`` over a flat parameter layout, in the form ``adamw_groups`` reads: a uint8 map with one byte per
+    64-element block and two f32 tables of 256 entries (unused entries ``lr_scale = 0``, ``wd = 0``: a stray map byte would freeze
+    its block, not move it).  ``spans``: ``(lo, hi, lr_scale, wd)`` in any order; every boundary a multiple of 64, together they
+    tile ``[0, total)`` without gap or overlap.  Spans whose ``(lr_scale, wd)`` agree AS fp32 share one group id (ids in order of
+    first appearance from the front of the layout); at most 256 distinct pairs.  ``ValueError`` otherwise.  ``pairs[g]``: the
+    fp32 ``(lr_scale, wd)`` of group ``g`` as Python floats; ``spans``: the sorted ``(lo, hi, group id)``."""
+
+    def __init__(self, spans, device) -> None:
+        import numpy as np
+        spans = sorted((int(lo), int(hi), float(np.float32(s)), float(np.float32(w))) for lo, hi, s, w in spans)
+        if not spans:
+            raise ValueError("ParamGroups: no spans")
+        ids, out, end = {}, [], 0
+        for lo, hi, s, w in spans:
+            if lo % GROUP_BLOCK or hi % GROUP_BLOCK:
+                raise ValueError(f"ParamGroups: span [{lo}, {hi}) is not aligned to {GROUP_BLOCK} elements")
+            if hi <= lo:
+                raise ValueError(f"ParamGroups: span [{lo}, {hi}) is empty")
+            if lo > end:
+                raise ValueError(f"ParamGroups: gap [{end}, {lo}) -- the spans must tile the layout from 0")
+            if lo < end:
+                raise ValueError(f"ParamGroups: overlap -- span [{lo}, {hi}) starts before {end}")
+            if not (math.isfinite(s) and math.isfinite(w)):
+                raise ValueError(f"ParamGroups: span [{lo}, {hi}) has a non-finite lr_scale / wd")
+            gid = ids.setdefault((s, w), len(ids))
+            out.append((lo, hi, gid))
+            end = hi
+        if len(ids) > GROUP_TABLE:
+            raise ValueError(f"ParamGroups: {len(ids)} distinct (lr_scale, wd) pairs, at most {GROUP_TABLE} fit the tables")
+        self.total, self.spans, self.pairs = end, out, list(ids)
+        group_of = np.zeros(end // GROUP_BLOCK, dtype=np.uint8)
+        for lo, hi, gid in out:
+            group_of[lo // GROUP_BLOCK: hi // GROUP_BLOCK] = gid
+        table = np.zeros((2, GROUP_TABLE), dtype=np.float32)
+        table[:, : len(ids)] = np.array(self.pairs, dtype=np.float32).T
+        self.group_of = torch.from_numpy(group_of).to(device)
+        self.lr_scale, self.wd = torch.from_numpy(table[0].copy()).to(device), torch.from_numpy(table[1].copy()).to(device)
+
+    def map_at(self, a: int) -> torch.Tensor:
+        """The map for a slice of the layout that starts at element ``a`` (a multiple of 64, ``0 <= a < total``)."""
+        a = int(a)
+        if a % GROUP_BLOCK or not 0 <= a < self.total:
+            raise ValueError(f"ParamGroups.map_at: offset {a} must be a multiple of {GROUP_BLOCK} inside [0, {self.total})")
+        return self.group_of[a // GROUP_BLOCK:]
+
+    def of(self, i: int) -> tuple[float, float]:
+        """``(lr_scale, wd)`` of element ``i`` (host lookup, for tests and tools)."""
+        for lo, hi, gid in self.spans:
+            if lo <= i < hi:
+                return self.pairs[gid]
+        raise IndexError(i)
 
 
 # ------------------------------------------------------------------------------------------------ kernel timing

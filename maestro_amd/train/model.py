@@ -302,14 +302,50 @@ class SSLModule(_Base):
         params = [p for n, p in self.named_parameters() if n != "_anchor"]
         # a torch.optim.AdamW (state-dict compatible with the reference's) whose step is one fused launch over the engine's
         # flat buffer once an engine owns the parameters (maestro_amd/train/optim.py:EngineAdamW)
-        from maestro_amd.train.optim import EngineAdamW
+        from maestro_amd.train.optim import EngineAdamW, resolve_lw_decay
+        max_lr = lr
+        lw_decay = getattr(tr, "lw_decay", None)
+        if lw_decay is not None and tr.ssl_phase == "finetune":
+            # layer-wise lr decay (maestro/train/baseline.py:110-131): named groups by the layer rule, one max_lr per group
+            params = self.layerwise_param_groups(lr, resolve_lw_decay(lw_decay))
+            max_lr = [g["lr"] for g in params]
         optimizer = EngineAdamW(params, lambda: getattr(self.model, "_engine", None) or getattr(self.model, "_sup_engine", None),
                                 lr=lr, weight_decay=tr.wd, betas=(tr.b1, tr.b2))
         scheduler = torch.optim.lr_scheduler.OneCycleLR(
-            optimizer, max_lr=lr, total_steps=tr.estimated_stepping_batches, pct_start=0.2, cycle_momentum=False,
+            optimizer, max_lr=max_lr, total_steps=tr.estimated_stepping_batches, pct_start=0.2, cycle_momentum=False,
             div_factor=1000, final_div_factor=tr.final_factor / 1000.0)
         return {"optimizer": optimizer,
                 "lr_scheduler": {"scheduler": scheduler, "interval": "step", "name": f"{tr.ssl_phase}_AdamW_lr"}}
+
+    def layerwise_param_groups(self, lr: float, lw_decay: float) -> list[dict]:
+        """``[{"params", "lr", "name"}]`` for finetuning with layer-wise lr decay: the encoder side of ``self.model`` grouped and
+        scaled by ``optim.layer_group_name`` / ``optim.layer_scale`` (patch embeds ``lr * r^(D + 1)``, encoder block ``i``
+        ``lr * r^(D - i)``, stack norms with the block that consumes them), then ``"other"`` (what finetuning leaves without a
+        gradient: decoder side, mask tokens, the EMA copy) and, LAST, ``"heads"``, both at ``lr`` -- the last group's rate is the
+        scalar ``EngineAdamW`` hands to the fused launch."""
+        from maestro_amd.train.optim import layer_group_name, layer_scale
+        m = self.model
+        groups, other, heads = {}, [], []
+        for n, p in self.named_parameters():
+            if n == "_anchor":
+                continue
+            part = n.split(".", 1)
+            inner = part[1] if part[0] == "model" and len(part) > 1 else ""
+            if inner.startswith("heads."):
+                heads.append(p)
+            elif inner.startswith(("patch_embed.", "encoder.", "encoder_inter.")):
+                name = layer_group_name(inner)
+                g = groups.setdefault(name, {"params": [], "lr": lr * layer_scale(inner, m.depth, m.inter_depth or 0, lw_decay),
+                                             "name": name})
+                g["params"].append(p)
+            else:
+                other.append(p)
+        out = list(groups.values())
+        if other:
+            out.append({"params": other, "lr": lr, "name": "other"})
+        if heads:
+            out.append({"params": heads, "lr": lr, "name": "heads"})
+        return out
 
     def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
         """Lightning's hook behind ``Trainer(gradient_clip_val=...)``.  The "norm" algorithm (Lightning's default), when an engine

@@ -72,19 +72,126 @@ def refuse_guard_conflicts(guarded: bool, overlap_optimizer: bool = False, dtype
                          "its chunks of the reduced gradient there")
 
 
+def resolve_lw_decay(lw_decay: float | None = None) -> float | None:
+    """The layer-wise learning-rate decay of the finetune loop: an explicit value wins; None reads ``MAESTRO_LW_DECAY`` (unset or
+    empty = off).  A float in ``(0, 1]`` is accepted, anything else is a ``ValueError``."""
+    import os
+    if lw_decay is None:
+        text = os.environ.get("MAESTRO_LW_DECAY", "").strip()
+        if not text:
+            return None
+        try:
+            lw_decay = float(text)
+        except ValueError:
+            raise ValueError(f"MAESTRO_LW_DECAY={text!r}: lw_decay must be a number in (0, 1]") from None
+    if isinstance(lw_decay, bool) or not isinstance(lw_decay, (int, float)) or not 0.0 < float(lw_decay) <= 1.0:
+        raise ValueError(f"lw_decay={lw_decay!r}: expected a number in (0, 1] (None = off)")
+    return float(lw_decay)
+
+
+def refuse_group_conflicts(grouped: bool, dtype: str | None = None, sharded: bool = False, phase: str | None = None,
+                           lw_decay: float | None = None) -> None:
+    """What AdamW parameter groups (``lw_decay`` / ``no_decay_1d``) exclude, as ``ValueError``s raised before anything is
+    launched."""
+    if phase == "probe" and lw_decay is not None:
+        raise ValueError("lw_decay is a finetune option: in phase='probe' only the heads train (all at the base rate), and the "
+                         "reference's trainer gives probe no lw_decay")
+    if not grouped:
+        return
+    if dtype == "fp8":
+        raise ValueError("AdamW parameter groups (lw_decay / no_decay_1d) are not available with dtype='fp8': mh_adamw_fp8 has no "
+                         "grouped form")
+    if sharded:
+        raise ValueError("AdamW parameter groups (lw_decay / no_decay_1d) exclude step_sharded (exchange_mode='rs_ag'): the chunks "
+                         "of a bucket are not 64-element aligned by construction")
+
+
+def layer_scale(name: str, depth: int, inter_depth: int, lw_decay: float | None) -> float:
+    """The learning-rate scale of the supervised engine's parameter ``name`` under layer-wise decay ``r = lw_decay`` -- the
+    baselines' rule (``maestro/baselines/dinov2.py:312-373``: patch_embed ``r^(depth + 1)``, block ``i`` ``r^(depth - i)``, heads
+    and the last LayerNorm 1) restated for this model, whose encoder is ``d = depth - inter_depth`` blocks per modality / group
+    followed by ``inter_depth`` joint blocks (``D = depth`` in total):
+
+        patch_embed.*                    r^(D + 1)
+        encoder.<name>.layers.<i>.*      r^(D - i)
+        encoder_inter.layers.<j>.*       r^(D - (d + j))
+        encoder.<name>.norm.*            r^(D - d)     the scale of the block that consumes it (1 without joint blocks)
+        encoder_inter.norm.*             1
+        heads.*                          1
+
+    Python floats; None = no decay (1 everywhere).  A name outside this list is a ``ValueError``."""
+    if lw_decay is None:
+        return 1.0
+    r, D, d = float(lw_decay), int(depth), int(depth) - int(inter_depth)  # noqa: N806
+    part = name.split(".")
+    if part[0] == "heads":
+        return 1.0
+    if part[0] == "patch_embed":
+        return r ** (D + 1)
+    if part[0] == "encoder" and len(part) > 3 and part[2] == "layers":
+        return r ** (D - int(part[3]))
+    if part[0] == "encoder" and len(part) > 2 and part[2] == "norm":
+        return r ** (D - d)
+    if part[0] == "encoder_inter" and len(part) > 2 and part[1] == "layers":
+        return r ** (D - (d + int(part[2])))
+    if part[0] == "encoder_inter" and part[1] == "norm":
+        return 1.0
+    raise ValueError(f"layer_scale: {name!r} is no parameter of the probe / finetune model")
+
+
+def layer_group_name(name: str) -> str:
+    """The parameter group ``name`` belongs to on the ``torch.optim`` surface: one per patch embed, encoder block, stack norm, and
+    one for all heads (the baselines' ``patch_embed.<mod>`` / ``encoder.<mod>.<i>`` / ``heads``)."""
+    part = name.split(".")
+    if part[0] == "heads":
+        return "heads"
+    if part[0] == "patch_embed":
+        return ".".join(part[:2])
+    if part[0] == "encoder":
+        return f"encoder.{part[1]}.{part[3]}" if part[2] == "layers" else f"encoder.{part[1]}.norm"
+    if part[0] == "encoder_inter":
+        return f"encoder_inter.{part[2]}" if part[1] == "layers" else "encoder_inter.norm"
+    raise ValueError(f"layer_group_name: {name!r} is no parameter of the probe / finetune model")
+
+
+def layer_groups(engine, lw_decay: float | None, weight_decay: float, no_decay_1d: bool = False):
+    """``hip.ParamGroups`` over the engine's flat layout by the layer rule (:func:`layer_scale`), from ``engine.store``'s names and
+    offsets: one span per parameter (its 64-element padding included), scale from its name, weight decay ``weight_decay`` -- or 0
+    for every parameter with ``ndim <= 1`` (biases, LayerNorm / GroupNorm gains, 1-d head parameters) when ``no_decay_1d``.
+    ``lw_decay=None`` with ``no_decay_1d=False`` returns None: no groups, the ungrouped launches."""
+    if lw_decay is None and not no_decay_1d:
+        return None
+    st, model = engine.store, engine.model
+    offs = [st.offset[id(p)] for p in st.params] + [st.total]
+    spans = []
+    for k, (name, p) in enumerate(zip(st.names, st.params)):
+        wd = 0.0 if (no_decay_1d and p.ndim <= 1) else float(weight_decay)
+        spans.append((offs[k], offs[k + 1], layer_scale(name, model.depth, model.inter_depth or 0, lw_decay), wd))
+    return hip.ParamGroups(spans, st.flat.device)
+
+
 class FusedAdamW:
     """One ``mh_adamw`` launch over all trainable parameters; also refreshes the bf16 weight shadows.
 
     ``guard`` (a ``hip.GradGuard`` over the trainable span, attribute or ``step`` argument; default None = exactly the launches
     above): the step becomes norm + finish + ONE ``mh_adamw_dev`` that reads its scalars -- clipping coefficient folded into the
     gradient scale, ``active`` = 0 on a skipped step -- from the guard; Adam's step count then lives in the guard's device
-    state (``t`` property, ``state_dict``)."""
+    state (``t`` property, ``state_dict``).
 
-    def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.01) -> None:
+    ``groups`` (a ``hip.ParamGroups`` over the store's whole flat layout, e.g. :func:`layer_groups`; default None = exactly the
+    launches above): every launch becomes its grouped form -- ``mh_adamw_groups`` on the slices where ``mh_adamw`` ran,
+    ``mh_adamw_groups_dev`` under a guard -- with the map offset to the slice; ``lr`` is then the BASE rate and ``weight_decay`` is
+    not read (each group carries its own).  Excludes an fp8 plan and ``step_sharded`` (``refuse_group_conflicts``).  The
+    ``state_dict`` layout is the ungrouped one."""
+
+    def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.01, groups=None) -> None:
         import torch
 
         self.engine, self.lr, self.betas, self.eps, self.wd = engine, lr, betas, eps, weight_decay
         st = engine.store
+        if groups is not None and groups.total != st.total:
+            raise ValueError(f"FusedAdamW: parameter groups over {groups.total} elements, flat layout of {st.total}")
+        self.groups = groups
         # the engine's trainable slice of the flat buffer (probe phase: the heads only -- frozen parameters must not even
         # see weight decay, as torch.optim.AdamW skips parameters without a gradient)
         self.lo, self.hi = getattr(engine, "trainable_span", (0, st.total))
@@ -104,8 +211,13 @@ class FusedAdamW:
         if between is not None:
             between()
         guard.launch(st.grad[lo:hi], lr, self.betas[0], self.betas[1], grad_scale)
-        hip.adamw_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], hi - lo, self.betas[0], self.betas[1],
-                      self.eps, self.wd, guard.hyper)
+        gr = self.groups
+        if gr is not None:
+            hip.adamw_groups_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], gr.map_at(lo), gr.lr_scale, gr.wd,
+                                 hi - lo, self.betas[0], self.betas[1], self.eps, guard.hyper)
+        else:
+            hip.adamw_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], hi - lo, self.betas[0], self.betas[1],
+                          self.eps, self.wd, guard.hyper)
         st.mark_synced()
         self.engine._pack_conv_weights()
 
@@ -120,6 +232,8 @@ class FusedAdamW:
         packed weights that are rebuilt afterwards are rebuilt from unchanged masters.  ``ValueError`` with an fp8 plan."""
         import os
         import torch
+        gr = self.groups
+        refuse_group_conflicts(gr is not None, dtype="fp8" if getattr(self.engine, "fp8", None) is not None else None)
         roctx = os.environ.get("MAESTRO_ROCTX", "0") == "1"
         if roctx:
             torch.cuda.nvtx.range_push("maestro:adamw")
@@ -144,6 +258,9 @@ class FusedAdamW:
                 hip.adamw_fp8(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b],
                               plan.w8_flat[a:b], plan.slot_map[a // 64:], plan.wsc.scale, plan.wsc.amax, b - a, lr, self.betas[0],
                               self.betas[1], self.eps, self.wd, self.t, grad_scale)
+            elif b > a and gr is not None:
+                hip.adamw_groups(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], gr.map_at(a),
+                                 gr.lr_scale, gr.wd, b - a, lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale)
             elif b > a:
                 fused8 = False
                 hip.adamw(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], b - a, lr,
@@ -163,6 +280,7 @@ class FusedAdamW:
         The moments of a chunk live on its owner only (``gather_state`` assembles them for a checkpoint).  Parameters after the
         step are bit-identical on every rank, and equal to the all-reduce plan's up to the summation order inside the collective."""
         st = self.engine.store
+        refuse_group_conflicts(self.groups is not None, sharded=True)
         if getattr(self.engine, "fp8", None) is not None:
             raise hip.HipExtensionError("FusedAdamW.step_sharded: not available with dtype='fp8' (the e4m3 shadows of chunks owned "
                                         "by other ranks would need their scales: use the all-reduce plan)")
@@ -252,11 +370,17 @@ class EngineAdamW(torch.optim.AdamW):
 
     ``engine_of()`` returns the engine that owns the parameters right now (or None before the first ``training_step``).  The
     fused launch is used when the optimizer has ONE parameter group (the reference's case) with plain AdamW options and covers
-    every parameter of the engine's trainable span; otherwise ``torch.optim.AdamW.step`` runs unchanged."""
+    every parameter of the engine's trainable span; otherwise ``torch.optim.AdamW.step`` runs unchanged.
+
+    SEVERAL groups (layer-wise lr decay, ``maestro/train/baseline.py:110-131``; no weight decay on 1-d parameters) stay fused as
+    one ``mh_adamw_groups`` launch when they agree in betas, eps and flags and every parameter of the span is in one of them: the
+    last group's lr is the kernel's scalar, every group's ``lr / lr_last`` and ``weight_decay`` go into a ``hip.ParamGroups``
+    when the engine is bound (``_groups_expressible`` re-checks the ratios every step; when they no longer hold torch's step
+    runs, as for anything not eligible)."""
 
     def __init__(self, params, engine_of, **kw) -> None:
         super().__init__(params, **kw)
-        self._engine_of, self._bound, self._fused = engine_of, None, None
+        self._engine_of, self._bound, self._fused, self._scales = engine_of, None, None, None
 
     def load_state_dict(self, state_dict) -> None:
         super().load_state_dict(state_dict)
@@ -273,32 +397,66 @@ class EngineAdamW(torch.optim.AdamW):
         return sd
 
     def _eligible(self, eng) -> bool:
-        if eng is None or len(self.param_groups) != 1:
+        groups = self.param_groups
+        if eng is None:
             return False
-        g = self.param_groups[0]
-        if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or isinstance(g["lr"], torch.Tensor):
+        for g in groups:
+            if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or isinstance(g["lr"], torch.Tensor):
+                return False
+        if len(groups) > 1 and not self._groups_expressible(eng):
             return False
-        mine = {id(p) for p in g["params"]}
+        mine = {id(p) for g in groups for p in g["params"]}
         st = eng.store
         lo, hi = getattr(eng, "trainable_span", (0, st.total))
         span = [p for p in st.params if lo <= st.offset[id(p)] < hi]
         if not all(id(p) in mine for p in span) or getattr(st, "fresh", True):
             return False
-        # ... and the reverse: a parameter of the group OUTSIDE the span that carries a gradient (stale from an earlier phase with
+        # ... and the reverse: a parameter of a group OUTSIDE the span that carries a gradient (stale from an earlier phase with
         # set_to_none=False, or a module parameter the engine does not own) would be updated and decayed by torch.optim.AdamW.step
         # but not by the fused launch -- behaviour must not depend on the path taken, so torch's step runs in that case
         inside = {id(p) for p in span}
-        if any(p.grad is not None for p in g["params"] if id(p) not in inside):
+        if any(p.grad is not None for g in groups for p in g["params"] if id(p) not in inside):
             return False
         # every gradient of the span must BE the flat buffer's slice (the autograd bridge attaches them)
         return all(p.grad is not None and p.grad.data_ptr() == st.g(p).data_ptr() for p in span)
 
+    def _groups_expressible(self, eng) -> bool:
+        """Several groups as ONE base rate and constant per-group scales: they agree in betas and eps, the LAST group's lr is the
+        scalar handed to the kernel, and every other group's lr is that scalar times the scale captured when the groups were
+        bound -- re-checked here on every step, a few dozen floats on the host (``1e-6`` relative: the ratio is exact in real
+        arithmetic, a scheduler that scales every ``max_lr`` by one factor keeps it up to float roundoff)."""
+        groups = self.param_groups
+        last = groups[-1]
+        if any(g["betas"] != last["betas"] or g["eps"] != last["eps"] for g in groups):
+            return False
+        lr_last = float(last["lr"])
+        if not (math.isfinite(lr_last) and lr_last > 0.0) or getattr(eng, "fp8", None) is not None:
+            return False
+        if len({(float(g["lr"]), float(g["weight_decay"])) for g in groups}) > hip.GROUP_TABLE:
+            return False
+        if self._bound is eng and self._scales is not None:
+            if len(self._scales) != len(groups):
+                return False
+            for g, (scale, wd) in zip(groups, self._scales):
+                if abs(float(g["lr"]) - lr_last * scale) > 1e-6 * lr_last or float(g["weight_decay"]) != wd:
+                    return False
+        return True
+
     def _bind(self, eng) -> None:
         """Moments into the engine's layout (adopting whatever per-parameter state exists: a loaded checkpoint, steps done by
         torch's implementation, a previous engine of another batch size) and ``state[p]`` re-pointed at views of them."""
-        g = self.param_groups[0]
-        fused = FusedAdamW(eng, g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"])
-        st, lo, hi = eng.store, fused.lo, fused.hi
+        g = self.param_groups[-1]
+        st = eng.store
+        groups, self._scales = None, None
+        if len(self.param_groups) > 1:      # scale_g = lr_g / lr_last, captured once; parameters of no group are never touched
+            lr_last = float(g["lr"])
+            self._scales = [(float(q["lr"]) / lr_last, float(q["weight_decay"])) for q in self.param_groups]
+            pair = {id(p): self._scales[k] for k, q in enumerate(self.param_groups) for p in q["params"]}
+            offs = [st.offset[id(p)] for p in st.params] + [st.total]
+            groups = hip.ParamGroups([(offs[k], offs[k + 1], *pair.get(id(p), (0.0, 0.0))) for k, p in enumerate(st.params)],
+                                     st.flat.device)
+        fused = FusedAdamW(eng, g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], groups=groups)
+        lo, hi = fused.lo, fused.hi
         t = 0
         with torch.no_grad():
             for p in st.params:
@@ -336,7 +494,7 @@ class EngineAdamW(torch.optim.AdamW):
             return loss
         if self._bound is not eng:
             self._bind(eng)
-        g, f = self.param_groups[0], self._fused
+        g, f = self.param_groups[-1], self._fused      # (with several groups: the base rate; f.wd is not read then)
         f.betas, f.eps, f.wd = g["betas"], g["eps"], g["weight_decay"]
         f.step(lr=float(g["lr"]))
         self._step.fill_(float(f.t))

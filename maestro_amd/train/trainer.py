@@ -12,7 +12,8 @@ import torch
 
 from maestro_amd.engine import training_warm_passes
 from maestro_amd.train.ddp import GradSync, broadcast_parameters
-from maestro_amd.train.optim import FusedAdamW, OneCycle, refuse_guard_conflicts, resolve_grad_guard, scaled_lr
+from maestro_amd.train.optim import (FusedAdamW, OneCycle, layer_groups, refuse_group_conflicts, refuse_guard_conflicts,
+                                     resolve_grad_guard, resolve_lw_decay, scaled_lr)
 
 
 def synthetic_batch(dataset, B: int, device, seed: int = 0) -> dict:  # noqa: N803
@@ -252,20 +253,32 @@ class SupervisedLoop(_GuardSurface):
     """Probe / finetune counterpart of :class:`PretrainLoop` (reference ``base.py:185-224`` around the optimizer step):
     engine forward (+ ``loss_pred``) -> backward (probe: heads only) -> all-reduce -> fused AdamW on the trainable slice.
     ``max_grad_norm`` / ``skip_nonfinite``: the gradient guard of :class:`PretrainLoop`, over the trainable span (probe: the heads
-    only -- what lies below the span is neither normed nor looked at)."""
+    only -- what lies below the span is neither normed nor looked at).
+
+    ``lw_decay`` (finetune only; None reads ``MAESTRO_LW_DECAY``, unset or empty = off; a float in ``(0, 1]``): the reference's
+    layer-wise learning-rate decay (``OptFinetuneConfig.lw_decay``, ``maestro/train/baseline.py:110-131``) by the layer rule of
+    ``optim.layer_scale`` -- patch embeds at ``r^(D + 1)``, encoder block ``i`` at ``r^(D - i)``, heads at the base rate.
+    ``no_decay_1d``: weight decay 0 on every parameter with ``ndim <= 1``.  Either makes every AdamW launch its grouped form
+    (``optim.layer_groups``, ``mh_adamw_groups``); with neither the loop issues exactly the ungrouped launches.  The schedule
+    stays the ONE scalar ``OneCycle``: ``OneCycleLR`` is linear in ``max_lr`` -- its initial and final rates are ``max_lr``
+    divided by constants, and the cosine interpolates between them -- so ``sched.lr(t) * scale_g`` IS the reference's
+    per-group ``OneCycleLR(max_lr=[lr * scale_g ...])`` at every step.  ``phase="probe"`` with a decay is a ``ValueError``."""
 
     def __init__(self, model, batch_size: int, device, phase: str = "finetune", base_lr: float = 3e-5, betas=(0.9, 0.99),
                  weight_decay: float = 0.01, total_steps: int = 1000, world_size: int = 1, final_factor: float = 1e7,
                  bucket_mb: int = 64, exchange: bool | None = None, bucket_dtype=None, max_grad_norm: float | None = None,
-                 skip_nonfinite: bool | None = None) -> None:
+                 skip_nonfinite: bool | None = None, lw_decay: float | None = None, no_decay_1d: bool = False) -> None:
         max_norm, skip = resolve_grad_guard(max_grad_norm, skip_nonfinite)      # (refused before anything is built)
+        lw_decay = resolve_lw_decay(lw_decay)
+        refuse_group_conflicts(lw_decay is not None or no_decay_1d, phase=phase, lw_decay=lw_decay)
         self.engine = model.sup_engine(batch_size, device, phase)
         self.engine.warm_passes = training_warm_passes()
         broadcast_parameters(self.engine)
         lr = scaled_lr(base_lr, batch_size, 1, 1, world_size)
         self.sched = OneCycle(lr, max(total_steps, 2), pct_start=0.2, div_factor=1000.0,
                               final_div_factor=final_factor / 1000.0)
-        self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay)
+        self.groups = layer_groups(self.engine, lw_decay, weight_decay, no_decay_1d)      # None: no groups, the ungrouped launches
+        self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay, groups=self.groups)
         self.guard = _make_guard(self.opt, device, max_norm, skip) if (max_norm is not None or skip) else None
         lo, hi = self.engine.trainable_span
         st = self.engine.store
