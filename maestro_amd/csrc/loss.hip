@@ -1,6 +1,9 @@
 // Masked reconstruction loss at patch layout + its gradient, bias-gradient column sums, casts, fused AdamW.
 #include "gemm_common.hpp"
+#include "philox.hpp"
 #include "../../include/maestro_hip_optim.h"
+#include "../../include/maestro_hip_moments.h"
+#include <type_traits>
 
 namespace {
 
@@ -184,12 +187,33 @@ __global__ __launch_bounds__(256) void unpack_rows_add_kernel(const float* __res
 // records this step's (delayed scaling: a weight moves by one learning-rate step at a time).
 struct Fp8Shadow { uint8_t* p8; const short* slot_map; const float* scale; float* amax; };
 
+// bf16 moments (include/maestro_hip_moments.h): what the stochastic rounding of a launch draws from.  One Philox call per lane
+// (= per quad) gives the eight 16-bit words of its four m and four v elements.  The ten rounds are twenty 32 x 32 -> 64-bit
+// multiplies (v_mad_u64_u32) and some 60 xor / add per wave beside 5.6 KB of HBM traffic per wave (22 bytes x 256 elements): at
+// ~10 B / cycle / CU a CU moves a wave's bytes in ~560 cycles, i.e. each of its four SIMDs has ~2200 cycles per wave it owns, and
+// the rounds issue in under half that -- measured, the kernel runs at mh_adamw's bandwidth (profiles/adamw_moments.md).
+struct MomentSR { uint32_t k0, k1, step; long elem_base; };
+struct NoSR {};
+
+// u = fp32 bits, r < 65536 -> bf16 bits: the magnitude goes up with probability low16(u) / 65536; inf / NaN pass (a NaN stays
+// one), a finite value never becomes inf.  On integers: sr_bf16_reference in maestro_amd/hip.py is the same lines.
+__device__ __forceinline__ uint32_t sr_bf16(float x, uint32_t r) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7f800000u) == 0x7f800000u) return (u >> 16) | (((u & 0x007fffffu) && !(u & 0x007f0000u)) ? 0x40u : 0u);
+    const uint32_t t = u + r;
+    return ((t & 0x7f800000u) == 0x7f800000u ? u : t) >> 16;
+}
+
+// The ONE update of the library, on how the moments are held: MT = float (m / v fp32, SR = NoSR: mh_adamw and its kin) or bf16_t
+// (upcast exactly on load, stored by stochastic rounding, SR = MomentSR); the arithmetic between load and store is the same text.
 // returns the fp8 scale slot of this lane's four elements (-1: none) and their absmax in *amax_out
-__device__ __forceinline__ int adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                             float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1, float b2,
+template <typename MT = float, typename SR = NoSR>
+__device__ __forceinline__ int adamw_update(float* __restrict__ p, const float* __restrict__ g, MT* __restrict__ m,
+                                             MT* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1, float b2,
                                              float eps, float wd, float bc1, float bc2_sqrt, float gscale,
                                              Fp8Shadow f8 = Fp8Shadow{nullptr, nullptr, nullptr, nullptr},
-                                             float* amax_out = nullptr) {
+                                             float* amax_out = nullptr, SR sr = SR{}) {
+    constexpr bool BF16M = std::is_same<MT, bf16_t>::value;
     const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return -1;
     // Every stream of this kernel is touched once per step (30 bytes per parameter, 5.3 GB on C3): nontemporal loads AND stores keep
@@ -197,19 +221,45 @@ __device__ __forceinline__ int adamw_update(float* __restrict__ p, const float* 
     // alone gains 1 %, two or four quads per lane nothing (scripts/micro_adamw.hip, profiles/r05_experiments.md).
     const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + i)) * gscale;
     f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + i));
-    f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + i));
-    f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + i));
+    f32x4 mv, vv;
+    if constexpr (BF16M) {
+        const u32x2 m2 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(m + i));
+        const u32x2 v2 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(v + i));
+        mv = (f32x4){__uint_as_float(m2[0] << 16), __uint_as_float(m2[0] & 0xffff0000u),
+                     __uint_as_float(m2[1] << 16), __uint_as_float(m2[1] & 0xffff0000u)};
+        vv = (f32x4){__uint_as_float(v2[0] << 16), __uint_as_float(v2[0] & 0xffff0000u),
+                     __uint_as_float(v2[1] << 16), __uint_as_float(v2[1] & 0xffff0000u)};
+    } else {
+        mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + i));
+        vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + i));
+    }
+    // Every rounding is written out: which products fuse into an fma is the text below, not the optimiser's choice per
+    // instantiation (left to it, the bf16 form packed b2 * v with (1 - b2) * g and ADDED, where the fp32 form fused) -- both forms
+    // give the same p, m and v bits from the same operands.  The fused places are the ones mh_adamw has always compiled to.
+    {
+#pragma clang fp contract(off)
+        const float decay = __builtin_fmaf(-lr, wd, 1.f), rate = lr / bc1, c1 = 1.f - b1, c2 = 1.f - b2;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        pv[e] *= 1.f - lr * wd;
-        mv[e] = b1 * mv[e] + (1.f - b1) * gv[e];
-        vv[e] = b2 * vv[e] + (1.f - b2) * gv[e] * gv[e];
-        const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-        pv[e] -= (lr / bc1) * (mv[e] / denom);
+        for (int e = 0; e < 4; ++e) {
+            mv[e] = __builtin_fmaf(c1, gv[e], b1 * mv[e]);
+            vv[e] = __builtin_fmaf(c2 * gv[e], gv[e], b2 * vv[e]);
+            const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+            pv[e] = __builtin_fmaf(decay, pv[e], -(rate * (mv[e] / denom)));
+        }
     }
     __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p + i));
-    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m + i));
-    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + i));
+    if constexpr (BF16M) {
+        const u32x4 w = philox4x32_10((uint32_t)((sr.elem_base + i) >> 2), sr.step, 0u, MH_ADAMW_SR_TAG, sr.k0, sr.k1);
+        const u32x2 m2 = {sr_bf16(mv[0], w[0] & 0xffffu) | sr_bf16(mv[1], w[0] >> 16) << 16,
+                          sr_bf16(mv[2], w[1] & 0xffffu) | sr_bf16(mv[3], w[1] >> 16) << 16};
+        const u32x2 v2 = {sr_bf16(vv[0], w[2] & 0xffffu) | sr_bf16(vv[1], w[2] >> 16) << 16,
+                          sr_bf16(vv[2], w[3] & 0xffffu) | sr_bf16(vv[3], w[3] >> 16) << 16};
+        __builtin_nontemporal_store(m2, reinterpret_cast<u32x2*>(m + i));
+        __builtin_nontemporal_store(v2, reinterpret_cast<u32x2*>(v + i));
+    } else {
+        __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m + i));
+        __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + i));
+    }
     if (pb) {
         u32x2 pk = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3])};
         __builtin_nontemporal_store(pk, reinterpret_cast<u32x2*>(pb + i));
@@ -277,16 +327,18 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, c
 // workgroup beside 30 bytes per parameter of nontemporal traffic: PLAIN loads, which the vector L1 serves (nontemporal loads
 // bypass it), while the streams above leave no line behind that could displace them.  lr_g is one explicitly rounded product:
 // what follows in adamw_update sees the float mh_adamw would have been handed for this group.
-__device__ __forceinline__ void adamw_group_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, bf16_t* __restrict__ pb,
+template <typename MT = float, typename SR = NoSR>
+__device__ __forceinline__ void adamw_group_update(float* __restrict__ p, const float* __restrict__ g, MT* __restrict__ m,
+                                                   MT* __restrict__ v, bf16_t* __restrict__ pb,
                                                    const uint8_t* __restrict__ group_of, const float* __restrict__ lr_scale,
                                                    const float* __restrict__ wd, long n, float lr, float b1, float b2, float eps,
-                                                   float bc1, float bc2_sqrt, float gscale) {
+                                                   float bc1, float bc2_sqrt, float gscale, SR sr = SR{}) {
     const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;                      // before the map is read: its last byte is the one of element n - 1
     const unsigned grp = group_of[i >> 6];
     const float lr_g = __fmul_rn(lr, lr_scale[grp]);
-    adamw_update(p, g, m, v, pb, n, lr_g, b1, b2, eps, wd[grp], bc1, bc2_sqrt, gscale);
+    adamw_update(p, g, m, v, pb, n, lr_g, b1, b2, eps, wd[grp], bc1, bc2_sqrt, gscale, Fp8Shadow{nullptr, nullptr, nullptr, nullptr},
+                 nullptr, sr);
 }
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, bf16_t* __restrict__ pb,
@@ -303,6 +355,44 @@ __global__ __launch_bounds__(256) void adamw_groups_dev_kernel(float* __restrict
                                                                const float* __restrict__ hyper) {
     if (hyper[4] == 0.f) return;
     adamw_group_update(p, g, m, v, pb, group_of, lr_scale, wd, n, hyper[0], b1, b2, eps, hyper[1], hyper[2], hyper[3]);
+}
+
+// bf16 moments (include/maestro_hip_moments.h): the four launches above with m / v as bf16 and the rounding draws' key, step and
+// layout offset.  The device forms take the step from the low 32 bits of *step_dev (the guard's MhGuardState.t).
+__global__ __launch_bounds__(256) void adamw_bf16m_kernel(float* __restrict__ p, const float* __restrict__ g, bf16_t* __restrict__ m,
+                                                          bf16_t* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr,
+                                                          float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                          float gscale, MomentSR sr) {
+    adamw_update(p, g, m, v, pb, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, Fp8Shadow{nullptr, nullptr, nullptr, nullptr}, nullptr, sr);
+}
+__global__ __launch_bounds__(256) void adamw_bf16m_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                              bf16_t* __restrict__ m, bf16_t* __restrict__ v, bf16_t* __restrict__ pb,
+                                                              long n, float b1, float b2, float eps, float wd,
+                                                              const float* __restrict__ hyper, const long long* __restrict__ step_dev,
+                                                              MomentSR sr) {
+    if (hyper[4] == 0.f) return;
+    sr.step = (uint32_t)*step_dev;
+    adamw_update(p, g, m, v, pb, n, hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], hyper[3], Fp8Shadow{nullptr, nullptr, nullptr, nullptr},
+                 nullptr, sr);
+}
+__global__ __launch_bounds__(256) void adamw_groups_bf16m_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                 bf16_t* __restrict__ m, bf16_t* __restrict__ v, bf16_t* __restrict__ pb,
+                                                                 const uint8_t* __restrict__ group_of,
+                                                                 const float* __restrict__ lr_scale, const float* __restrict__ wd,
+                                                                 long n, float lr, float b1, float b2, float eps, float bc1,
+                                                                 float bc2_sqrt, float gscale, MomentSR sr) {
+    adamw_group_update(p, g, m, v, pb, group_of, lr_scale, wd, n, lr, b1, b2, eps, bc1, bc2_sqrt, gscale, sr);
+}
+__global__ __launch_bounds__(256) void adamw_groups_bf16m_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                     bf16_t* __restrict__ m, bf16_t* __restrict__ v,
+                                                                     bf16_t* __restrict__ pb, const uint8_t* __restrict__ group_of,
+                                                                     const float* __restrict__ lr_scale, const float* __restrict__ wd,
+                                                                     long n, float b1, float b2, float eps,
+                                                                     const float* __restrict__ hyper,
+                                                                     const long long* __restrict__ step_dev, MomentSR sr) {
+    if (hyper[4] == 0.f) return;
+    sr.step = (uint32_t)*step_dev;
+    adamw_group_update(p, g, m, v, pb, group_of, lr_scale, wd, n, hyper[0], b1, b2, eps, hyper[1], hyper[2], hyper[3], sr);
 }
 
 // x *= *scale, skipped when the device scalar is exactly 1 (loss.backward() with autograd's default ones gradient): the
@@ -521,6 +611,67 @@ extern "C" int mh_adamw_groups_dev(float* p, const float* g, float* m, float* v,
     MH_CHECK_ARG(adamw_groups_aligned(p, g, m, v, p_bf16), "mh_adamw_groups_dev: p, g, m, v must be 16-byte, p_bf16 8-byte aligned");
     hipLaunchKernelGGL(adamw_groups_dev_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                        (bf16_t*)p_bf16, group_of, lr_scale, wd, n, b1, b2, eps, hyper);
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- bf16 moments (include/maestro_hip_moments.h)
+static bool adamw_bf16m_aligned(const void* p, const void* g, const void* m16, const void* v16, const void* p_bf16) {
+    return (((uintptr_t)p | (uintptr_t)g) % 16) == 0 && (((uintptr_t)m16 | (uintptr_t)v16 | (uintptr_t)p_bf16) % 8) == 0;
+}
+#define MH_ADAMW_BF16M_CHECK(name, block, extra)                                                                                    \
+    MH_CHECK_ARG(p && g && m16 && v16 && (extra) && n > 0 && n % 4 == 0,                                                           \
+                 name ": bad arguments (null pointer, n > 0, n %% 4 == 0, step >= 1)");                                              \
+    MH_CHECK_ARG(elem_base >= 0 && elem_base % block == 0, name ": elem_base %ld must be a non-negative multiple of %d", elem_base, block); \
+    MH_CHECK_ARG(adamw_bf16m_aligned(p, g, m16, v16, p_bf16), name ": p, g must be 16-byte, m16, v16, p_bf16 8-byte aligned")
+static MomentSR moment_sr(uint64_t seed, long long step, long elem_base) {
+    return MomentSR{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (uint32_t)step, elem_base};
+}
+
+extern "C" int mh_adamw_bf16m(float* p, const float* g, void* m16, void* v16, void* p_bf16, long n, long elem_base, uint64_t seed,
+                              float lr, float b1, float b2, float eps, float wd, int step, float grad_scale, void* stream) {
+    MH_ADAMW_BF16M_CHECK("mh_adamw_bf16m", 4, step >= 1);
+    const float bc1 = 1.f - powf(b1, (float)step);
+    const float bc2_sqrt = sqrtf(1.f - powf(b2, (float)step));
+    hipLaunchKernelGGL(adamw_bf16m_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, (bf16_t*)m16,
+                       (bf16_t*)v16, (bf16_t*)p_bf16, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, moment_sr(seed, step, elem_base));
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_adamw_bf16m_dev(float* p, const float* g, void* m16, void* v16, void* p_bf16, long n, long elem_base,
+                                  uint64_t seed, float b1, float b2, float eps, float wd, const float* hyper,
+                                  const long long* step_dev, void* stream) {
+    MH_ADAMW_BF16M_CHECK("mh_adamw_bf16m_dev", 4, hyper && step_dev);
+    hipLaunchKernelGGL(adamw_bf16m_dev_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, (bf16_t*)m16,
+                       (bf16_t*)v16, (bf16_t*)p_bf16, n, b1, b2, eps, wd, hyper, step_dev, moment_sr(seed, 0, elem_base));
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_adamw_groups_bf16m(float* p, const float* g, void* m16, void* v16, void* p_bf16, const unsigned char* group_of,
+                                     const float* lr_scale, const float* wd, long n, long elem_base, uint64_t seed, float lr,
+                                     float b1, float b2, float eps, int step, float grad_scale, void* stream) {
+    MH_ADAMW_BF16M_CHECK("mh_adamw_groups_bf16m", MH_ADAMW_GROUP_BLOCK, step >= 1);
+    MH_CHECK_ARG(group_of && lr_scale && wd, "mh_adamw_groups_bf16m: the group map and both tables are required (null pointer)");
+    const float bc1 = 1.f - powf(b1, (float)step);
+    const float bc2_sqrt = sqrtf(1.f - powf(b2, (float)step));
+    hipLaunchKernelGGL(adamw_groups_bf16m_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, (bf16_t*)m16,
+                       (bf16_t*)v16, (bf16_t*)p_bf16, group_of, lr_scale, wd, n, lr, b1, b2, eps, bc1, bc2_sqrt, grad_scale,
+                       moment_sr(seed, step, elem_base));
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mh_adamw_groups_bf16m_dev(float* p, const float* g, void* m16, void* v16, void* p_bf16,
+                                         const unsigned char* group_of, const float* lr_scale, const float* wd, long n,
+                                         long elem_base, uint64_t seed, float b1, float b2, float eps, const float* hyper,
+                                         const long long* step_dev, void* stream) {
+    MH_ADAMW_BF16M_CHECK("mh_adamw_groups_bf16m_dev", MH_ADAMW_GROUP_BLOCK, hyper && step_dev);
+    MH_CHECK_ARG(group_of && lr_scale && wd, "mh_adamw_groups_bf16m_dev: the group map and both tables are required (null pointer)");
+    hipLaunchKernelGGL(adamw_groups_bf16m_dev_kernel, dim3(ceil_div(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, (bf16_t*)m16,
+                       (bf16_t*)v16, (bf16_t*)p_bf16, group_of, lr_scale, wd, n, b1, b2, eps, hyper, step_dev,
+                       moment_sr(seed, 0, elem_base));
     MH_LAUNCH_CHECK();
     return 0;
 }

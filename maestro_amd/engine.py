@@ -1363,6 +1363,8 @@ class MAEEngine(EngineBase):
     def attach_optimizer(self, opt) -> None:
         if self.deterministic:
             raise ValueError("deterministic=True excludes overlap_optimizer (the update inside the next forward is not covered)")
+        if getattr(opt, "moment_dtype", "fp32") != "fp32":      # the stages below launch mh_adamw_dev on fp32 moments
+            raise ValueError("moment_dtype='bf16' excludes overlap_optimizer: the per-layer deferred stages launch the fp32-moment update")
         self._attach_optimizer(opt)
 
     def _attach_optimizer(self, opt) -> None:

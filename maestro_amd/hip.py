@@ -66,6 +66,13 @@ def lib() -> ctypes.CDLL:
         _lib.mh_adamw_groups.argtypes = [vp] * 8 + [cl, cf, cf, cf, cf, ci, cf, vp]     # parameter groups (include/maestro_hip_optim.h)
         _lib.mh_adamw_groups_dev.argtypes = [vp] * 8 + [cl, cf, cf, cf, vp, vp]
         _lib.mh_adamw_groups.restype = _lib.mh_adamw_groups_dev.restype = ci
+        u64 = ctypes.c_uint64                                               # bf16 moments (include/maestro_hip_moments.h)
+        _lib.mh_adamw_bf16m.argtypes = [vp] * 5 + [cl, cl, u64, cf, cf, cf, cf, cf, ci, cf, vp]
+        _lib.mh_adamw_bf16m_dev.argtypes = [vp] * 5 + [cl, cl, u64, cf, cf, cf, cf, vp, vp, vp]
+        _lib.mh_adamw_groups_bf16m.argtypes = [vp] * 8 + [cl, cl, u64, cf, cf, cf, cf, ci, cf, vp]
+        _lib.mh_adamw_groups_bf16m_dev.argtypes = [vp] * 8 + [cl, cl, u64, cf, cf, cf, vp, vp, vp]
+        _lib.mh_adamw_bf16m.restype = _lib.mh_adamw_bf16m_dev.restype = ci
+        _lib.mh_adamw_groups_bf16m.restype = _lib.mh_adamw_groups_bf16m_dev.restype = ci
     return _lib
 
 
@@ -632,6 +639,7 @@ class GradGuard:
         self.norm = self.state[0:4].view(torch.float32)
         self.coef = self.state[4:8].view(torch.float32)
         self._counters = self.state[16:32].view(torch.int64)      # t, skipped
+        self.t_dev = self._counters[:1]      # Adam's t as a device word: what ``adamw_bf16m_dev`` reads after ``launch``
 
     def launch(self, grad, lr: float, b1: float, b2: float, grad_scale: float = 1.0) -> None:
         if grad.dtype != torch.float32 or grad.numel() != self.n or not grad.is_contiguous():
@@ -1154,6 +1162,100 @@ def adamw_groups_dev(p, g, m, v, p_bf16, group_of, lr_scale, wd, n, b1, b2, eps,
     _check_groups("adamw_groups_dev", group_of, lr_scale, wd, n)
     _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_groups_dev", p, g, m, v, p_bf16, group_of, lr_scale, wd, _L(n),
               _F(b1), _F(b2), _F(eps), hyper)
+
+
+# ---- AdamW with bf16 moments (include/maestro_hip_moments.h)
+ADAMW_SR_TAG = 0x5352424D      # MH_ADAMW_SR_TAG: c3 of every rounding draw
+_U64 = ctypes.c_uint64
+
+
+def _check_moments(what, m16, v16, n):
+    """bf16 moments of at least ``n`` elements: a fp32 buffer handed to these entries would be read as twice as many bf16."""
+    for name, t in (("m16", m16), ("v16", v16)):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() < int(n):
+            raise HipExtensionError(f"{what}: {name} must be a dense bfloat16 tensor of at least n = {int(n)} elements")
+
+
+def adamw_bf16m(p, g, m16, v16, p_bf16, n, elem_base, seed, lr, b1, b2, eps, wd, step, grad_scale=1.0):
+    """``adamw`` with both moments held as bf16: upcast exactly, updated in fp32 (``p`` moves by the unrounded moments), stored by
+    stochastic rounding with the words of ``sr_bf16_reference`` at indices ``elem_base + i`` (``elem_base``: the offset of
+    ``p[0]`` in the flat layout, a multiple of 4).  22 bytes per parameter instead of 30."""
+    _check_moments("adamw_bf16m", m16, v16, n)
+    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_bf16m", p, g, m16, v16, p_bf16, _L(n), _L(elem_base),
+              _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(lr), _F(b1), _F(b2), _F(eps), _F(wd), _I(step), _F(grad_scale))
+
+
+def adamw_bf16m_dev(p, g, m16, v16, p_bf16, n, elem_base, seed, b1, b2, eps, wd, hyper, step_dev):
+    """``adamw_dev`` with bf16 moments; ``step_dev``: a 1-element int64 DEVICE tensor holding Adam's ``t`` (the guard's counter,
+    read by the kernel after ``grad_guard_finish`` wrote it)."""
+    _check_moments("adamw_bf16m_dev", m16, v16, n)
+    if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
+        raise HipExtensionError("adamw_bf16m_dev: step_dev must be an int64 tensor")
+    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_bf16m_dev", p, g, m16, v16, p_bf16, _L(n), _L(elem_base),
+              _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(b1), _F(b2), _F(eps), _F(wd), hyper, step_dev)
+
+
+def adamw_groups_bf16m(p, g, m16, v16, p_bf16, group_of, lr_scale, wd, n, elem_base, seed, lr, b1, b2, eps, step, grad_scale=1.0):
+    """``adamw_groups`` with bf16 moments (``elem_base`` a multiple of 64: the map has one byte per 64 elements)."""
+    _check_groups("adamw_groups_bf16m", group_of, lr_scale, wd, n)
+    _check_moments("adamw_groups_bf16m", m16, v16, n)
+    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_groups_bf16m", p, g, m16, v16, p_bf16, group_of, lr_scale, wd,
+              _L(n), _L(elem_base), _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(lr), _F(b1), _F(b2), _F(eps), _I(step), _F(grad_scale))
+
+
+def adamw_groups_bf16m_dev(p, g, m16, v16, p_bf16, group_of, lr_scale, wd, n, elem_base, seed, b1, b2, eps, hyper, step_dev):
+    """``adamw_groups_dev`` with bf16 moments (``step_dev`` as in ``adamw_bf16m_dev``)."""
+    _check_groups("adamw_groups_bf16m_dev", group_of, lr_scale, wd, n)
+    _check_moments("adamw_groups_bf16m_dev", m16, v16, n)
+    if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
+        raise HipExtensionError("adamw_groups_bf16m_dev: step_dev must be an int64 tensor")
+    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_groups_bf16m_dev", p, g, m16, v16, p_bf16, group_of, lr_scale,
+              wd, _L(n), _L(elem_base), _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(b1), _F(b2), _F(eps), hyper, step_dev)
+
+
+def sr_bf16_words(index, seed, step, which):
+    """The 16-bit random word of the stochastic rounding at flat element ``index`` (array), for moment ``which`` ("m" / "v"):
+    Philox4x32-10, key ``(seed & 0xffffffff, seed >> 32)``, counter ``(index // 4, step, 0, ADAMW_SR_TAG)`` (each the low 32
+    bits); element ``e = index % 4`` takes ``(w[e >> 1] >> 16 * (e & 1)) & 0xffff`` for ``m`` and the same of ``w[2 + (e >> 1)]``
+    for ``v``.  uint32 array."""
+    import numpy as np
+
+    from maestro_amd.layers.utils import philox4x32
+    if which not in ("m", "v"):
+        raise ValueError(f"which={which!r}: expected 'm' or 'v'")
+    index = np.asarray(index).astype(np.uint64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32((index >> np.uint64(2), np.uint64(int(step) & 0xFFFFFFFF), np.uint64(0), np.uint64(ADAMW_SR_TAG)),
+                   (seed & 0xFFFFFFFF, seed >> 32))
+    e = (index & np.uint64(3)).astype(np.intp)
+    word = np.choose((e >> 1) + (2 if which == "v" else 0), w)
+    return (word >> (np.uint32(16) * (e & 1).astype(np.uint32))) & np.uint32(0xFFFF)
+
+
+def sr_bf16_round(bits_f32, r):
+    """The rounding rule alone, on integers: fp32 bit patterns ``bits_f32`` and 16-bit words ``r`` (arrays) -> bf16 bit patterns
+    (uint16).  inf / NaN: the upper half (a NaN whose surviving mantissa bits are zero gets the quiet bit); else ``t = u + r``,
+    and ``t >> 16`` unless ``t`` carried into an all-ones exponent, then ``u >> 16``."""
+    import numpy as np
+    u = np.asarray(bits_f32).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    r = np.asarray(r).astype(np.uint64)
+    if r.size and int(r.max()) > 0xFFFF:
+        raise ValueError("sr_bf16_round: r must be a 16-bit word")
+    exp = np.uint64(0x7F800000)
+    special = (u & exp) == exp
+    nan_lost = special & ((u & np.uint64(0x007FFFFF)) != 0) & ((u & np.uint64(0x007F0000)) == 0)
+    t = u + r
+    keep = (t & exp) == exp
+    out = np.where(special, (u >> np.uint64(16)) | np.where(nan_lost, np.uint64(0x40), np.uint64(0)),
+                   np.where(keep, u, t) >> np.uint64(16))
+    return out.astype(np.uint16)
+
+
+def sr_bf16_reference(bits_f32, index, seed, step, which):
+    """What ``adamw_bf16m`` stores for a new fp32 moment: ``bits_f32`` (uint32 array: the fp32 bit patterns) at flat element
+    indices ``index`` (``elem_base + i``) -> bf16 bit patterns (uint16), the contract of include/maestro_hip_moments.h restated in
+    numpy integers (runs on any machine).  ``which``: "m" or "v"."""
+    return sr_bf16_round(bits_f32, sr_bf16_words(index, seed, step, which))
 
 
 class ParamGroups:

@@ -106,6 +106,30 @@ def refuse_group_conflicts(grouped: bool, dtype: str | None = None, sharded: boo
                          "of a bucket are not 64-element aligned by construction")
 
 
+def resolve_moment_dtype(moment_dtype: str | None = None) -> str:
+    """How the loops' AdamW holds its two moments: an explicit value wins; None reads ``MAESTRO_MOMENT_DTYPE`` (unset, empty or
+    "fp32" = off).  Returns "fp32" or "bf16"; anything else is a ``ValueError``."""
+    import os
+    if moment_dtype is None:
+        moment_dtype = os.environ.get("MAESTRO_MOMENT_DTYPE", "").strip() or "fp32"
+    if moment_dtype not in ("fp32", "bf16"):
+        raise ValueError(f"moment_dtype={moment_dtype!r}: expected 'fp32' or 'bf16'")
+    return moment_dtype
+
+
+def refuse_moment_conflicts(bf16_moments: bool, overlap_optimizer: bool = False, dtype: str | None = None,
+                            exchange_mode: str = "all_reduce") -> None:
+    """What bf16 moments (``moment_dtype="bf16"``) exclude, as ``ValueError``s raised before anything is built."""
+    if not bf16_moments:
+        return
+    if dtype == "fp8":
+        raise ValueError("moment_dtype='bf16' is not available with dtype='fp8': mh_adamw_fp8 has no bf16-moment form")
+    if exchange_mode == "rs_ag":
+        raise ValueError("moment_dtype='bf16' excludes exchange_mode='rs_ag': the sharded moments and gather_state are fp32")
+    if overlap_optimizer:
+        raise ValueError("moment_dtype='bf16' excludes overlap_optimizer: the per-layer deferred stages launch the fp32-moment update")
+
+
 def layer_scale(name: str, depth: int, inter_depth: int, lw_decay: float | None) -> float:
     """The learning-rate scale of the supervised engine's parameter ``name`` under layer-wise decay ``r = lw_decay`` -- the
     baselines' rule (``maestro/baselines/dinov2.py:312-373``: patch_embed ``r^(depth + 1)``, block ``i`` ``r^(depth - i)``, heads
@@ -182,12 +206,25 @@ class FusedAdamW:
     launches above): every launch becomes its grouped form -- ``mh_adamw_groups`` on the slices where ``mh_adamw`` ran,
     ``mh_adamw_groups_dev`` under a guard -- with the map offset to the slice; ``lr`` is then the BASE rate and ``weight_decay`` is
     not read (each group carries its own).  Excludes an fp8 plan and ``step_sharded`` (``refuse_group_conflicts``).  The
-    ``state_dict`` layout is the ungrouped one."""
+    ``state_dict`` layout is the ungrouped one.
 
-    def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.01, groups=None) -> None:
+    ``moment_dtype`` ("fp32", the default = exactly the launches above; "bf16"), ``moment_seed``: with "bf16" ``m`` / ``v`` are
+    bf16 tensors (half the optimizer state, 22 instead of 30 bytes per parameter and step) and every launch of ``step`` -- plain,
+    split, guarded, grouped -- takes its ``_bf16m`` form (include/maestro_hip_moments.h) with ``elem_base`` = the slice's offset in
+    the flat layout: the parameters move by the unrounded fp32 moments, which are then stored by stochastic rounding with words
+    that are a function of ``(moment_seed, t, flat index)``, so a split step, a resumed run and every rank store the same bits.
+    ``state_dict`` hands the moments out upcast to fp32 (exact); ``load_state_dict`` takes fp32 moments from either kind and
+    rounds them to nearest-even into a bf16 optimizer (what a bf16 optimizer saved reloads bit for bit).  Excludes an fp8 plan,
+    ``step_sharded`` and the deferred per-layer stages (``refuse_moment_conflicts``)."""
+
+    def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.01, groups=None,
+                 moment_dtype: str = "fp32", moment_seed: int = 0) -> None:
         import torch
 
+        if moment_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"FusedAdamW: moment_dtype={moment_dtype!r}: expected 'fp32' or 'bf16'")
         self.engine, self.lr, self.betas, self.eps, self.wd = engine, lr, betas, eps, weight_decay
+        self.moment_dtype, self.moment_seed = moment_dtype, int(moment_seed) & 0xFFFFFFFFFFFFFFFF
         st = engine.store
         if groups is not None and groups.total != st.total:
             raise ValueError(f"FusedAdamW: parameter groups over {groups.total} elements, flat layout of {st.total}")
@@ -195,10 +232,17 @@ class FusedAdamW:
         # the engine's trainable slice of the flat buffer (probe phase: the heads only -- frozen parameters must not even
         # see weight decay, as torch.optim.AdamW skips parameters without a gradient)
         self.lo, self.hi = getattr(engine, "trainable_span", (0, st.total))
-        self.m = torch.zeros(self.hi - self.lo, dtype=st.flat.dtype, device=st.flat.device)
+        self.m = torch.zeros(self.hi - self.lo, dtype=torch.bfloat16 if self.bf16_moments else st.flat.dtype, device=st.flat.device)
         self.v = torch.zeros_like(self.m)
         self.t = 0
         self.guard = None
+
+    @property
+    def bf16_moments(self) -> bool:
+        return self.moment_dtype == "bf16"
+
+    def _refuse_moment_conflicts(self) -> None:
+        refuse_moment_conflicts(self.bf16_moments, dtype="fp8" if getattr(self.engine, "fp8", None) is not None else None)
 
     def _step_guarded(self, guard, lr: float, grad_scale: float, between) -> None:
         st, lo, hi = self.engine.store, self.lo, self.hi
@@ -212,7 +256,16 @@ class FusedAdamW:
             between()
         guard.launch(st.grad[lo:hi], lr, self.betas[0], self.betas[1], grad_scale)
         gr = self.groups
-        if gr is not None:
+        if self.bf16_moments:          # Adam's t of this step: the guard's device counter, written by the finish launch above
+            t_dev = guard.t_dev
+            if gr is not None:
+                hip.adamw_groups_bf16m_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], gr.map_at(lo), gr.lr_scale,
+                                           gr.wd, hi - lo, lo, self.moment_seed, self.betas[0], self.betas[1], self.eps, guard.hyper,
+                                           t_dev)
+            else:
+                hip.adamw_bf16m_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], hi - lo, lo, self.moment_seed,
+                                    self.betas[0], self.betas[1], self.eps, self.wd, guard.hyper, t_dev)
+        elif gr is not None:
             hip.adamw_groups_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], gr.map_at(lo), gr.lr_scale, gr.wd,
                                  hi - lo, self.betas[0], self.betas[1], self.eps, guard.hyper)
         else:
@@ -234,6 +287,7 @@ class FusedAdamW:
         import torch
         gr = self.groups
         refuse_group_conflicts(gr is not None, dtype="fp8" if getattr(self.engine, "fp8", None) is not None else None)
+        self._refuse_moment_conflicts()
         roctx = os.environ.get("MAESTRO_ROCTX", "0") == "1"
         if roctx:
             torch.cuda.nvtx.range_push("maestro:adamw")
@@ -258,6 +312,13 @@ class FusedAdamW:
                 hip.adamw_fp8(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b],
                               plan.w8_flat[a:b], plan.slot_map[a // 64:], plan.wsc.scale, plan.wsc.amax, b - a, lr, self.betas[0],
                               self.betas[1], self.eps, self.wd, self.t, grad_scale)
+            elif b > a and self.bf16_moments and gr is not None:
+                hip.adamw_groups_bf16m(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b],
+                                       gr.map_at(a), gr.lr_scale, gr.wd, b - a, a, self.moment_seed, lr, self.betas[0], self.betas[1],
+                                       self.eps, self.t, grad_scale)
+            elif b > a and self.bf16_moments:
+                hip.adamw_bf16m(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], b - a, a,
+                                self.moment_seed, lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t, grad_scale)
             elif b > a and gr is not None:
                 hip.adamw_groups(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], gr.map_at(a),
                                  gr.lr_scale, gr.wd, b - a, lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale)
@@ -281,6 +342,7 @@ class FusedAdamW:
         step are bit-identical on every rank, and equal to the all-reduce plan's up to the summation order inside the collective."""
         st = self.engine.store
         refuse_group_conflicts(self.groups is not None, sharded=True)
+        refuse_moment_conflicts(self.bf16_moments, exchange_mode="rs_ag")
         if getattr(self.engine, "fp8", None) is not None:
             raise hip.HipExtensionError("FusedAdamW.step_sharded: not available with dtype='fp8' (the e4m3 shadows of chunks owned "
                                         "by other ranks would need their scales: use the all-reduce plan)")
@@ -325,16 +387,21 @@ class FusedAdamW:
         # chunks gathered from other ranks go stale), and a deferred / asynchronous checkpoint writer holding them would save a
         # mixed-step Adam state without any error.  ("t" stamps the step the copies belong to.)
         m, v = (self.m.clone(), self.v.clone()) if sharded else (self.m, self.v)
+        if self.bf16_moments:          # bf16 -> fp32 is exact: a checkpoint holds fp32 moments whichever optimizer wrote it
+            m, v = m.float(), v.float()
         if self.guard is not None:     # Adam's step count lives in the guard's device state (a skipped step does not advance it)
             self.t = self.guard.state_dict()["t"]
-        return {"m": m, "v": v, "t": self.t, "lr": self.lr, "span": (self.lo, self.hi),
-                "exchange_mode": "rs_ag" if sharded else "all_reduce", "world": getattr(self, "_sharded_world", 1)}
+        sd = {"m": m, "v": v, "t": self.t, "lr": self.lr, "span": (self.lo, self.hi),
+              "exchange_mode": "rs_ag" if sharded else "all_reduce", "world": getattr(self, "_sharded_world", 1)}
+        if self.bf16_moments:          # (an fp32-moment optimizer's state keeps the keys it always had)
+            sd.update(moment_dtype=self.moment_dtype, moment_seed=self.moment_seed)
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         if "span" in sd and tuple(sd["span"]) != (self.lo, self.hi):
             raise hip.HipExtensionError(f"FusedAdamW.load_state_dict: state of span {tuple(sd['span'])}, optimizer of span {(self.lo, self.hi)}")
-        self.m.copy_(sd["m"])
-        self.v.copy_(sd["v"])
+        self.m.copy_(sd["m"])          # fp32 moments into a bf16 optimizer: copy_ rounds to nearest-even (exact for what a bf16
+        self.v.copy_(sd["v"])          # optimizer saved); the rounding words follow THIS optimizer's moment_seed
         self.t, self.lr = sd["t"], sd["lr"]
         if self.guard is not None:
             self.guard.load_state_dict({"t": self.t})

@@ -13,7 +13,7 @@ import torch
 from maestro_amd.engine import training_warm_passes
 from maestro_amd.train.ddp import GradSync, broadcast_parameters
 from maestro_amd.train.optim import (FusedAdamW, OneCycle, layer_groups, refuse_group_conflicts, refuse_guard_conflicts,
-                                     resolve_grad_guard, resolve_lw_decay, scaled_lr)
+                                     refuse_moment_conflicts, resolve_grad_guard, resolve_lw_decay, resolve_moment_dtype, scaled_lr)
 
 
 def synthetic_batch(dataset, B: int, device, seed: int = 0) -> dict:  # noqa: N803
@@ -61,8 +61,15 @@ class PretrainLoop(_GuardSurface):
                  accumulate: int = 1, overlap_optimizer: bool = False, bucket_dtype=None, dtype: str | None = None,
                  exchange_mode: str | None = None, fp8_scaling: str | None = None, deterministic: bool | None = None,
                  mask_rng: str | None = None, mask_seed: int = 0, row_base: int | None = None,
-                 max_grad_norm: float | None = None, skip_nonfinite: bool | None = None) -> None:
-        """``max_grad_norm`` / ``skip_nonfinite`` (None reads ``MAESTRO_MAX_GRAD_NORM`` / ``MAESTRO_SKIP_NONFINITE``, "1" = on): the
+                 max_grad_norm: float | None = None, skip_nonfinite: bool | None = None, moment_dtype: str | None = None,
+                 moment_seed: int = 0) -> None:
+        """``moment_dtype`` ("fp32" / "bf16"; None reads ``MAESTRO_MOMENT_DTYPE``, unset, empty or "fp32" = off), ``moment_seed``:
+        AdamW's moments held as bf16 with stochastic rounding inside the fused launch (``FusedAdamW``,
+        include/maestro_hip_moments.h): half the optimizer state, 22 instead of 30 bytes per parameter and step.  Off by default:
+        the step is then launch for launch the fp32-moment one.  Excludes ``dtype="fp8"``, ``exchange_mode="rs_ag"`` and
+        ``overlap_optimizer``; allowed in deterministic mode, with the gradient guard and with the all-reduce exchange (every rank
+        draws the same rounding words, so the parameters stay identical across ranks).
+        ``max_grad_norm`` / ``skip_nonfinite`` (None reads ``MAESTRO_MAX_GRAD_NORM`` / ``MAESTRO_SKIP_NONFINITE``, "1" = on): the
         gradient guard (``hip.GradGuard``, include/maestro_hip_guard.h) -- the global L2 norm of the reduced gradient is taken on
         the device, the clipping coefficient ``min(1, max_grad_norm / (norm + 1e-6))`` rides in AdamW's gradient scale, and with
         ``skip_nonfinite`` a step whose gradient holds an inf / NaN (or whose norm overflows) leaves weights, moments and Adam's
@@ -86,6 +93,9 @@ class PretrainLoop(_GuardSurface):
         max_norm, skip = resolve_grad_guard(max_grad_norm, skip_nonfinite)
         guarded = max_norm is not None or skip
         refuse_guard_conflicts(guarded, overlap_optimizer, dtype or os.environ.get("MAESTRO_DTYPE", "bf16"), self.exchange_mode)
+        moment_dtype = resolve_moment_dtype(moment_dtype)
+        refuse_moment_conflicts(moment_dtype == "bf16", overlap_optimizer, dtype or os.environ.get("MAESTRO_DTYPE", "bf16"),
+                                self.exchange_mode)
         from maestro_amd.engine import resolve_deterministic
         if resolve_deterministic(deterministic):     # refused before anything is built
             if overlap_optimizer:
@@ -101,13 +111,15 @@ class PretrainLoop(_GuardSurface):
         self.engine.row_base = int(row_base)
         self.engine.warm_passes = training_warm_passes()     # a training entry point: start-up passes on (engine.py: warm_passes)
         refuse_guard_conflicts(guarded, dtype="fp8" if self.engine.fp8 is not None else "bf16")   # (dtype=None kept an fp8 engine)
+        refuse_moment_conflicts(moment_dtype == "bf16", dtype="fp8" if self.engine.fp8 is not None else "bf16")
         if overlap_optimizer and self.engine.fp8 is not None:
             raise ValueError("overlap_optimizer is not available with dtype='fp8' (the e4m3 weight shadows are rebuilt after the update)")
         broadcast_parameters(self.engine)   # every rank starts from rank 0's weights (what Lightning's DDP wrap does)
         lr = scaled_lr(base_lr, batch_size, accumulate, 1, world_size)   # model.py:120-128: micro-batches count towards the batch
         self.sched = OneCycle(lr, max(total_steps, 2), pct_start=0.2, div_factor=1000.0,
                               final_div_factor=final_factor / 1000.0)
-        self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay)
+        self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay, moment_dtype=moment_dtype,
+                              moment_seed=moment_seed)
         self.guard = _make_guard(self.opt, device, max_norm, skip) if guarded else None
         exchange = world_size > 1 if exchange is None else exchange   # True at world_size 1: one-rank rehearsal of the launch plan
         st = self.engine.store
@@ -262,13 +274,18 @@ class SupervisedLoop(_GuardSurface):
     (``optim.layer_groups``, ``mh_adamw_groups``); with neither the loop issues exactly the ungrouped launches.  The schedule
     stays the ONE scalar ``OneCycle``: ``OneCycleLR`` is linear in ``max_lr`` -- its initial and final rates are ``max_lr``
     divided by constants, and the cosine interpolates between them -- so ``sched.lr(t) * scale_g`` IS the reference's
-    per-group ``OneCycleLR(max_lr=[lr * scale_g ...])`` at every step.  ``phase="probe"`` with a decay is a ``ValueError``."""
+    per-group ``OneCycleLR(max_lr=[lr * scale_g ...])`` at every step.  ``phase="probe"`` with a decay is a ``ValueError``.
+
+    ``moment_dtype`` / ``moment_seed``: bf16 moments as in :class:`PretrainLoop` (None reads ``MAESTRO_MOMENT_DTYPE``); the grouped
+    and guarded launches take their ``_bf16m`` forms."""
 
     def __init__(self, model, batch_size: int, device, phase: str = "finetune", base_lr: float = 3e-5, betas=(0.9, 0.99),
                  weight_decay: float = 0.01, total_steps: int = 1000, world_size: int = 1, final_factor: float = 1e7,
                  bucket_mb: int = 64, exchange: bool | None = None, bucket_dtype=None, max_grad_norm: float | None = None,
-                 skip_nonfinite: bool | None = None, lw_decay: float | None = None, no_decay_1d: bool = False) -> None:
+                 skip_nonfinite: bool | None = None, lw_decay: float | None = None, no_decay_1d: bool = False,
+                 moment_dtype: str | None = None, moment_seed: int = 0) -> None:
         max_norm, skip = resolve_grad_guard(max_grad_norm, skip_nonfinite)      # (refused before anything is built)
+        moment_dtype = resolve_moment_dtype(moment_dtype)
         lw_decay = resolve_lw_decay(lw_decay)
         refuse_group_conflicts(lw_decay is not None or no_decay_1d, phase=phase, lw_decay=lw_decay)
         self.engine = model.sup_engine(batch_size, device, phase)
@@ -278,7 +295,8 @@ class SupervisedLoop(_GuardSurface):
         self.sched = OneCycle(lr, max(total_steps, 2), pct_start=0.2, div_factor=1000.0,
                               final_div_factor=final_factor / 1000.0)
         self.groups = layer_groups(self.engine, lw_decay, weight_decay, no_decay_1d)      # None: no groups, the ungrouped launches
-        self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay, groups=self.groups)
+        self.opt = FusedAdamW(self.engine, lr, betas=betas, weight_decay=weight_decay, groups=self.groups, moment_dtype=moment_dtype,
+                              moment_seed=moment_seed)
         self.guard = _make_guard(self.opt, device, max_norm, skip) if (max_norm is not None or skip) else None
         lo, hi = self.engine.trainable_span
         st = self.engine.store
