@@ -502,6 +502,53 @@ int mh_count_masked(const uint8_t* mask, int B, int L, int t_lo, int t_hi, int* 
  * patch sizes in elements (mult = P*P*bands of the group); the denominator of mh_masked_loss_bands. */
 int mh_count_masked_elems(const uint8_t* mask, int B, int L, int t_lo, int t_hi, int* out, int mult, int accumulate, void* stream);
 
+/* Device-side mask draws: the structural Bernoulli masks and the per-token noise of the masking step that the reference draws
+ * from torch's generator in maestro/ssl/mae.py:178-246 (structural masks with their rejection loop 178-226, the rand(B, L) noise
+ * and its argsort 228-246), restated on a counter-based generator so that the draws of a step are a pure function of
+ * (seed, step, global sample index).  No atomics.
+ *
+ * THE DRAW FUNCTION.  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85, ten rounds), key = (seed & 0xffffffff, seed >> 32), counter
+ *     c0 = i >> 2,   c1 = global row,   c2 = step,   c3 = kind | stream << 4 | attempt << 16
+ * and U(seed, step, stream, kind, row, attempt, i) = (float)(word[i & 3] >> 8) * 2^-24: 24 bits in [0, 1), the value set of
+ * torch.rand.  kind: 0 noise (i = token, attempt 0), 1 mod (i = 0), 2 bands (i = band-group), 3 dates (i = date slot),
+ * 4 loc (i = token of the modality's grid).  A Bernoulli draw is U < p with p as float32. */
+#define MH_MASK_KIND_NOISE 0
+#define MH_MASK_KIND_MOD 1
+#define MH_MASK_KIND_BANDS 2
+#define MH_MASK_KIND_DATES 3
+#define MH_MASK_KIND_LOC 4
+#define MH_MASK_MAX_ATTEMPTS 64   /* the counted rejection loop: a row that is all-masked 64 times is stored all-clear */
+#define MH_MASK_MAX_L 8192
+#define MH_MASK_MAX_STREAMS 4096  /* stream ids are 12 bits of c3 */
+/* One modality (or band-group) inside a group's token row: tokens tok_off ... tok_off + D * L - 1, token (d, l) at d * L + l.
+ * mk(d, l) = OR over the active kinds of (U < p): mod at i = 0, bands at i = gi, dates at i = d, loc at i = l, all on `stream`
+ * (the modality's index) and the structural row; p < 0 (or 0) = the kind is off (the reference's None). */
+typedef struct {
+    int tok_off, D, L, gi, G, stream;
+    float p_mod, p_bands, p_dates, p_loc;
+} MhMaskSeg;
+/* One group: noise f32 [Beff, L] and struct u8 [Beff, L] (dense rows; 1 = structurally masked).
+ *   structural row of r:  row_base * struct_rpb + r
+ *   noise row of r:       row_base * noise_rpb + (r / row_div) * row_mul + row_add + r % row_div
+ * (the affine map picks rows (b, draw_g, d) of a [B, draw_G, D] draw: row_div = D, row_mul = draw_G * D, row_add = draw_g * D;
+ * 1, 1, 0 = the identity).  *_rpb = rows of the draw tensor per sample.  Segments seg0 ... seg0 + n_segs - 1 of the segment
+ * table tile [0, L) in order.  The row kept is that of the first attempt a = 0, 1, ... whose row is not all-masked. */
+typedef struct {
+    float* noise;
+    unsigned char* strct;
+    int Beff, L;
+    int noise_stream, noise_rpb, struct_rpb;
+    int row_div, row_mul, row_add;
+    int seg0, n_segs;
+} MhMaskJob;
+/* All groups of a step in ONE launch (one workgroup per (group, row)).  The tables are given twice: the host copies are
+ * checked before the launch (null pointers, 1 <= L <= MH_MASK_MAX_L, segments that do not tile the row, stream ids, row
+ * indices that leave 32 bits), the device copies are what the kernel reads.  n_jobs >= 1, 0 <= step <= 2^32 - 1,
+ * row_base >= 0; seed, step and row_base are by-value: nothing of a step is baked into a captured graph's table. */
+int mh_mask_draw(const MhMaskJob* jobs_host, const MhMaskJob* jobs_device, int n_jobs, const MhMaskSeg* segs_host,
+                 const MhMaskSeg* segs_device, int n_segs, uint64_t seed, long long step, long long row_base, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- loss
  * Masked reconstruction loss at patch layout (maestro/train/model.py:195-247) for one modality: rec f32 [B*Lm, PPC]
  * (pixelify GEMM output), target f32 [B*Lm, PPC] (mh_patchify), mask_group u8 [B, Lgroup] (token (b,t) of the modality
@@ -644,6 +691,129 @@ int mh_adamw_fp8(float* p, const float* g, float* m, float* v, void* p_bf16, voi
  * active}; active == 0 makes the launch a no-op (no update pending). */
 int mh_adamw_dev(float* p, const float* g, float* m, float* v, void* p_bf16, long n, float b1, float b2, float eps,
                  float wd, const float* hyper, void* stream);
+
+/* AdamW parameter groups: per-group learning-rate scale and weight decay inside the one fused launch over the flat parameter
+ * buffer.
+ *
+ * What it answers in the reference: the finetune configuration's layer-wise learning-rate decay.  OptFinetuneConfig.lw_decay
+ * (maestro/conf/opt.py:51) is handed on by SSLTrainer (maestro/train/trainer.py:43-52); maestro/train/baseline.py:110-131 turns it
+ * into AdamW parameter groups and a per-group OneCycleLR(max_lr=[...]); the groups are geometric in depth
+ * (maestro/baselines/dinov2.py:312-373): patch_embed at rate^(depth + 1), block i at rate^(depth - i), heads at the base rate.
+ * OneCycleLR is linear in max_lr, so a per-group rate is the scalar schedule times a constant scale: that scale is what the
+ * table below holds.  The other use of parameter groups, no weight decay on 1-d parameters, is the second table.
+ *
+ * The update arithmetic is mh_adamw's, one function in the library: a launch of mh_adamw_groups gives, on every span of one
+ * group, the bits of mh_adamw over that span with lr = fmul_rn(lr, lr_scale[g]) and wd = wd[g]. */
+/* Elements per byte of the group map (the alignment of every parameter in the flat layout) and the length of both tables. */
+#define MH_ADAMW_GROUP_BLOCK 64
+#define MH_ADAMW_GROUP_TABLE 256
+/* mh_adamw with per-group learning-rate scale and weight decay.  group_of[i / 64] = group of element i (parameters are
+ * 64-element aligned; p must start on a 64-element block of the layout the map was built for, the caller offsets the map
+ * pointer for a slice): ceil(n / 64) bytes are read.  lr_scale and wd are DEVICE float[256] tables (always 256 long, so any
+ * byte of the map indexes inside them); element i is updated with lr_g = fmul_rn(lr, lr_scale[g]) and wd[g].  p, g, m, v: f32,
+ * 16-byte aligned; p_bf16 (may be null): the bf16 shadow of p, 8-byte aligned.  n > 0, n % 4 == 0, step >= 1. */
+int mh_adamw_groups(float* p, const float* g, float* m, float* v, void* p_bf16, const unsigned char* group_of,
+                    const float* lr_scale, const float* wd, long n, float lr, float b1, float b2, float eps, int step,
+                    float grad_scale, void* stream);
+/* The same with {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale, active} from device memory (mh_adamw_dev's hyper[5]): with
+ * hyper[4] == 0 the kernel returns before it touches memory. */
+int mh_adamw_groups_dev(float* p, const float* g, float* m, float* v, void* p_bf16, const unsigned char* group_of,
+                        const float* lr_scale, const float* wd, long n, float b1, float b2, float eps,
+                        const float* hyper, void* stream);
+
+/* AdamW with bf16 moments: both Adam moments stored as bf16 with stochastic rounding inside the one fused launch.  The update
+ * stream drops from 30 to 22 bytes per parameter (p 8, g 4, m16 4, v16 4, bf16 shadow 2) and the optimizer state from 8 to 4
+ * bytes per parameter.  No atomics.
+ *
+ * ARITHMETIC.  The update is mh_adamw's, one function in the library.  Per element: the stored moments are upcast exactly
+ * (bits << 16); the new fp32 moments, the weight decay and the parameter step are computed as mh_adamw computes them -- the
+ * parameter therefore moves by the UNROUNDED new moments; each new moment is then stored as bf16 by stochastic rounding.  A
+ * launch gives the p / p_bf16 bits of mh_adamw started from the upcast moments.
+ *
+ * STOCHASTIC ROUNDING, on bits.  u = the fp32 pattern, r = a 16-bit random word:
+ *     u inf or NaN:  store u >> 16; a NaN whose surviving mantissa bits are all zero gets the quiet bit (0x0040)
+ *     else t = u + r:  t carried into an all-ones exponent -> store u >> 16 (stays finite), else store t >> 16
+ * The magnitude goes up with probability low16(u) / 65536: a value representable in bf16 is stored exactly, the expectation
+ * of the stored value is the fp32 value, negative values mirror positive ones, v stays non-negative.
+ *
+ * RANDOM WORDS.  Philox4x32-10 as for the mask draws (mh_mask_draw: same multipliers, key increments and rounds), one call per
+ * quad of elements: key = (seed & 0xffffffff, seed >> 32), counter
+ *     c0 = (elem_base + i) / 4 (low 32 bits),   c1 = step (low 32 bits),   c2 = 0,   c3 = MH_ADAMW_SR_TAG
+ * and element e = (elem_base + i) % 4 of the quad takes
+ *     m:  (w[e >> 1] >> 16 * (e & 1)) & 0xffff        v:  (w[2 + (e >> 1)] >> 16 * (e & 1)) & 0xffff
+ * elem_base is the offset of p[0] in the caller's flat layout: a split launch, a slice and one whole launch store the same
+ * bits.  step is Adam's t after the increment.  MH_ADAMW_SR_TAG differs from every c3 of the mask draws (kind | stream << 4 |
+ * attempt << 16 stays below 2^22 there), so no counter of the rounding draws is a counter of a mask draw under the same seed.
+ *
+ * p, g: f32, 16-byte aligned; m16, v16, p_bf16 (may be null): bf16, 8-byte aligned (one 8-byte store per quad each).
+ * n > 0, n % 4 == 0, elem_base >= 0, elem_base % 4 == 0 (% 64 in the grouped forms: the map has one byte per 64 elements),
+ * step >= 1. */
+#define MH_ADAMW_SR_TAG 0x5352424Du /* c3 of every rounding draw ("SRBM") */
+/* mh_adamw with bf16 moments. */
+int mh_adamw_bf16m(float* p, const float* g, void* m16, void* v16, void* p_bf16, long n, long elem_base, uint64_t seed, float lr,
+                   float b1, float b2, float eps, float wd, int step, float grad_scale, void* stream);
+/* mh_adamw_dev with bf16 moments: hyper = {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale, active} (mh_adamw_dev's float[5]), step_dev =
+ * a device word holding Adam's t (MhGuardState.t, read after mh_grad_guard_finish): its low 32 bits are the counter's step.
+ * With hyper[4] == 0 the kernel returns before it touches memory. */
+int mh_adamw_bf16m_dev(float* p, const float* g, void* m16, void* v16, void* p_bf16, long n, long elem_base, uint64_t seed,
+                       float b1, float b2, float eps, float wd, const float* hyper, const long long* step_dev, void* stream);
+/* mh_adamw_groups with bf16 moments: group_of, lr_scale, wd as in mh_adamw_groups (p starts on a 64-element block of the
+ * layout the map was built for, so elem_base % 64 == 0). */
+int mh_adamw_groups_bf16m(float* p, const float* g, void* m16, void* v16, void* p_bf16, const unsigned char* group_of,
+                          const float* lr_scale, const float* wd, long n, long elem_base, uint64_t seed, float lr, float b1,
+                          float b2, float eps, int step, float grad_scale, void* stream);
+/* mh_adamw_groups_dev with bf16 moments (hyper and step_dev as above). */
+int mh_adamw_groups_bf16m_dev(float* p, const float* g, void* m16, void* v16, void* p_bf16, const unsigned char* group_of,
+                              const float* lr_scale, const float* wd, long n, long elem_base, uint64_t seed, float b1, float b2,
+                              float eps, const float* hyper, const long long* step_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------- gradient guard
+ * The global L2 norm of the flat gradient buffer, the clipping coefficient and the non-finite skip, computed on the device and
+ * handed to mh_adamw_dev through its five device scalars.
+ *
+ * What it answers in the reference: the trainer runs precision="16-mixed" (maestro/conf/trainer.py:13), so Lightning's GradScaler
+ * skips the optimizer step of maestro/train/model.py:135-140 (AdamW + OneCycleLR) whenever a gradient is inf / NaN, and a
+ * Trainer(gradient_clip_val=...) clips by the global norm with torch.nn.utils.clip_grad_norm_, whose coefficient rule
+ *     coef = min(1, max_norm / (norm + 1e-6))
+ * is restated here.  A skipped step does not advance Adam's step count (GradScaler semantics).
+ *
+ * No atomics: every sum has ONE order, fixed by the arguments, so the same gradient gives the same bits on every run and on
+ * every rank. */
+/* Elements per workgroup of the first phase (256 threads, 16 float4 loads per lane).  Why 16384: a lane's 16 loads (64 registers)
+ * leave before the first is consumed and the kernel, at 72 registers, still runs 7 waves per SIMD; the C3 gradient (176 M elements) gives
+ * 10.7 k workgroups = 42 per CU, so the ragged tail of the grid is 2 % of it; and the partials of that buffer (43 KB + 43 KB)
+ * are summed by the ONE workgroup of the second phase in 42 strided loads per thread.  A smaller chunk lengthens that serial
+ * second phase, a larger one leaves the small trainable spans (probe: a few workgroups) with even fewer.  The partial layout
+ * is a function of n alone. */
+#define MH_GUARD_CHUNK 16384
+/* Caller-owned DEVICE struct, zeroed once; mh_grad_guard_finish reads and writes it. */
+typedef struct {
+    float norm;          /* |grad_scale| * sqrt(sum g^2) of the last call */
+    float coef;          /* clipping coefficient of the last call (1 = not clipped) */
+    int finite;          /* 1: the norm is finite and no element was inf / NaN */
+    unsigned bad;        /* number of inf / NaN elements (saturating) */
+    long long t;         /* Adam's step count: advanced by every APPLIED step */
+    long long skipped;   /* number of skipped steps */
+} MhGuardState;
+/* ceil(n / MH_GUARD_CHUNK): rows of `partial` and `bad` for a gradient of n elements (0 for n <= 0). */
+long mh_grad_sumsq_partial_rows(long n);
+/* First phase.  Workgroup i: partial[i] = sum of g[j]^2 and bad[i] = number of j whose exponent bits are all ones (inf, NaN),
+ * j in [i * MH_GUARD_CHUNK, min(n, (i + 1) * MH_GUARD_CHUNK)); plain stores, every row is written.  g: f32, 16-byte aligned,
+ * n > 0, n % 4 == 0.  Order of the additions: lane (of 256) l accumulates acc[c] = fma(g, g, acc[c]) over its float4s
+ * k = 0 ... 15 at element 4 * (256 * k + l) + c of the chunk, in k order, c = 0 ... 3; lane sum (acc[0] + acc[1]) + (acc[2] + acc[3]);
+ * xor-butterfly over the wave (offsets 32, 16, ... 1); ((w0 + w1) + w2) + w3 over the four waves. */
+int mh_grad_sumsq_partial(const float* g, long n, float* partial, unsigned* bad, void* stream);
+/* Second phase, one workgroup.  rows = mh_grad_sumsq_partial_rows(n) of the first phase (1 <= rows <= 2^24).
+ *   S      = sum of partial[0 ... rows) in double (thread l of 256: rows l, l + 256, ... in order; then a fixed binary tree)
+ *   norm   = (float)(|grad_scale| * sqrt(S));   bad = min(sum of bad[i], UINT_MAX)
+ *   finite = isfinite(norm) && bad == 0        (a finite gradient whose sum of squares overflows fp32 counts as non-finite)
+ *   coef   = (max_norm > 0 && finite) ? min(1, max_norm / (norm + 1e-6f)) : 1
+ *   apply  = finite || !skip_nonfinite;  apply ? state->t += 1 : state->skipped += 1
+ *   hyper[0 ... 5) = {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale * coef, apply ? 1 : 0}   with t after the increment, the two
+ *            correction terms computed in double from the float b1 / b2 and rounded once -- mh_adamw_dev's five scalars.
+ * norm, coef, finite, bad are stored in *state.  grad_scale, max_norm, lr finite (max_norm <= 0: no clipping), 0 <= b1, b2 < 1. */
+int mh_grad_guard_finish(const float* partial, const unsigned* bad, long rows, float grad_scale, float max_norm,
+                         int skip_nonfinite, float lr, float b1, float b2, float* hyper, MhGuardState* state, void* stream);
 
 #ifdef __cplusplus
 }

@@ -50,9 +50,7 @@ def _hipcc() -> str:
 
 def _digest(src: Path) -> str:
     h = hashlib.sha256()
-    for f in [src, *sorted(CSRC.glob("*.hpp")), ROOT / "include" / "maestro_hip.h",
-              ROOT / "include" / "maestro_hip_rng.h", ROOT / "include" / "maestro_hip_guard.h",
-              ROOT / "include" / "maestro_hip_optim.h", ROOT / "include" / "maestro_hip_moments.h"]:   # every shared header: none can leave stale objects
+    for f in [src, *sorted(CSRC.glob("*.hpp")), ROOT / "include" / "maestro_hip.h"]:   # every shared header: none can leave stale objects
         h.update(f.read_bytes())
     h.update(" ".join(FLAGS + FILE_FLAGS.get(src.name, [])).encode())
     return h.hexdigest()[:16]

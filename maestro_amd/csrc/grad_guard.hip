@@ -1,10 +1,10 @@
-// Gradient guard (include/maestro_hip_guard.h): global L2 norm of the flat gradient buffer, clipping coefficient and the
+// Gradient guard (include/maestro_hip.h): global L2 norm of the flat gradient buffer, clipping coefficient and the
 // non-finite skip, as the five device scalars of mh_adamw_dev.  Two launches: mh_grad_sumsq_partial streams the gradient once
 // (one f32 partial and one inf / NaN count per MH_GUARD_CHUNK elements, plain stores), mh_grad_guard_finish -- one workgroup --
 // sums the partials in double and writes hyper[5] + the MhGuardState.  No atomics, every order of additions is fixed by
 // (n, lane, wave): the same gradient gives the same bits on every run.
 #include "common.hpp"
-#include "../../include/maestro_hip_guard.h"
+#include "../../include/maestro_hip.h"
 #include <limits.h>
 
 // Loads of the streaming phase: 0 = plain (default), 1 = nontemporal.  Alone, over the 705 MB gradient of C3, the nontemporal form

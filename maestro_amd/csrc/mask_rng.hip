@@ -1,10 +1,10 @@
-// Device-side mask draws (mh_mask_draw, include/maestro_hip_rng.h): the structural Bernoulli masks with their rejection loop
+// Device-side mask draws (mh_mask_draw, include/maestro_hip.h): the structural Bernoulli masks with their rejection loop
 // and the per-token noise of maestro/ssl/mae.py:178-246 on Philox4x32-10.  One workgroup per (group, row): first the
 // structural row (counted attempt loop, all-masked test = workgroup-wide AND through LDS), then the noise row (four values per
 // Philox call, one 16-byte store where the row is 16-byte aligned).  Integer ALU + a few hundred KB of stores; no atomics.
 #include "common.hpp"
 #include "philox.hpp"
-#include "../../include/maestro_hip_rng.h"
+#include "../../include/maestro_hip.h"
 
 namespace {
 

@@ -965,7 +965,7 @@ class MAEEngine(EngineBase):
 
         ``mask_rng``: "host" (default; None reads ``MAESTRO_MASK_RNG``) draws the masks of a step on the host generator in the
         reference's order and uploads them; "device" draws them with one ``mh_mask_draw`` launch as a pure function of
-        ``(mask_seed, mask_step, row_base + sample)`` (include/maestro_hip_rng.h): no host arithmetic, no upload, and the same
+        ``(mask_seed, mask_step, row_base + sample)`` (include/maestro_hip.h): no host arithmetic, no upload, and the same
         masks after a resume or under another split of the global batch.  ``mask_step`` is a public, settable int that every
         drawing forward advances by one; ``row_base`` (settable too) is the global index of this rank's first sample.  A
         forward that is handed ``noise=`` / ``struct=`` takes the host path for that call.  Not with ``tie_order="torch"``."""

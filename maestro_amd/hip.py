@@ -56,23 +56,22 @@ def lib() -> ctypes.CDLL:
                                          ctypes.c_float, vp]               # input staging
         _lib.mh_select_dates.restype = ci
         _lib.mh_mask_draw.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_longlong, vp]   # device-side draws
-        _lib.mh_mask_draw.restype = ci                                      # (include/maestro_hip_rng.h)
-        cl, cf = ctypes.c_long, ctypes.c_float                              # gradient guard (include/maestro_hip_guard.h)
-        _lib.mh_grad_sumsq_partial_rows.argtypes = [cl]
+        _lib.mh_mask_draw.restype = ci
+        cl, cf, u64 = ctypes.c_long, ctypes.c_float, ctypes.c_uint64
+        _lib.mh_grad_sumsq_partial_rows.argtypes = [cl]                     # gradient guard
         _lib.mh_grad_sumsq_partial_rows.restype = cl
         _lib.mh_grad_sumsq_partial.argtypes = [vp, cl, vp, vp, vp]
         _lib.mh_grad_guard_finish.argtypes = [vp, vp, cl, cf, cf, ci, cf, cf, cf, vp, vp, vp]
         _lib.mh_grad_sumsq_partial.restype = _lib.mh_grad_guard_finish.restype = ci
-        _lib.mh_adamw_groups.argtypes = [vp] * 8 + [cl, cf, cf, cf, cf, ci, cf, vp]     # parameter groups (include/maestro_hip_optim.h)
+        # AdamW: {plain | grouped} x {host | device scalars}, fp32 moments, then the same four with bf16 moments (elem_base, seed)
+        _lib.mh_adamw_groups.argtypes = [vp] * 8 + [cl, cf, cf, cf, cf, ci, cf, vp]
         _lib.mh_adamw_groups_dev.argtypes = [vp] * 8 + [cl, cf, cf, cf, vp, vp]
-        _lib.mh_adamw_groups.restype = _lib.mh_adamw_groups_dev.restype = ci
-        u64 = ctypes.c_uint64                                               # bf16 moments (include/maestro_hip_moments.h)
         _lib.mh_adamw_bf16m.argtypes = [vp] * 5 + [cl, cl, u64, cf, cf, cf, cf, cf, ci, cf, vp]
         _lib.mh_adamw_bf16m_dev.argtypes = [vp] * 5 + [cl, cl, u64, cf, cf, cf, cf, vp, vp, vp]
         _lib.mh_adamw_groups_bf16m.argtypes = [vp] * 8 + [cl, cl, u64, cf, cf, cf, cf, ci, cf, vp]
         _lib.mh_adamw_groups_bf16m_dev.argtypes = [vp] * 8 + [cl, cl, u64, cf, cf, cf, vp, vp, vp]
-        _lib.mh_adamw_bf16m.restype = _lib.mh_adamw_bf16m_dev.restype = ci
-        _lib.mh_adamw_groups_bf16m.restype = _lib.mh_adamw_groups_bf16m_dev.restype = ci
+        for name in ("groups", "groups_dev", "bf16m", "bf16m_dev", "groups_bf16m", "groups_bf16m_dev"):
+            getattr(_lib, "mh_adamw_" + name).restype = ci
     return _lib
 
 
@@ -525,7 +524,7 @@ class OrderedReduce:
             ev[1].record()
 
 
-# ---- device-side mask draws (include/maestro_hip_rng.h)
+# ---- device-side mask draws
 MASK_MAX_L, MASK_MAX_STREAMS = 8192, 4096     # MH_MASK_MAX_L, MH_MASK_MAX_STREAMS
 
 
@@ -592,7 +591,7 @@ def mask_draw_reference(groups, mods, B, seed, step, row_base=0):  # noqa: N803
     return reference(groups, mods, B, seed, step, row_base)
 
 
-# ---- gradient guard (include/maestro_hip_guard.h)
+# ---- gradient guard
 GUARD_CHUNK = 16384     # MH_GUARD_CHUNK
 
 
@@ -619,7 +618,7 @@ def grad_guard_finish(partial, bad, rows, grad_scale, max_norm, skip_nonfinite, 
 
 class GradGuard:
     """Device-side global gradient norm, clipping coefficient and non-finite skip over a flat f32 gradient of ``n`` elements
-    (include/maestro_hip_guard.h).  Owns the partial rows, the five scalars ``hyper`` that ``adamw_dev`` reads and the device
+    (include/maestro_hip.h).  Owns the partial rows, the five scalars ``hyper`` that ``adamw_dev`` reads and the device
     ``MhGuardState`` (Adam's step count ``t`` lives THERE: a skipped step does not advance it).  ``launch`` issues the two
     kernels; ``norm`` / ``coef`` / ``hyper`` are device views, nothing on the step path reads them on the host.  ``max_norm``
     None or <= 0: no clipping.  No atomics and one fixed order of additions: the same gradient gives the same bits."""
@@ -1099,9 +1098,41 @@ def unpack_rows_add(src, dst, E, K, Kpad):
     call("mh_unpack_rows_add", src, dst, _I(E), _I(K), _I(Kpad))
 
 
+GROUP_BLOCK, GROUP_TABLE = 64, 256      # MH_ADAMW_GROUP_BLOCK, MH_ADAMW_GROUP_TABLE
+ADAMW_SR_TAG = 0x5352424D               # MH_ADAMW_SR_TAG: c3 of every rounding draw
+_U64 = ctypes.c_uint64
+
+
+def _adamw(p, g, m, v, p_bf16, n, b1, b2, eps, *, wd=None, groups=None, scalars=None, hyper=None, draws=None, step_dev=None):
+    """The eight forms {fp32 | bf16 moments} x {plain | grouped} x {host | device scalars} of ``mh_adamw`` behind the wrappers
+    below; what is given selects the entry.  ``groups = (group_of, lr_scale, wd)`` in place of ``wd``; ``scalars = (lr, step,
+    grad_scale)`` or the device tensor ``hyper``; ``draws = (elem_base, seed)``: m and v are bf16 (then the device form also takes
+    ``step_dev``).  Algorithmic bytes per parameter: 30, or 22 with bf16 moments, minus an absent shadow."""
+    what = "adamw" + ("_groups" if groups is not None else "") + ("_bf16m" if draws is not None else "") + ("_dev" if scalars is None else "")
+    if groups is not None:      # the sizes the kernel relies on: one map byte per 64-element block of [0, n), two tables of 256 floats
+        group_of, lr_scale, wd_of = groups
+        if group_of.dtype != torch.uint8 or not group_of.is_contiguous() or group_of.numel() < -(-int(n) // GROUP_BLOCK):
+            raise HipExtensionError(f"{what}: the group map must be a dense uint8 tensor of at least ceil(n / {GROUP_BLOCK}) = "
+                                    f"{-(-int(n) // GROUP_BLOCK)} bytes")
+        for name, t in (("lr_scale", lr_scale), ("wd", wd_of)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != GROUP_TABLE:
+                raise HipExtensionError(f"{what}: {name} must be a dense f32 table of exactly {GROUP_TABLE} entries")
+    if draws is not None:       # a fp32 buffer handed to these entries would be read as twice as many bf16
+        for name, t in (("m16", m), ("v16", v)):
+            if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() < int(n):
+                raise HipExtensionError(f"{what}: {name} must be a dense bfloat16 tensor of at least n = {int(n)} elements")
+        if scalars is None and (step_dev.dtype != torch.int64 or step_dev.numel() < 1):
+            raise HipExtensionError(f"{what}: step_dev must be an int64 tensor")
+    args = [p, g, m, v, p_bf16, *(groups or ()), _L(n)]
+    if draws is not None:
+        args += [_L(draws[0]), _U64(int(draws[1]) & 0xFFFFFFFFFFFFFFFF)]
+    args += ([] if scalars is None else [_F(scalars[0])]) + [_F(b1), _F(b2), _F(eps)] + ([] if groups is not None else [_F(wd)])
+    args += [_I(scalars[1]), _F(scalars[2])] if scalars is not None else [hyper] + ([step_dev] if draws is not None else [])
+    _hbm_call("adamw", float(n) * ((22 if draws is not None else 30) - 2 + _esz(p_bf16)), "mh_" + what, *args)
+
+
 def adamw(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, step, grad_scale=1.0):
-    _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw", p, g, m, v, p_bf16, _L(n), _F(lr), _F(b1), _F(b2), _F(eps), _F(wd),
-              _I(step), _F(grad_scale))
+    _adamw(p, g, m, v, p_bf16, n, b1, b2, eps, wd=wd, scalars=(lr, step, grad_scale))
 
 
 def adamw_fp8(p, g, m, v, p_bf16, p_fp8, slot_map, scale, amax, n, lr, b1, b2, eps, wd, step, grad_scale=1.0):
@@ -1131,86 +1162,44 @@ def adamw_bias_corrections(b1: float, b2: float, step: int) -> tuple[float, floa
 
 def adamw_dev(p, g, m, v, p_bf16, n, b1, b2, eps, wd, hyper):
     """AdamW with {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale, active} read from the device tensor ``hyper`` (graph-capturable)."""
-    _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_dev", p, g, m, v, p_bf16, _L(n), _F(b1), _F(b2), _F(eps), _F(wd), hyper)
-
-
-# ---- AdamW parameter groups (include/maestro_hip_optim.h)
-GROUP_BLOCK, GROUP_TABLE = 64, 256      # MH_ADAMW_GROUP_BLOCK, MH_ADAMW_GROUP_TABLE
-
-
-def _check_groups(what, group_of, lr_scale, wd, n):
-    """The sizes the kernel relies on: one map byte per 64-element block of ``[0, n)`` and two tables of 256 floats."""
-    if group_of.dtype != torch.uint8 or not group_of.is_contiguous() or group_of.numel() < -(-int(n) // GROUP_BLOCK):
-        raise HipExtensionError(f"{what}: the group map must be a dense uint8 tensor of at least ceil(n / {GROUP_BLOCK}) = "
-                                f"{-(-int(n) // GROUP_BLOCK)} bytes")
-    for name, t in (("lr_scale", lr_scale), ("wd", wd)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != GROUP_TABLE:
-            raise HipExtensionError(f"{what}: {name} must be a dense f32 table of exactly {GROUP_TABLE} entries")
+    _adamw(p, g, m, v, p_bf16, n, b1, b2, eps, wd=wd, hyper=hyper)
 
 
 def adamw_groups(p, g, m, v, p_bf16, group_of, lr_scale, wd, n, lr, b1, b2, eps, step, grad_scale=1.0):
     """``adamw`` with per-group hyper-parameters: element ``i`` is updated with ``lr * lr_scale[group_of[i // 64]]`` (one fp32
     product) and ``wd[group_of[i // 64]]``; ``group_of`` uint8 (``p`` starts on a 64-element block of the layout the map was
     built for), ``lr_scale`` / ``wd`` f32 tables of 256 entries (``ParamGroups`` owns all three)."""
-    _check_groups("adamw_groups", group_of, lr_scale, wd, n)
-    _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_groups", p, g, m, v, p_bf16, group_of, lr_scale, wd, _L(n), _F(lr),
-              _F(b1), _F(b2), _F(eps), _I(step), _F(grad_scale))
+    _adamw(p, g, m, v, p_bf16, n, b1, b2, eps, groups=(group_of, lr_scale, wd), scalars=(lr, step, grad_scale))
 
 
 def adamw_groups_dev(p, g, m, v, p_bf16, group_of, lr_scale, wd, n, b1, b2, eps, hyper):
     """``adamw_groups`` with {lr, 1 - b1^t, sqrt(1 - b2^t), grad_scale, active} read from the device tensor ``hyper``."""
-    _check_groups("adamw_groups_dev", group_of, lr_scale, wd, n)
-    _hbm_call("adamw", float(n) * (16 + 12 + _esz(p_bf16)), "mh_adamw_groups_dev", p, g, m, v, p_bf16, group_of, lr_scale, wd, _L(n),
-              _F(b1), _F(b2), _F(eps), hyper)
-
-
-# ---- AdamW with bf16 moments (include/maestro_hip_moments.h)
-ADAMW_SR_TAG = 0x5352424D      # MH_ADAMW_SR_TAG: c3 of every rounding draw
-_U64 = ctypes.c_uint64
-
-
-def _check_moments(what, m16, v16, n):
-    """bf16 moments of at least ``n`` elements: a fp32 buffer handed to these entries would be read as twice as many bf16."""
-    for name, t in (("m16", m16), ("v16", v16)):
-        if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() < int(n):
-            raise HipExtensionError(f"{what}: {name} must be a dense bfloat16 tensor of at least n = {int(n)} elements")
+    _adamw(p, g, m, v, p_bf16, n, b1, b2, eps, groups=(group_of, lr_scale, wd), hyper=hyper)
 
 
 def adamw_bf16m(p, g, m16, v16, p_bf16, n, elem_base, seed, lr, b1, b2, eps, wd, step, grad_scale=1.0):
     """``adamw`` with both moments held as bf16: upcast exactly, updated in fp32 (``p`` moves by the unrounded moments), stored by
     stochastic rounding with the words of ``sr_bf16_reference`` at indices ``elem_base + i`` (``elem_base``: the offset of
     ``p[0]`` in the flat layout, a multiple of 4).  22 bytes per parameter instead of 30."""
-    _check_moments("adamw_bf16m", m16, v16, n)
-    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_bf16m", p, g, m16, v16, p_bf16, _L(n), _L(elem_base),
-              _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(lr), _F(b1), _F(b2), _F(eps), _F(wd), _I(step), _F(grad_scale))
+    _adamw(p, g, m16, v16, p_bf16, n, b1, b2, eps, wd=wd, scalars=(lr, step, grad_scale), draws=(elem_base, seed))
 
 
 def adamw_bf16m_dev(p, g, m16, v16, p_bf16, n, elem_base, seed, b1, b2, eps, wd, hyper, step_dev):
     """``adamw_dev`` with bf16 moments; ``step_dev``: a 1-element int64 DEVICE tensor holding Adam's ``t`` (the guard's counter,
     read by the kernel after ``grad_guard_finish`` wrote it)."""
-    _check_moments("adamw_bf16m_dev", m16, v16, n)
-    if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
-        raise HipExtensionError("adamw_bf16m_dev: step_dev must be an int64 tensor")
-    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_bf16m_dev", p, g, m16, v16, p_bf16, _L(n), _L(elem_base),
-              _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(b1), _F(b2), _F(eps), _F(wd), hyper, step_dev)
+    _adamw(p, g, m16, v16, p_bf16, n, b1, b2, eps, wd=wd, hyper=hyper, draws=(elem_base, seed), step_dev=step_dev)
 
 
 def adamw_groups_bf16m(p, g, m16, v16, p_bf16, group_of, lr_scale, wd, n, elem_base, seed, lr, b1, b2, eps, step, grad_scale=1.0):
     """``adamw_groups`` with bf16 moments (``elem_base`` a multiple of 64: the map has one byte per 64 elements)."""
-    _check_groups("adamw_groups_bf16m", group_of, lr_scale, wd, n)
-    _check_moments("adamw_groups_bf16m", m16, v16, n)
-    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_groups_bf16m", p, g, m16, v16, p_bf16, group_of, lr_scale, wd,
-              _L(n), _L(elem_base), _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(lr), _F(b1), _F(b2), _F(eps), _I(step), _F(grad_scale))
+    _adamw(p, g, m16, v16, p_bf16, n, b1, b2, eps, groups=(group_of, lr_scale, wd), scalars=(lr, step, grad_scale),
+           draws=(elem_base, seed))
 
 
 def adamw_groups_bf16m_dev(p, g, m16, v16, p_bf16, group_of, lr_scale, wd, n, elem_base, seed, b1, b2, eps, hyper, step_dev):
     """``adamw_groups_dev`` with bf16 moments (``step_dev`` as in ``adamw_bf16m_dev``)."""
-    _check_groups("adamw_groups_bf16m_dev", group_of, lr_scale, wd, n)
-    _check_moments("adamw_groups_bf16m_dev", m16, v16, n)
-    if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
-        raise HipExtensionError("adamw_groups_bf16m_dev: step_dev must be an int64 tensor")
-    _hbm_call("adamw", float(n) * (12 + 8 + _esz(p_bf16)), "mh_adamw_groups_bf16m_dev", p, g, m16, v16, p_bf16, group_of, lr_scale,
-              wd, _L(n), _L(elem_base), _U64(int(seed) & 0xFFFFFFFFFFFFFFFF), _F(b1), _F(b2), _F(eps), hyper, step_dev)
+    _adamw(p, g, m16, v16, p_bf16, n, b1, b2, eps, groups=(group_of, lr_scale, wd), hyper=hyper,
+           draws=(elem_base, seed), step_dev=step_dev)
 
 
 def sr_bf16_words(index, seed, step, which):
@@ -1253,7 +1242,7 @@ def sr_bf16_round(bits_f32, r):
 
 def sr_bf16_reference(bits_f32, index, seed, step, which):
     """What ``adamw_bf16m`` stores for a new fp32 moment: ``bits_f32`` (uint32 array: the fp32 bit patterns) at flat element
-    indices ``index`` (``elem_base + i``) -> bf16 bit patterns (uint16), the contract of include/maestro_hip_moments.h restated in
+    indices ``index`` (``elem_base + i``) -> bf16 bit patterns (uint16), the contract of include/maestro_hip.h restated in
     numpy integers (runs on any machine).  ``which``: "m" or "v"."""
     return sr_bf16_round(bits_f32, sr_bf16_words(index, seed, step, which))
 

@@ -3,7 +3,7 @@
 These run once at construction or once per step on the HOST (index/RNG logic); the per-token arithmetic of the
 hot path lives in the HIP kernels.  References: ``maestro/layers/utils.py:103-125,176-198`` (tables) and
 ``maestro/ssl/mae.py:178-226`` (structural masks).  The second half restates the same draws on the counter-based generator of the
-device mode (``mask_rng="device"``, include/maestro_hip_rng.h) in numpy: the contract ``mh_mask_draw`` is tested against.
+device mode (``mask_rng="device"``, include/maestro_hip.h) in numpy: the contract ``mh_mask_draw`` is tested against.
 """
 
 from __future__ import annotations
@@ -77,7 +77,7 @@ def draw_struct_masks(groups, mods, generator=None) -> dict[str, Tensor]:
 
 
 # ---------------------------------------------------------------------------------------------------- device-side draws
-# The counter-based form of the draws above (include/maestro_hip_rng.h, csrc/mask_rng.hip): Philox4x32-10, a draw is a pure
+# The counter-based form of the draws above (include/maestro_hip.h, csrc/mask_rng.hip): Philox4x32-10, a draw is a pure
 # function of (seed, step, stream, kind, global row, attempt, i).  What follows is the numpy restatement of that contract --
 # the reference the kernel is tested against bit for bit, and what a user calls to know the masks of a step without a GPU.
 MASK_NOISE, MASK_MOD, MASK_BANDS, MASK_DATES, MASK_LOC = range(5)     # MH_MASK_KIND_*

@@ -210,7 +210,7 @@ class FusedAdamW:
 
     ``moment_dtype`` ("fp32", the default = exactly the launches above; "bf16"), ``moment_seed``: with "bf16" ``m`` / ``v`` are
     bf16 tensors (half the optimizer state, 22 instead of 30 bytes per parameter and step) and every launch of ``step`` -- plain,
-    split, guarded, grouped -- takes its ``_bf16m`` form (include/maestro_hip_moments.h) with ``elem_base`` = the slice's offset in
+    split, guarded, grouped -- takes its ``_bf16m`` form (include/maestro_hip.h) with ``elem_base`` = the slice's offset in
     the flat layout: the parameters move by the unrounded fp32 moments, which are then stored by stochastic rounding with words
     that are a function of ``(moment_seed, t, flat index)``, so a split step, a resumed run and every rank store the same bits.
     ``state_dict`` hands the moments out upcast to fp32 (exact); ``load_state_dict`` takes fp32 moments from either kind and
@@ -244,6 +244,22 @@ class FusedAdamW:
     def _refuse_moment_conflicts(self) -> None:
         refuse_moment_conflicts(self.bf16_moments, dtype="fp8" if getattr(self.engine, "fp8", None) is not None else None)
 
+    def _update(self, a: int, b: int, lr: float | None = None, grad_scale: float | None = None, *, guard=None, fp8=None) -> None:
+        """The one launch on ``[a, b)`` of the flat layout, in the form the optimizer's state selects: grouped with ``self.groups``
+        (the map offset to ``a``), bf16 moments (``elem_base = a``), the scalars ``(lr, self.t, grad_scale)`` -- or, under
+        ``guard``, its device scalars ``hyper`` and Adam's ``t`` from its device counter, written by its finish launch --, and with
+        ``fp8`` (the engine's fp8 plan, when it fuses) ``mh_adamw_fp8``, which refreshes the e4m3 shadows as well."""
+        st, gr, lo = self.engine.store, self.groups, self.lo
+        ops = (st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b])
+        if fp8 is not None:
+            return hip.adamw_fp8(*ops, fp8.w8_flat[a:b], fp8.slot_map[a // 64:], fp8.wsc.scale, fp8.wsc.amax, b - a, lr, self.betas[0],
+                                 self.betas[1], self.eps, self.wd, self.t, grad_scale)
+        hip._adamw(*ops, b - a, self.betas[0], self.betas[1], self.eps,
+                   wd=self.wd if gr is None else None, groups=None if gr is None else (gr.map_at(a), gr.lr_scale, gr.wd),
+                   scalars=(lr, self.t, grad_scale) if guard is None else None, hyper=None if guard is None else guard.hyper,
+                   draws=(a, self.moment_seed) if self.bf16_moments else None,
+                   step_dev=guard.t_dev if guard is not None and self.bf16_moments else None)
+
     def _step_guarded(self, guard, lr: float, grad_scale: float, between) -> None:
         st, lo, hi = self.engine.store, self.lo, self.hi
         if getattr(self.engine, "fp8", None) is not None:
@@ -255,22 +271,7 @@ class FusedAdamW:
         if between is not None:
             between()
         guard.launch(st.grad[lo:hi], lr, self.betas[0], self.betas[1], grad_scale)
-        gr = self.groups
-        if self.bf16_moments:          # Adam's t of this step: the guard's device counter, written by the finish launch above
-            t_dev = guard.t_dev
-            if gr is not None:
-                hip.adamw_groups_bf16m_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], gr.map_at(lo), gr.lr_scale,
-                                           gr.wd, hi - lo, lo, self.moment_seed, self.betas[0], self.betas[1], self.eps, guard.hyper,
-                                           t_dev)
-            else:
-                hip.adamw_bf16m_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], hi - lo, lo, self.moment_seed,
-                                    self.betas[0], self.betas[1], self.eps, self.wd, guard.hyper, t_dev)
-        elif gr is not None:
-            hip.adamw_groups_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], gr.map_at(lo), gr.lr_scale, gr.wd,
-                                 hi - lo, self.betas[0], self.betas[1], self.eps, guard.hyper)
-        else:
-            hip.adamw_dev(st.flat[lo:hi], st.grad[lo:hi], self.m, self.v, st.half[lo:hi], hi - lo, self.betas[0], self.betas[1],
-                          self.eps, self.wd, guard.hyper)
+        self._update(lo, hi, guard=guard)
         st.mark_synced()
         self.engine._pack_conv_weights()
 
@@ -285,8 +286,7 @@ class FusedAdamW:
         packed weights that are rebuilt afterwards are rebuilt from unchanged masters.  ``ValueError`` with an fp8 plan."""
         import os
         import torch
-        gr = self.groups
-        refuse_group_conflicts(gr is not None, dtype="fp8" if getattr(self.engine, "fp8", None) is not None else None)
+        refuse_group_conflicts(self.groups is not None, dtype="fp8" if getattr(self.engine, "fp8", None) is not None else None)
         self._refuse_moment_conflicts()
         roctx = os.environ.get("MAESTRO_ROCTX", "0") == "1"
         if roctx:
@@ -308,24 +308,9 @@ class FusedAdamW:
         for a, b in ((split, hi), (lo, split)):
             if a == lo and between is not None:
                 between()
-            if b > a and fused8 and a % 64 == 0:
-                hip.adamw_fp8(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b],
-                              plan.w8_flat[a:b], plan.slot_map[a // 64:], plan.wsc.scale, plan.wsc.amax, b - a, lr, self.betas[0],
-                              self.betas[1], self.eps, self.wd, self.t, grad_scale)
-            elif b > a and self.bf16_moments and gr is not None:
-                hip.adamw_groups_bf16m(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b],
-                                       gr.map_at(a), gr.lr_scale, gr.wd, b - a, a, self.moment_seed, lr, self.betas[0], self.betas[1],
-                                       self.eps, self.t, grad_scale)
-            elif b > a and self.bf16_moments:
-                hip.adamw_bf16m(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], b - a, a,
-                                self.moment_seed, lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t, grad_scale)
-            elif b > a and gr is not None:
-                hip.adamw_groups(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], gr.map_at(a),
-                                 gr.lr_scale, gr.wd, b - a, lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale)
-            elif b > a:
-                fused8 = False
-                hip.adamw(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], b - a, lr,
-                          self.betas[0], self.betas[1], self.eps, self.wd, self.t, grad_scale)
+            if b > a:
+                fused8 = fused8 and a % 64 == 0        # one plain launch: the e4m3 shadows are then cast from the masters afterwards
+                self._update(a, b, lr, grad_scale, fp8=plan if fused8 else None)
         st.mark_synced()               # bf16 shadows were refreshed by the kernel itself
         if plan is not None:
             self.engine._pack_conv_weights(fp8_done=fused8)  # K-padded patch-embed weights (+ e4m3 shadows unless fused above)
@@ -357,8 +342,7 @@ class FusedAdamW:
         for _, _, a, b in owned:
             a, b = max(a, lo), min(b, hi)
             if b > a:
-                hip.adamw(st.flat[a:b], st.grad[a:b], self.m[a - lo: b - lo], self.v[a - lo: b - lo], st.half[a:b], b - a, lr,
-                          self.betas[0], self.betas[1], self.eps, self.wd, self.t, grad_scale)
+                self._update(a, b, lr, grad_scale)
         for a, b in sync.gather_params(st.flat):
             a, b = max(a, lo), min(b, hi)
             if b > a:

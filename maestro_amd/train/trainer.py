@@ -65,12 +65,12 @@ class PretrainLoop(_GuardSurface):
                  moment_seed: int = 0) -> None:
         """``moment_dtype`` ("fp32" / "bf16"; None reads ``MAESTRO_MOMENT_DTYPE``, unset, empty or "fp32" = off), ``moment_seed``:
         AdamW's moments held as bf16 with stochastic rounding inside the fused launch (``FusedAdamW``,
-        include/maestro_hip_moments.h): half the optimizer state, 22 instead of 30 bytes per parameter and step.  Off by default:
+        include/maestro_hip.h): half the optimizer state, 22 instead of 30 bytes per parameter and step.  Off by default:
         the step is then launch for launch the fp32-moment one.  Excludes ``dtype="fp8"``, ``exchange_mode="rs_ag"`` and
         ``overlap_optimizer``; allowed in deterministic mode, with the gradient guard and with the all-reduce exchange (every rank
         draws the same rounding words, so the parameters stay identical across ranks).
         ``max_grad_norm`` / ``skip_nonfinite`` (None reads ``MAESTRO_MAX_GRAD_NORM`` / ``MAESTRO_SKIP_NONFINITE``, "1" = on): the
-        gradient guard (``hip.GradGuard``, include/maestro_hip_guard.h) -- the global L2 norm of the reduced gradient is taken on
+        gradient guard (``hip.GradGuard``, include/maestro_hip.h) -- the global L2 norm of the reduced gradient is taken on
         the device, the clipping coefficient ``min(1, max_grad_norm / (norm + 1e-6))`` rides in AdamW's gradient scale, and with
         ``skip_nonfinite`` a step whose gradient holds an inf / NaN (or whose norm overflows) leaves weights, moments and Adam's
         step count untouched (what Lightning's ``GradScaler`` does under the reference's ``precision="16-mixed"``); the OneCycle

@@ -1,4 +1,4 @@
-"""Cost of AdamW parameter groups (include/maestro_hip_optim.h): ``mh_adamw_groups`` beside ``mh_adamw`` over one buffer.
+"""Cost of AdamW parameter groups (include/maestro_hip.h): ``mh_adamw_groups`` beside ``mh_adamw`` over one buffer.
 
     python scripts/bench_adamw_groups.py [--n 176200000] [--groups 1 14 52] [--rounds 20] [--warmup 5] [--out FILE.md]
 

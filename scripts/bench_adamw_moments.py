@@ -1,4 +1,4 @@
-"""Cost of AdamW with bf16 moments (include/maestro_hip_moments.h): ``mh_adamw_bf16m`` beside ``mh_adamw``, and the guarded
+"""Cost of AdamW with bf16 moments (include/maestro_hip.h): ``mh_adamw_bf16m`` beside ``mh_adamw``, and the guarded
 (device-scalar) and grouped pairs, over one buffer.
 
     python scripts/bench_adamw_moments.py [--n 176200000 898300000] [--rounds 20] [--warmup 5] [--out FILE.md]

@@ -1,4 +1,4 @@
-"""Cost of the gradient guard (include/maestro_hip_guard.h): the streaming kernel alone, and the training step with it.
+"""Cost of the gradient guard (include/maestro_hip.h): the streaming kernel alone, and the training step with it.
 
     python scripts/bench_grad_guard.py [--config c3] [--batch 32] [--variant NAME=LIB.so ...] [--out FILE.md]
 

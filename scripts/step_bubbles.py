@@ -5,9 +5,9 @@ kernels on either side."""
 import csv, sys, collections
 rows = []
 for r in csv.DictReader(open(sys.argv[1])):
-    rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0][:60], r.get("Queue_Id", "")))
+    rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].replace("(anonymous namespace)::", "").removeprefix("void ").split("(")[0][:60], r.get("Queue_Id", "")))
 rows.sort()
-cuts = [i for i, r in enumerate(rows) if r[2].startswith("adamw_kernel")]
+cuts = [i for i, r in enumerate(rows) if r[2].startswith("adamw_kernel")]   # adamw_kernel<MT, GROUPED, DEV>: every form but the fp8 one
 print(f"{len(rows)} dispatches, {len(cuts)} AdamW launches")
 skip = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 for si in range(skip, len(cuts) - 1):

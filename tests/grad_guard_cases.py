@@ -1,7 +1,7 @@
 """Shared by tests/test_grad_guard_host.py and tests/test_grad_guard_gpu.py (a plain helper module): the sizes, the inputs, the
 fp32 emulation of the addition tree of ``mh_grad_sumsq_partial`` and the error bound derived from that tree.
 
-THE TREE (include/maestro_hip_guard.h).  A chunk is C = MH_GUARD_CHUNK = 16384 elements for one workgroup of 256 lanes; lane l
+THE TREE (include/maestro_hip.h).  A chunk is C = MH_GUARD_CHUNK = 16384 elements for one workgroup of 256 lanes; lane l
 holds four accumulators acc[c], c = 0 ... 3, and for k = 0 ... 15 in order does acc[c] = fma(g, g, acc[c]) with g = element
 4 * (256 * k + l) + c of the chunk (elements past n count as +0).  Then (acc[0] + acc[1]) + (acc[2] + acc[3]); then six
 butterfly steps over the 64 lanes of a wave (v += v[lane ^ o], o = 32, 16, ... 1); then ((w0 + w1) + w2) + w3 over the four waves.

@@ -213,7 +213,8 @@ def bits_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
 # test_guard_bands_gpu.py, or the guard section -- the text below the "guard bands (tests/guards.py)" banner -- of the other
 # files listed here) and EXEMPT; tests/test_abi.py enforces it, so a new entry point cannot arrive without a decision.
 GUARD_TEST_FILES = ("test_guard_bands_gpu.py", "test_fp8_gpu.py", "test_mx_gpu.py", "test_det_kernels_gpu.py",
-                    "test_step_ends_gpu.py", "test_metrics_gpu.py", "test_date_select_gpu.py")
+                    "test_step_ends_gpu.py", "test_metrics_gpu.py", "test_date_select_gpu.py", "test_mask_rng_gpu.py",
+                    "test_grad_guard_gpu.py", "test_adamw_groups_gpu.py", "test_adamw_moments_gpu.py")
 
 # name -> how a guard test reaches it when not by its own name or the hip.py wrapper of the same name (hip.<name without mh_>)
 VIA = {
@@ -225,6 +226,7 @@ VIA = {
     "mh_quant_mx_batched": "hip.QuantMxBatch(",
     "mh_transpose_u8_batched": "hip.TransposeBatch(",
     "mh_reduce_ordered": "hip.OrderedReduce(",
+    "mh_mask_draw": "hip.MaskDraw(",
 }
 
 GUARDED = {
@@ -242,6 +244,8 @@ GUARDED = {
     "mh_adamw", "mh_adamw_dev", "mh_scale_dev", "mh_zero_spans",
     "mh_gemm_fp8", "mh_gemm_mx", "mh_quant_batched", "mh_quant_mx_batched", "mh_transpose_u8_batched", "mh_fp8_update_scales",
     "mh_adamw_fp8",
+    "mh_adamw_groups", "mh_adamw_groups_dev", "mh_adamw_bf16m", "mh_adamw_bf16m_dev", "mh_adamw_groups_bf16m", "mh_adamw_groups_bf16m_dev",
+    "mh_mask_draw", "mh_grad_sumsq_partial", "mh_grad_guard_finish",
     "mh_reduce_ordered", "mh_colsum_partial", "mh_masked_loss_det", "mh_masked_loss_bands_det", "mh_unmask_token_grad_det",
     "mh_unmask_token_grad_per_sample_det", "mh_embed_finish_bwd_det",
     "mh_masked_loss_cs", "mh_masked_loss_bands_cs", "mh_gather_rows_bf16_cs", "mh_embed_finish_bwd_ends",
@@ -266,5 +270,6 @@ EXEMPT = {
     "mh_masked_loss_cs_rows": NO_DEVICE_BUFFER,
     "mh_gather_rows_cs_rows": NO_DEVICE_BUFFER,
     "mh_embed_bwd_cs_rows": NO_DEVICE_BUFFER,
+    "mh_grad_sumsq_partial_rows": NO_DEVICE_BUFFER,
 }
 MAX_OTHER_EXEMPT = 6

@@ -13,7 +13,7 @@ tests/test_numerics_gpu.py (the HIP kernels against the same bounds).  Nothing h
   reduction in wave order, ``wave_two_pass_stats``) against fp64 on the very inputs of the case.
 * Attention (``attn_bounds``): a first-order propagation of every rounding of csrc/attn.hip through softmax and its gradient; the
   derivation stands in front of the function, the measured slack in profiles/attn_numerics.md.
-* AdamW (``adamw_bounds``): a first-order propagation of the roundings of ``adamw_update`` (csrc/loss.hip) through the moments, the
+* AdamW (``adamw_bounds``): a first-order propagation of the roundings of ``adamw_update`` (csrc/optim.hip) through the moments, the
   square root and the quotient; used by tests/test_adamw_numerics_gpu.py, checked on the CPU by tests/test_step_end_selfcheck.py,
   measured in profiles/step_end_numerics.md.
 """
@@ -516,7 +516,7 @@ def attn_criterion_b(got, emulated, want64, bound):
 
 
 # ------------------------------------------------------------------------------------------------ AdamW
-# One step of csrc/loss.hip's adamw_update on fp32 p, g, m, v with fp32 scalars (the ABI takes floats):
+# One step of csrc/optim.hip's adamw_update on fp32 p, g, m, v with fp32 scalars (the ABI takes floats):
 #   g' = g gs;  p1 = p (1 - lr wd);  m' = b1 m + (1 - b1) g';  v' = b2 v + (1 - b2) g'^2
 #   denom = sqrt(v') / bc2_sqrt + eps;  step = (lr / bc1) (m' / denom);  p' = p1 - step
 # Error model (u = 2^-24, FL = 2^-126; correctly rounded / and sqrtf: hipcc's default, build.py passes no fast-math flag):
@@ -594,7 +594,7 @@ def adamw_bounds(ref):
 
 
 def adamw_emulated(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, fma: bool = False, form: str = "honest"):
-    """fp32 torch written as ``adamw_update`` (csrc/loss.hip) is; returns ``(p, m, v)``.  ``fma``: the moments and the final
+    """fp32 torch written as ``adamw_update`` (csrc/optim.hip) is; returns ``(p, m, v)``.  ``fma``: the moments and the final
     subtraction as the compiler may contract them (one rounding for a product and its sum).  ``form``: "honest", or one of
     ADAMW_WRONG -- eps inside the division by bc2_sqrt, eps inside the square root, a missing bc1 or bc2, weight decay applied
     after the step, weight decay on the gradient (L2)."""

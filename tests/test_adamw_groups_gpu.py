@@ -1,4 +1,4 @@
-"""``mh_adamw_groups`` / ``mh_adamw_groups_dev`` (include/maestro_hip_optim.h) and the two surfaces built on them.
+"""``mh_adamw_groups`` / ``mh_adamw_groups_dev`` (include/maestro_hip.h) and the two surfaces built on them.
 
 The main check is bit identity: one grouped launch equals one ``mh_adamw`` launch per span with that span's
 ``lr_g = float32(lr) * float32(scale)`` (one fp32 product, numpy's) and weight decay -- on a buffer whose group boundaries fall
@@ -197,38 +197,6 @@ def test_a_slice_with_the_map_offset_is_the_whole_launch_on_that_range(dev):
         assert guards.bits_equal(t, w)
 
 
-@pytest.mark.parametrize("entry", ["adamw_groups", "adamw_groups_dev"])
-def test_guard_bands_around_every_operand_the_map_and_both_tables(dev, entry):
-    from maestro_amd import hip
-    h = nm.ADAMW_HYPER
-    host = nm.adamw_inputs("unit", N)
-    gs = guards.GuardSet(dev)
-    p, m, v = (gs.out((N,), name=k) for k in "pmv")
-    pb = gs.out((N,), torch.bfloat16, align=8, name="p_bf16")
-    g = gs.inp(host[1], name="g")
-    gmap = gs.inp(_map(dev).cpu(), fill="e8m0", align=1, name="group map")           # bands of 0xFF, an odd base address
-    ls_h, wd_h = (t.cpu() for t in _tables(dev))
-    ls, wd = gs.inp(ls_h, name="lr_scale"), gs.inp(wd_h, name="wd")
-    assert ls.numel() == 256 and wd.numel() == 256 and gmap.numel() == 68 and gmap.data_ptr() % 2 == 1
-    p.copy_(host[0])
-    m.copy_(host[2])
-    v.copy_(host[3])
-    gs.arm()
-    if entry == "adamw_groups":
-        hip.adamw_groups(p, g, m, v, pb, gmap, ls, wd, N, h["lr"], h["b1"], 0.999, h["eps"], 3, h["grad_scale"])
-    else:
-        bc1, bc2_sqrt = hip.adamw_bias_corrections(h["b1"], 0.999, 3)
-        hyper = gs.inp(torch.tensor([h["lr"], bc1, bc2_sqrt, h["grad_scale"], 1.0]), name="hyper")
-        hip.adamw_groups_dev(p, g, m, v, pb, gmap, ls, wd, N, h["b1"], 0.999, h["eps"], hyper)
-    gs.check()
-    q, g2, m2, v2, qb = _fresh(dev, *host)
-    for lo, hi, lr_g, wd_g in _spans():
-        hip.adamw(q[lo:hi], g2[lo:hi], m2[lo:hi], v2[lo:hi], qb[lo:hi], hi - lo, lr_g, h["b1"], 0.999, h["eps"], wd_g, 3, h["grad_scale"])
-    torch.cuda.synchronize()
-    for name, a, b in zip(("p", "m", "v", "p_bf16"), (p, m, v, pb), (q, m2, v2, qb)):
-        assert guards.bits_equal(a, b), name
-
-
 # ------------------------------------------------------------------------------------------------ the built-in loop
 def _finetune_setup(dev, **loop_kw):
     import maestro_amd.conf as conf
@@ -375,3 +343,36 @@ def test_lightning_surface_binds_the_grouped_path_and_leaves_it_when_the_ratio_b
              for k, p in enumerate(st.params)]
     assert all(mv for mv, hg in zip(moved, has_grad) if hg) and sum(has_grad) >= 0.9 * len(has_grad)
     assert bool(torch.isfinite(st.flat.detach()).all())
+
+
+# ------------------------------------------------------------------------------------------------ guard bands (tests/guards.py)
+@pytest.mark.parametrize("entry", ["adamw_groups", "adamw_groups_dev"])
+def test_guard_bands_around_every_operand_the_map_and_both_tables(dev, entry):
+    from maestro_amd import hip
+    h = nm.ADAMW_HYPER
+    host = nm.adamw_inputs("unit", N)
+    gs = guards.GuardSet(dev)
+    p, m, v = (gs.out((N,), name=k) for k in "pmv")
+    pb = gs.out((N,), torch.bfloat16, align=8, name="p_bf16")
+    g = gs.inp(host[1], name="g")
+    gmap = gs.inp(_map(dev).cpu(), fill="e8m0", align=1, name="group map")           # bands of 0xFF, an odd base address
+    ls_h, wd_h = (t.cpu() for t in _tables(dev))
+    ls, wd = gs.inp(ls_h, name="lr_scale"), gs.inp(wd_h, name="wd")
+    assert ls.numel() == 256 and wd.numel() == 256 and gmap.numel() == 68 and gmap.data_ptr() % 2 == 1
+    p.copy_(host[0])
+    m.copy_(host[2])
+    v.copy_(host[3])
+    gs.arm()
+    if entry == "adamw_groups":
+        hip.adamw_groups(p, g, m, v, pb, gmap, ls, wd, N, h["lr"], h["b1"], 0.999, h["eps"], 3, h["grad_scale"])
+    else:
+        bc1, bc2_sqrt = hip.adamw_bias_corrections(h["b1"], 0.999, 3)
+        hyper = gs.inp(torch.tensor([h["lr"], bc1, bc2_sqrt, h["grad_scale"], 1.0]), name="hyper")
+        hip.adamw_groups_dev(p, g, m, v, pb, gmap, ls, wd, N, h["b1"], 0.999, h["eps"], hyper)
+    gs.check()
+    q, g2, m2, v2, qb = _fresh(dev, *host)
+    for lo, hi, lr_g, wd_g in _spans():
+        hip.adamw(q[lo:hi], g2[lo:hi], m2[lo:hi], v2[lo:hi], qb[lo:hi], hi - lo, lr_g, h["b1"], 0.999, h["eps"], wd_g, 3, h["grad_scale"])
+    torch.cuda.synchronize()
+    for name, a, b in zip(("p", "m", "v", "p_bf16"), (p, m, v, pb), (q, m2, v2, qb)):
+        assert guards.bits_equal(a, b), name

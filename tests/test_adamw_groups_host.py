@@ -1,7 +1,7 @@
 """AdamW parameter groups, the parts that need no GPU: the layer rule (``optim.layer_scale`` / ``layer_groups``) on tiny models of
 three fusion modes, ``hip.ParamGroups`` (validation, merging, the map and the tables), the scalar schedule against torch's
 per-group ``OneCycleLR``, ``SSLModule.configure_optimizers`` with and without ``lw_decay``, the refusals of the loop and the
-optimizer, and the side header against the library."""
+optimizer, and the header against the library."""
 
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ import pytest
 import torch
 
 ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "maestro_hip_optim.h"
+HEADER = ROOT / "include" / "maestro_hip.h"
 NAMES = ["mh_adamw_groups", "mh_adamw_groups_dev"]
 R = 0.75
 
@@ -390,22 +390,22 @@ def lib():
     return handle
 
 
-def test_library_exports_what_the_side_header_declares(lib):
+def test_library_exports_what_the_header_declares(lib):
     import inspect
 
     from maestro_amd import hip
     from maestro_amd.csrc import build as B
     text = HEADER.read_text()
-    assert sorted(set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", text))) == NAMES
+    assert sorted(p.name for p in (ROOT / "include").iterdir()) == ["maestro_hip.h"]
+    assert not [n for n in NAMES if not re.search(rf"^int {n}\(", text, re.M)]
     assert not [n for n in NAMES if not hasattr(lib, n)]
-    main = (ROOT / "include" / "maestro_hip.h").read_text()
-    assert not [n for n in NAMES if re.search(rf"\b{n}\b", main)]
     for cite in ("maestro/conf/opt.py:51", "maestro/train/trainer.py:43-52", "maestro/train/baseline.py:110-131",
                  "maestro/baselines/dinov2.py:312-373"):
         assert cite in text, cite
     assert f"#define MH_ADAMW_GROUP_BLOCK {hip.GROUP_BLOCK}" in text and f"#define MH_ADAMW_GROUP_TABLE {hip.GROUP_TABLE}" in text
-    assert '"maestro_hip_optim.h"' in inspect.getsource(B._digest)
-    assert '#include "../../include/maestro_hip_optim.h"' in (B.CSRC / "loss.hip").read_text()
+    assert '"maestro_hip.h"' in inspect.getsource(B._digest) and inspect.getsource(B._digest).count("maestro_hip") == 1
+    optim = (B.CSRC / "optim.hip").read_text()
+    assert '#include "../../include/maestro_hip.h"' in optim and not [n for n in NAMES if f'extern "C" int {n}(' not in optim]
 
 
 def test_bad_arguments_are_refused_before_the_gpu_is_touched(lib):

@@ -1,4 +1,4 @@
-"""AdamW with bf16 moments on the GPU (include/maestro_hip_moments.h): ``mh_adamw_bf16m`` and its device-scalar and grouped forms
+"""AdamW with bf16 moments on the GPU (include/maestro_hip.h): ``mh_adamw_bf16m`` and its device-scalar and grouped forms
 against the fp32-moment kernels and the integer restatement of the rounding (``hip.sr_bf16_reference``), bit for bit; slices of
 the flat layout; poisoned guard bands; ``FusedAdamW(moment_dtype="bf16")`` and the loops on a tiny model (launch ledger, state
 dict, resume, a skipped step); and the drift against fp32 moments over 20 steps.
@@ -166,35 +166,6 @@ def test_elem_base_indexes_the_reference(dev):
     assert (_u16(c["got"][1]) == want_m).all() and (_u16(c["got"][2]) == want_v).all()
     other_m, _ = _expect_moments(c["ref"], n, step, 0)
     assert (other_m != want_m).any()
-
-
-# ------------------------------------------------------------------------------------------------ guard bands (tests/guards.py)
-@pytest.mark.parametrize("shadow", [True, False])
-def test_nothing_outside_the_first_n_elements_changes(dev, shadow):
-    """p, m16, v16 and p_bf16 in the middle of NaN-poisoned allocations (bf16 views 8-byte and not 16-byte aligned), g read-only;
-    the views are 64 elements longer than ``n``: the bands and every element at or beyond ``n`` keep their bits."""
-    from maestro_amd import hip
-    n, extra, step = 1028, 64, 7
-    host = _inputs(n)
-    gs = guards.GuardSet(dev)
-    p = gs.out((n + extra,), name="p")
-    m16, v16 = (gs.out((n + extra,), torch.bfloat16, align=8, name=k) for k in ("m16", "v16"))
-    pb = gs.out((n + extra,), torch.bfloat16, align=8, name="p_bf16") if shadow else None
-    g = gs.inp(torch.cat([host[1], torch.full((extra,), float("nan"))]), name="g")
-    assert m16.data_ptr() % 16 == 8 and v16.data_ptr() % 16 == 8 and p.data_ptr() % 32 == 16
-    p[:n].copy_(host[0])
-    m16[:n].copy_(host[2])
-    v16[:n].copy_(host[3])
-    gs.arm()
-    tails = [t[n:].clone() for t in (p, m16, v16)] + ([pb[n:].clone()] if shadow else [])
-    hip.adamw_bf16m(p, g, m16, v16, pb, n, 0, SEED, H["lr"], H["b1"], H["b2"], H["eps"], H["wd"], step, H["grad_scale"])
-    gs.check()
-    for name, t, w in zip(("p", "m16", "v16", "p_bf16"), [p, m16, v16] + ([pb] if shadow else []), tails):
-        assert guards.bits_equal(t[n:], w), f"{name}: an element at or beyond n changed"
-    want = _pair(dev, n, step)["got"]
-    for name, t, w in zip(("p", "m16", "v16", "p_bf16"), [p, m16, v16] + ([pb] if shadow else []), want):
-        assert guards.bits_equal(t[:n], w), name
-    assert bool(torch.isfinite(p[:n]).all()) and bool(torch.isfinite(m16[:n].float()).all())
 
 
 # ------------------------------------------------------------------------------------------------ the device form
@@ -529,3 +500,51 @@ def test_drift_of_a_twenty_step_loop(dev, observed):
     assert DRIFT_LOSS is not None and DRIFT_PARAMS is not None, "the measured drift has not been recorded"
     assert rel_loss <= 2.0 * DRIFT_LOSS, rel_loss
     assert 0.0 < rel_p <= 2.0 * DRIFT_PARAMS, rel_p
+
+# ------------------------------------------------------------------------------------------------ guard bands (tests/guards.py)
+@pytest.mark.parametrize("shadow", [True, False])
+def test_nothing_outside_the_first_n_elements_changes(dev, shadow):
+    """All four forms.  p, m16, v16 and p_bf16 in the middle of NaN-poisoned allocations (bf16 views 8-byte and not 16-byte
+    aligned), g, the device scalars, the group map and both tables read-only; the views are 64 elements longer than ``n``: the
+    bands and every element at or beyond ``n`` keep their bits.  The grouped forms run ONE group (id 5, scale 1, the plain weight
+    decay; every other table entry 0, the map between bands of 0xFF), so each form must give the plain launch's bits: a map byte
+    or a table entry read outside its view is another group's rate."""
+    from maestro_amd import hip
+    n, extra, step = 1028, 64, 7
+    host = _inputs(n)
+    want = _pair(dev, n, step)["got"]
+    for entry in ("adamw_bf16m", "adamw_bf16m_dev", "adamw_groups_bf16m", "adamw_groups_bf16m_dev"):
+        gs = guards.GuardSet(dev)
+        p = gs.out((n + extra,), name="p")
+        m16, v16 = (gs.out((n + extra,), torch.bfloat16, align=8, name=k) for k in ("m16", "v16"))
+        pb = gs.out((n + extra,), torch.bfloat16, align=8, name="p_bf16") if shadow else None
+        g = gs.inp(torch.cat([host[1], torch.full((extra,), float("nan"))]), name="g")
+        assert m16.data_ptr() % 16 == 8 and v16.data_ptr() % 16 == 8 and p.data_ptr() % 32 == 16
+        if "groups" in entry:
+            tables = torch.zeros(2, 256)
+            tables[0, 5], tables[1, 5] = 1.0, H["wd"]
+            gmap = gs.inp(torch.full(((n + 63) // 64,), 5, dtype=torch.uint8), fill="e8m0", align=1, name="group map")
+            ls, wd = gs.inp(tables[0], name="lr_scale"), gs.inp(tables[1], name="wd")
+            assert gmap.numel() == 17 and gmap.data_ptr() % 2 == 1
+        if entry.endswith("_dev"):
+            hyper = gs.inp(_hyper(dev, step).cpu(), name="hyper")
+            t_dev = gs.inp(torch.tensor([step], dtype=torch.int64), align=8, name="step_dev")
+        p[:n].copy_(host[0])
+        m16[:n].copy_(host[2])
+        v16[:n].copy_(host[3])
+        gs.arm()
+        tails = [t[n:].clone() for t in (p, m16, v16)] + ([pb[n:].clone()] if shadow else [])
+        if entry == "adamw_bf16m":
+            hip.adamw_bf16m(p, g, m16, v16, pb, n, 0, SEED, H["lr"], H["b1"], H["b2"], H["eps"], H["wd"], step, H["grad_scale"])
+        elif entry == "adamw_bf16m_dev":
+            hip.adamw_bf16m_dev(p, g, m16, v16, pb, n, 0, SEED, H["b1"], H["b2"], H["eps"], H["wd"], hyper, t_dev)
+        elif entry == "adamw_groups_bf16m":
+            hip.adamw_groups_bf16m(p, g, m16, v16, pb, gmap, ls, wd, n, 0, SEED, H["lr"], H["b1"], H["b2"], H["eps"], step, H["grad_scale"])
+        else:
+            hip.adamw_groups_bf16m_dev(p, g, m16, v16, pb, gmap, ls, wd, n, 0, SEED, H["b1"], H["b2"], H["eps"], hyper, t_dev)
+        gs.check()
+        for name, t, w in zip(("p", "m16", "v16", "p_bf16"), [p, m16, v16] + ([pb] if shadow else []), tails):
+            assert guards.bits_equal(t[n:], w), f"{entry} {name}: an element at or beyond n changed"
+        for name, t, w in zip(("p", "m16", "v16", "p_bf16"), [p, m16, v16] + ([pb] if shadow else []), want):
+            assert guards.bits_equal(t[:n], w), (entry, name)
+        assert bool(torch.isfinite(p[:n]).all()) and bool(torch.isfinite(m16[:n].float()).all())

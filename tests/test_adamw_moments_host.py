@@ -1,4 +1,4 @@
-"""AdamW with bf16 moments, the parts that need no GPU: the side header against the library and its bad-argument refusals, the
+"""AdamW with bf16 moments, the parts that need no GPU: the header against the library and its bad-argument refusals, the
 stochastic rounding restated on integers (``hip.sr_bf16_round``), the counter layout of its random words
 (``hip.sr_bf16_words``), the unbiasedness of the reference, and the surface (``MAESTRO_MOMENT_DTYPE``, the refusals of the
 loops and of the optimizer)."""
@@ -15,7 +15,7 @@ import pytest
 import torch
 
 ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "maestro_hip_moments.h"
+HEADER = ROOT / "include" / "maestro_hip.h"
 NAMES = ["mh_adamw_bf16m", "mh_adamw_bf16m_dev", "mh_adamw_groups_bf16m", "mh_adamw_groups_bf16m_dev"]
 
 
@@ -30,19 +30,23 @@ def lib():
     return handle
 
 
-def test_library_exports_what_the_side_header_declares(lib):
+def test_library_exports_what_the_header_declares(lib):
     import inspect
 
     from maestro_amd import hip
     from maestro_amd.csrc import build as B
     text = HEADER.read_text()
-    assert sorted(set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", text))) == NAMES
+    assert sorted(p.name for p in (ROOT / "include").iterdir()) == ["maestro_hip.h"]
+    assert not [n for n in NAMES if not re.search(rf"^int {n}\(", text, re.M)]
     assert not [n for n in NAMES if not hasattr(lib, n)]
-    main = (ROOT / "include" / "maestro_hip.h").read_text()
-    assert not [n for n in NAMES if re.search(rf"\b{n}\b", main)]
+    for layout in ("c0 = (elem_base + i) / 4 (low 32 bits),   c1 = step (low 32 bits),   c2 = 0,   c3 = MH_ADAMW_SR_TAG",
+                   "m:  (w[e >> 1] >> 16 * (e & 1)) & 0xffff        v:  (w[2 + (e >> 1)] >> 16 * (e & 1)) & 0xffff",
+                   "else t = u + r:  t carried into an all-ones exponent -> store u >> 16 (stays finite), else store t >> 16"):
+        assert layout in text, layout
     assert f"#define MH_ADAMW_SR_TAG 0x{hip.ADAMW_SR_TAG:08X}u" in text
-    assert '"maestro_hip_moments.h"' in inspect.getsource(B._digest)
-    assert '#include "../../include/maestro_hip_moments.h"' in (B.CSRC / "loss.hip").read_text()
+    assert '"maestro_hip.h"' in inspect.getsource(B._digest) and inspect.getsource(B._digest).count("maestro_hip") == 1
+    optim = (B.CSRC / "optim.hip").read_text()
+    assert '#include "../../include/maestro_hip.h"' in optim and not [n for n in NAMES if f'extern "C" int {n}(' not in optim]
 
 
 def test_bad_arguments_are_refused_before_the_gpu_is_touched(lib):
@@ -182,11 +186,11 @@ def test_words_differ_between_steps_seeds_and_moments():
 
 def test_no_counter_collides_with_a_mask_draw_counter():
     """Counters are (c0, c1, c2, c3) under the key of the seed.  The mask draws put ``kind | stream << 4 | attempt << 16`` into c3
-    (``layers.utils.mask_uniform``, include/maestro_hip_rng.h): kind <= 4 in four bits, stream < 4096, attempt < 64, so c3 < 2^22.
+    (``layers.utils.mask_uniform``, include/maestro_hip.h): kind <= 4 in four bits, stream < 4096, attempt < 64, so c3 < 2^22.
     The rounding draws put the tag there."""
     from maestro_amd import hip
     from maestro_amd.layers import utils
-    rng_h = (ROOT / "include" / "maestro_hip_rng.h").read_text()
+    rng_h = HEADER.read_text()
     streams = int(re.search(r"#define MH_MASK_MAX_STREAMS (\d+)", rng_h).group(1))
     attempts = int(re.search(r"#define MH_MASK_MAX_ATTEMPTS (\d+)", rng_h).group(1))
     kinds = [utils.MASK_NOISE, utils.MASK_MOD, utils.MASK_BANDS, utils.MASK_DATES, utils.MASK_LOC]

@@ -1,5 +1,5 @@
 """``mh_adamw`` / ``mh_adamw_dev`` against fp64 under the elementwise bounds of tests/numerics.py (``adamw_bounds``: derived
-from the roundings of ``adamw_update``, csrc/loss.hip; accepted and rejected forms in tests/test_step_end_selfcheck.py).
+from the roundings of ``adamw_update``, csrc/optim.hip; accepted and rejected forms in tests/test_step_end_selfcheck.py).
 
 Single steps from given ``(p, g, m, v)``: eight kinds of operands (eps visible, cancelling and underflowing moments, large and
 zero parameters) crossed with early and late steps at a ``grad_scale`` that is no power of two; ``p``, ``m`` and ``v`` are all

@@ -1,4 +1,4 @@
-"""Gradient guard, the parts that need no GPU: the side header against the library and the binding, the argument checks of the
+"""Gradient guard, the parts that need no GPU: the header against the library and the binding, the argument checks of the
 three entry points, the switches and refusals of the loops, the numpy restatement of the contract (``hip.grad_guard_reference``)
 against ``torch.nn.utils.clip_grad_norm_``, and the teeth of the error bound the GPU tests use (tests/grad_guard_cases.py)."""
 
@@ -16,7 +16,7 @@ import torch
 from tests import grad_guard_cases as G
 
 ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "maestro_hip_guard.h"
+HEADER = ROOT / "include" / "maestro_hip.h"
 NAMES = ["mh_grad_guard_finish", "mh_grad_sumsq_partial", "mh_grad_sumsq_partial_rows"]
 
 
@@ -37,7 +37,7 @@ def lib():
 
 
 def _declared():
-    return sorted(set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", HEADER.read_text())))
+    return sorted(n for n in set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", HEADER.read_text())) if n.startswith("mh_grad_"))
 
 
 def test_every_declared_symbol_is_exported(lib):
@@ -45,10 +45,10 @@ def test_every_declared_symbol_is_exported(lib):
     assert not [n for n in NAMES if not hasattr(lib, n)]
 
 
-def test_guard_names_stay_out_of_the_main_header():
-    main = (ROOT / "include" / "maestro_hip.h").read_text()
-    assert not [n for n in _declared() if re.search(rf"\b{n}\b", main)]
+def test_guard_names_are_declared_in_the_one_header():
     text = HEADER.read_text()
+    assert sorted(p.name for p in (ROOT / "include").iterdir()) == ["maestro_hip.h"]
+    assert not [n for n in NAMES if not re.search(rf"^(int|long) {n}\(", text, re.M)]
     for cite in ("maestro/conf/trainer.py:13", "maestro/train/model.py:135-140", "clip_grad_norm_"):
         assert cite in text, cite
 
@@ -67,12 +67,13 @@ def test_struct_and_chunk_match_the_header():
 
 
 def test_the_header_is_hashed_by_the_build():
-    """csrc/build.py keys every object by its source and the shared headers: the side header is one of them."""
+    """csrc/build.py keys every object by its source and the shared headers: the one C header is among them, and the source that
+    defines the entries includes it."""
     import inspect
 
     from maestro_amd.csrc import build as B
-    assert '"maestro_hip_guard.h"' in inspect.getsource(B._digest)
-    assert (B.CSRC / "grad_guard.hip").exists() and '#include "../../include/maestro_hip_guard.h"' in (B.CSRC / "grad_guard.hip").read_text()
+    assert '"maestro_hip.h"' in inspect.getsource(B._digest) and inspect.getsource(B._digest).count("maestro_hip") == 1
+    assert (B.CSRC / "grad_guard.hip").exists() and '#include "../../include/maestro_hip.h"' in (B.CSRC / "grad_guard.hip").read_text()
 
 
 def test_partial_rows_depend_on_n_alone(lib):

@@ -6,8 +6,6 @@ resumed training loop."""
 from __future__ import annotations
 
 import copy
-import re
-from pathlib import Path
 
 import pytest
 import torch
@@ -18,7 +16,6 @@ from tests import mask_rng_cases as C
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
 SEED = (0xC0FFEE << 40) | 0x1234567        # high bits set
 STEPS = (0, 1, 2 ** 32 - 1)
 ROW_BASE = 5
@@ -100,11 +97,6 @@ def test_the_bound_is_exercised():
 
 
 # ------------------------------------------------------------------------------------------------ guard bands (tests/guards.py)
-# This file's own ledger (the side header is not in the ledger of tests/guards.py yet): entry point -> how the guard test below
-# reaches it.
-GUARD_LEDGER = {"mh_mask_draw": "hip.MaskDraw("}
-
-
 @pytest.mark.parametrize("kind,L,B", [("plain", 9, 3), ("plain", 25, 3), ("two_mods", 1, 1), ("two_mods", 25, 3), ("two_mods", 64, 3),
                                       ("folded", 9, 3), ("folded", 64, 1)])
 def test_nothing_outside_the_views_changes(kind, L, B):  # noqa: N803
@@ -124,14 +116,6 @@ def test_nothing_outside_the_views_changes(kind, L, B):  # noqa: N803
     for n, s in bufs.values():
         assert torch.isfinite(n).all() and int(s.max()) <= 1
     _check_against_reference(groups, mods, B, bufs, SEED, 3, ROW_BASE, f"guarded {kind} L={L} B={B}")
-
-
-def test_guard_ledger_covers_the_side_header():
-    declared = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", (ROOT / "include" / "maestro_hip_rng.h").read_text()))
-    assert declared == set(GUARD_LEDGER)
-    section = Path(__file__).read_text().split("guard bands (tests/guards.py)", 1)[1].split("def test_guard_ledger_covers", 1)[0]
-    for name, via in GUARD_LEDGER.items():
-        assert via in section and "guards.GuardSet(" in section, name
 
 
 # ------------------------------------------------------------------------------------------------ engine

@@ -1,6 +1,6 @@
 """Device-side mask draws, the parts that need no GPU: the numpy Philox against the published Random123 vectors, the
 restatement of the draw contract (``maestro_amd.layers.utils.mask_draw_reference``: sensitivity to every argument, batch-size
-invariance, the counted rejection loop, its distribution against the host drawer, uniformity), the side header, the argument
+invariance, the counted rejection loop, its distribution against the host drawer, uniformity), the header, the argument
 checks of ``mh_mask_draw``, the switch and the refusals."""
 
 from __future__ import annotations
@@ -173,8 +173,11 @@ def lib():
     return handle
 
 
+HEADER = ROOT / "include" / "maestro_hip.h"
+
+
 def _declared():
-    return sorted(set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", (ROOT / "include" / "maestro_hip_rng.h").read_text())))
+    return sorted(n for n in set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", HEADER.read_text())) if n.startswith("mh_mask_draw"))
 
 
 def test_every_declared_symbol_is_exported(lib):
@@ -182,15 +185,23 @@ def test_every_declared_symbol_is_exported(lib):
     assert not [n for n in _declared() if not hasattr(lib, n)]
 
 
-def test_rng_names_stay_out_of_the_main_header():
-    main = (ROOT / "include" / "maestro_hip.h").read_text()
-    assert not [n for n in _declared() if re.search(rf"\b{n}\b", main)]
-    assert "maestro/ssl/mae.py:178-246" in (ROOT / "include" / "maestro_hip_rng.h").read_text()
+def test_rng_names_are_declared_in_the_one_header():
+    import inspect
+
+    from maestro_amd.csrc import build as B
+    text = HEADER.read_text()
+    assert sorted(p.name for p in (ROOT / "include").iterdir()) == ["maestro_hip.h"]
+    assert re.search(r"^int mh_mask_draw\(", text, re.M) and "maestro/ssl/mae.py:178-246" in text
+    for layout in ("c0 = i >> 2,   c1 = global row,   c2 = step,   c3 = kind | stream << 4 | attempt << 16", "0xD2511F53 / 0xCD9E8D57",
+                   "0x9E3779B9 /", "(float)(word[i & 3] >> 8) * 2^-24"):
+        assert layout in text, layout
+    assert '"maestro_hip.h"' in inspect.getsource(B._digest) and inspect.getsource(B._digest).count("maestro_hip") == 1
+    assert '#include "../../include/maestro_hip.h"' in (B.CSRC / "mask_rng.hip").read_text()
 
 
 def test_structs_match_the_header():
     from maestro_amd import hip
-    text = (ROOT / "include" / "maestro_hip_rng.h").read_text()
+    text = HEADER.read_text()
     for cls, name in ((hip._MhMaskSeg, "MhMaskSeg"), (hip._MhMaskJob, "MhMaskJob")):
         body = re.search(r"typedef struct \{([^}]*)\} " + name + ";", text).group(1)
         fields = [f.strip().lstrip("*") for decl in body.split(";") if decl.strip()
