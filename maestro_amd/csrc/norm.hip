@@ -97,19 +97,12 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // the two reductions, chunk by chunk, and each chunk's wait also covered the previous chunk's STORES -- 7-8 memory round
 // trips per row, one after the other.  Here the row, gamma and beta are requested back to back before anything is
 // waited for, and the stores leave together at the end.
-#ifndef MH_LN_FAST
-#define MH_LN_FAST 1      // -DMH_LN_FAST=0 (MH_BUILD_FLAGS) builds the library without the straight-line forms (A/B aid)
-#endif
-#ifndef MH_LN_DPP
-#define MH_LN_DPP 1
-#endif
-// Wave sum of the straight-line kernels (all 64 lanes active there).  MH_LN_DPP = 1 (default): each 16-lane row all-reduces by
-// four DPP rotations (row_ror:8, 4, 2, 1: one v_add_f32_dpp each, no LDS crossbar round trip), then the four row sums meet
-// through v_readlane.  With the loads no longer serialized the twelve ds_bpermute round trips per row show: forward -4 ... -7 %
-// per launch, backward -1 ... -9 % (profiles/r03_ln_straightline.txt); 0 keeps the shuffle butterfly of wave_sum (the sums then
-// differ from the generic kernels' in their last bits only by fma contraction; with 1 also by the order of the 64 partial sums).
+// Wave sum of the straight-line kernels (all 64 lanes active there): each 16-lane row all-reduces by four DPP rotations
+// (row_ror:8, 4, 2, 1: one v_add_f32_dpp each, no LDS crossbar round trip), then the four row sums meet through v_readlane.
+// With the loads no longer serialized the twelve ds_bpermute round trips per row of the shuffle butterfly (wave_sum) show:
+// forward -4 ... -7 % per launch, backward -1 ... -9 % (profiles/r03_ln_straightline.txt).  The sums differ from the generic
+// kernels' in their last bits by fma contraction and by the order of the 64 partial sums.
 __device__ __forceinline__ float ln_wave_sum(float v) {
-#if MH_LN_DPP
 #define MH_ROR(n) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + (n), 0xf, 0xf, false))
     v += MH_ROR(8); v += MH_ROR(4); v += MH_ROR(2); v += MH_ROR(1);
 #undef MH_ROR
@@ -117,19 +110,15 @@ __device__ __forceinline__ float ln_wave_sum(float v) {
     const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 16));
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 48));
     return (r0 + r1) + (r2 + r3);
-#else
-    return wave_sum(v);
-#endif
 }
 // Y8 = LN_Y8_TENSOR (mh_layernorm_fwd_fp8): the same kernel also writes the e4m3 copy of the output (the next GEMM's A operand)
 // and folds |y| into the tensor's amax row; Y8 = LN_Y8_MX (mh_layernorm_fwd_mx): the MX copy of the BF16 output -- a lane holds
 // 4 consecutive values per i, so 8 lanes hold one 32-element block (3 xor shuffles for its max), lane (l & 7) == 0 writes the
 // scale byte.  The bf16 output is the SAME instruction sequence in all three, hence bit-identical to Y8 = LN_Y8_NONE.  (Other
 // widths with dim %% 32 == 0 -- the small models' 384 -- take the generic ln_fwd_kernel, which writes the MX copy the same way.)
-// (One __device__ body, three kernels: ln_fwd_fast_kernel<NV, FP8> keeps its two instantiations, ln_fwd_fast_mx_kernel<NV> is the third.)
 enum { LN_Y8_NONE = 0, LN_Y8_TENSOR = 1, LN_Y8_MX = 2 };
 template <int NV, int Y8>
-__device__ __forceinline__ void ln_fwd_fast_body(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
+__global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, bf16_t* __restrict__ y, RowMap ym,
                                                           float* __restrict__ mean, float* __restrict__ rstd, int B, int n,
                                                           float eps, uint8_t* __restrict__ y8, const float* __restrict__ y8_scale,
@@ -195,31 +184,32 @@ __device__ __forceinline__ void ln_fwd_fast_body(const float* __restrict__ x, Ro
         }
     }
 }
-template <int NV, bool FP8>
-__global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, bf16_t* __restrict__ y, RowMap ym,
-                                                          float* __restrict__ mean, float* __restrict__ rstd, int B, int n,
-                                                          float eps, uint8_t* __restrict__ y8, const float* __restrict__ y8_scale,
-                                                          float* __restrict__ y8_amax) {
-    ln_fwd_fast_body<NV, FP8 ? LN_Y8_TENSOR : LN_Y8_NONE>(x, xm, gamma, beta, y, ym, mean, rstd, B, n, eps, y8, y8_scale, y8_amax,
-                                                          nullptr, 0);
-}
-template <int NV>
-__global__ __launch_bounds__(256) void ln_fwd_fast_mx_kernel(const float* __restrict__ x, RowMap xm, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, bf16_t* __restrict__ y, RowMap ym,
-                                                             float* __restrict__ mean, float* __restrict__ rstd, int B, int n,
-                                                             float eps, uint8_t* __restrict__ y8, uint8_t* __restrict__ y8s,
-                                                             int ld_y8s) {
-    ln_fwd_fast_body<NV, LN_Y8_MX>(x, xm, gamma, beta, y, ym, mean, rstd, B, n, eps, y8, nullptr, nullptr, y8s, ld_y8s);
-}
 
 // Backward. Each wave walks ROWS_PER_WAVE rows keeping per-column partials of dgamma, dbeta and colsum(dx) in
 // registers; the block reduces them through LDS and writes ONE partial row [3*dim] to the workspace (plain stores);
 // ln_bwd_reduce_kernel then sums the partial rows (few atomics per column, no same-address storm).
-#ifndef LN_ROWS
-#define LN_ROWS 4
-#endif
-constexpr int ROWS_PER_WAVE = LN_ROWS;  // 4: 16 rows per block, >= 2 blocks per CU at M = 8192 (8 was bandwidth-starved: 256 blocks)
+constexpr int ROWS_PER_WAVE = 4;  // 16 rows per block, >= 2 blocks per CU at M = 8192 (8 was bandwidth-starved: 256 blocks)
+
+// The block tail of the backward kernels: every wave parks gsum | bsum | csum in LDS ([4 waves][3][dim]), the block adds the
+// four waves and stores one partial row.  FULL: dim == 256 * NV, every lane holds all of its NV chunks (no lane predicate).
+template <int NV, bool FULL>
+__device__ __forceinline__ void ln_bwd_store_partial(float* red, float* __restrict__ partial, const f32x4 (&gsum)[NV],
+                                                     const f32x4 (&bsum)[NV], const f32x4 (&csum)[NV], int w, int lane, int dim) {
+    float* rg = red + (size_t)w * 3 * dim;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        if (FULL || c < (dim >> 2)) {
+            *reinterpret_cast<f32x4*>(rg + 4 * c) = gsum[i];
+            *reinterpret_cast<f32x4*>(rg + dim + 4 * c) = bsum[i];
+            *reinterpret_cast<f32x4*>(rg + 2 * dim + 4 * c) = csum[i];
+        }
+    }
+    __syncthreads();
+    float* prow = partial + (size_t)blockIdx.x * 3 * dim;
+    for (int c = threadIdx.x; c < 3 * dim; c += 256)
+        prow[c] = red[c] + red[3 * dim + c] + red[6 * dim + c] + red[9 * dim + c];
+}
 
 template <int NV>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy, RowMap dym, int dy_is_f32,
@@ -288,6 +278,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
                 if (dy_is_f32) {
                     d = __builtin_bit_cast(f32x4, dyv[i]);
                 } else {
+                    // (bf2x2_to_f32x4 written out: through the call the NV = 8 form takes 446 + 190 registers instead of 444 + 188)
                     d = (f32x4){__uint_as_float(dyv[i][0] << 16), __uint_as_float(dyv[i][0] & 0xffff0000u),
                                 __uint_as_float(dyv[i][1] << 16), __uint_as_float(dyv[i][1] & 0xffff0000u)};
                 }
@@ -321,39 +312,36 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
         }
     }
     if (!partial) return;
-    float* rg = red + (size_t)w * 3 * dim;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            *reinterpret_cast<f32x4*>(rg + 4 * c) = gsum[i];
-            *reinterpret_cast<f32x4*>(rg + dim + 4 * c) = bsum[i];
-            *reinterpret_cast<f32x4*>(rg + 2 * dim + 4 * c) = csum[i];
-        }
-    }
-    __syncthreads();
-    float* prow = partial + (size_t)blockIdx.x * 3 * dim;
-    for (int c = threadIdx.x; c < 3 * dim; c += 256)
-        prow[c] = red[c] + red[3 * dim + c] + red[6 * dim + c] + red[9 * dim + c];
+    ln_bwd_store_partial<NV, false>(red, partial, gsum, bsum, csum, w, lane, dim);
 }
 
-// Straight-line backward for the transformer blocks' own case: dim == 256 * NV, bf16 dy, a residual gradient to add, a bf16
-// copy of dx to write, rows % ROWS_PER_WAVE == 0 (a wave's rows exist together).  Same operations, same order, same
-// partial-row layout as ln_bwd_kernel (results equal up to fma contraction / packing: a few fp32 ulp).  Why it exists: in the generic kernel the run-time cases
+// Straight-line backward for the step's own cases: dim == 256 * NV, a bf16 copy of dx to write, rows % ROWS_PER_WAVE == 0 (a
+// wave's rows exist together).  Same operations, same order, same partial-row layout as ln_bwd_kernel (results equal up to fma
+// contraction / packing: a few fp32 ulp).  Why it exists: in the generic kernel the run-time cases
 // (dy type, dres / dx_bf16 present, lane < nv) are branches INSIDE the software pipeline; its ISA waits `vmcnt(0)` after
 // each chunk's dy load (the bf16 words are moved into the f32-sized registers of the other case) and again at the loop
 // head (store counts are not static across the branches), so the "prefetch" of the next row was NV + 1 dependent round
 // trips and also waited for the previous row's stores: ~5 us per row and wave, whatever the bandwidth.  Here the wave's
 // rows are unrolled, the operands of DEPTH rows are in flight before the first one is reduced, the waits carry exact
 // counts, and the sched_barriers pin the issue order (loads of row r + DEPTH, then the arithmetic and stores of row r).
-template <int NV, int DEPTH>
-__global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const bf16_t* __restrict__ dy, RowMap dym, const float* __restrict__ x,
+// Three forms are launched, all decided at compile time so that nothing is decided inside the pipeline:
+//   <., ., false, true>    the transformer blocks: bf16 dy, a residual gradient to add (RES);
+//   <., ., false, false>   the final LayerNorms of the step (decoder per modality, joint / encoder per group): no residual gradient;
+//   <., ., true,  false>   the same with fp32 dy (DY_F32: one 16-byte load per chunk, nothing to unpack).
+// ONE __global__ template whose differences are `if constexpr`, not a __device__ body shared by several kernels: routed through
+// an inlined function the blocks' form once grew from 177 to 200 registers at dim 768 and from 238 to 262 at dim 1024; as one
+// template every form keeps the registers its hand-written kernel had (74 / 121 / 177 / 238 with RES, 66 / 104 / 149 / 209 and
+// 68 / 104 / 150 / 214 without, NV = 1 .. 4: profiles/ln_unify.md).
+constexpr int ln_bwd_depth(int nv) { return nv <= 3 ? 4 : 2; }   // rows of operands in flight per wave before the first is reduced (two at dim 1024: registers)
+template <int NV, int DEPTH, bool DY_F32, bool RES>
+__global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const void* __restrict__ dy, RowMap dym, const float* __restrict__ x,
                                                           RowMap xm, const float* __restrict__ gamma,
                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
                                                           const float* __restrict__ dres, float* __restrict__ dx,
                                                           bf16_t* __restrict__ dx_bf16, float* __restrict__ partial, int B, int n) {
     constexpr int dim = 256 * NV;
     static_assert(DEPTH >= 1 && DEPTH <= ROWS_PER_WAVE, "prefetch distance in rows");
+    static_assert(!(DY_F32 && RES), "fp32 dy with a residual gradient takes the generic kernel: nothing launches this form");
     extern __shared__ __attribute__((aligned(16))) float red[];  // [4 waves][3][dim]
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     f32x4 gsum[NV], bsum[NV], csum[NV], gm[NV];
@@ -364,101 +352,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const bf16_t* __restri
     }
     const int row0 = (blockIdx.x * 4 + w) * ROWS_PER_WAVE;
     if (row0 < B * n) {
-        f32x4 xq[ROWS_PER_WAVE][NV], rq[ROWS_PER_WAVE][NV];
-        u32x2 dq[ROWS_PER_WAVE][NV];
-        float muq[ROWS_PER_WAVE], rsq[ROWS_PER_WAVE];
-        size_t xrowq[ROWS_PER_WAVE];
-        auto fetch = [&](int p) {
-            const int row = row0 + p, b = row / n, j = row - b * n;
-            xrowq[p] = map_row(xm, b, j) * dim;
-            const size_t dyrow = map_row(dym, b, j) * dim;
-            muq[p] = mean[row]; rsq[p] = rstd[row];
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int c4 = 4 * (lane + 64 * i);
-                xq[p][i] = *reinterpret_cast<const f32x4*>(x + xrowq[p] + c4);
-                dq[p][i] = *reinterpret_cast<const u32x2*>(dy + dyrow + c4);
-                rq[p][i] = *reinterpret_cast<const f32x4*>(dres + xrowq[p] + c4);
-            }
-        };
-#pragma unroll
-        for (int p = 0; p < DEPTH; ++p) fetch(p);
-#pragma unroll
-        for (int rr = 0; rr < ROWS_PER_WAVE; ++rr) {
-            if (rr + DEPTH < ROWS_PER_WAVE) fetch(rr + DEPTH);
-            __builtin_amdgcn_sched_barrier(0);
-            const float mu = muq[rr], rs = rsq[rr];
-            f32x4 xh[NV], dz[NV];
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const u32x2 pk = dq[rr][i];
-                const f32x4 d = {__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                 __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[i][e] = (xq[rr][i][e] - mu) * rs;
-                    dz[i][e] = d[e] * gm[i][e];
-                    s1 += dz[i][e];
-                    s2 += dz[i][e] * xh[i][e];
-                    gsum[i][e] += d[e] * xh[i][e];
-                    bsum[i][e] += d[e];
-                }
-            }
-            const float c1 = ln_wave_sum(s1) / dim, c2 = ln_wave_sum(s2) / dim;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int c4 = 4 * (lane + 64 * i);
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = rs * (dz[i][e] - c1 - xh[i][e] * c2);
-                o += rq[rr][i];
-                csum[i] += o;
-                *reinterpret_cast<f32x4*>(dx + xrowq[rr] + c4) = o;
-                const u32x2 pk = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
-                *reinterpret_cast<u32x2*>(dx_bf16 + xrowq[rr] + c4) = pk;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if (!partial) return;
-    float* rg = red + (size_t)w * 3 * dim;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c4 = 4 * (lane + 64 * i);
-        *reinterpret_cast<f32x4*>(rg + c4) = gsum[i];
-        *reinterpret_cast<f32x4*>(rg + dim + c4) = bsum[i];
-        *reinterpret_cast<f32x4*>(rg + 2 * dim + c4) = csum[i];
-    }
-    __syncthreads();
-    float* prow = partial + (size_t)blockIdx.x * 3 * dim;
-    for (int c = threadIdx.x; c < 3 * dim; c += 256)
-        prow[c] = red[c] + red[3 * dim + c] + red[6 * dim + c] + red[9 * dim + c];
-}
-
-// The same straight-line sequence for the final LayerNorms of the step (decoder per modality, joint / encoder per group): no
-// residual gradient to add, dy bf16 or fp32 (DY_F32: one 16-byte load per chunk, nothing to unpack).  Both are compile-time forms,
-// so nothing is decided inside the pipeline.  A kernel of its own and not a shared inlined body: routed through a common
-// __device__ function the blocks' form above grew from 177 to 200 registers at dim 768 and from 238 to 262 at dim 1024.
-template <int NV, int DEPTH, bool DY_F32>
-__global__ __launch_bounds__(256) void ln_bwd_final_kernel(const void* __restrict__ dy, RowMap dym, const float* __restrict__ x,
-                                                          RowMap xm, const float* __restrict__ gamma,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          float* __restrict__ dx,
-                                                          bf16_t* __restrict__ dx_bf16, float* __restrict__ partial, int B, int n) {
-    constexpr int dim = 256 * NV;
-    static_assert(DEPTH >= 1 && DEPTH <= ROWS_PER_WAVE, "prefetch distance in rows");
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [4 waves][3][dim]
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    f32x4 gsum[NV], bsum[NV], csum[NV], gm[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        gsum[i] = (f32x4){0, 0, 0, 0}; bsum[i] = (f32x4){0, 0, 0, 0}; csum[i] = (f32x4){0, 0, 0, 0};
-        gm[i] = *reinterpret_cast<const f32x4*>(gamma + 4 * (lane + 64 * i));
-    }
-    const int row0 = (blockIdx.x * 4 + w) * ROWS_PER_WAVE;
-    if (row0 < B * n) {
-        f32x4 xq[ROWS_PER_WAVE][NV];
+        f32x4 xq[ROWS_PER_WAVE][NV], rq[RES ? ROWS_PER_WAVE : 1][NV];
         std::conditional_t<DY_F32, f32x4, u32x2> dq[ROWS_PER_WAVE][NV];
         float muq[ROWS_PER_WAVE], rsq[ROWS_PER_WAVE];
         size_t xrowq[ROWS_PER_WAVE];
@@ -473,6 +367,7 @@ __global__ __launch_bounds__(256) void ln_bwd_final_kernel(const void* __restric
                 xq[p][i] = *reinterpret_cast<const f32x4*>(x + xrowq[p] + c4);
                 if constexpr (DY_F32) dq[p][i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(dy) + dyrow + c4);
                 else dq[p][i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(dy) + dyrow + c4);
+                if constexpr (RES) rq[p][i] = *reinterpret_cast<const f32x4*>(dres + xrowq[p] + c4);
             }
         };
 #pragma unroll
@@ -487,13 +382,8 @@ __global__ __launch_bounds__(256) void ln_bwd_final_kernel(const void* __restric
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 f32x4 d;
-                if constexpr (DY_F32) {
-                    d = dq[rr][i];
-                } else {
-                    const u32x2 pk = dq[rr][i];
-                    d = (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
-                }
+                if constexpr (DY_F32) d = dq[rr][i];
+                else d = bf2x2_to_f32x4(dq[rr][i][0], dq[rr][i][1]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     xh[i][e] = (xq[rr][i][e] - mu) * rs;
@@ -511,6 +401,7 @@ __global__ __launch_bounds__(256) void ln_bwd_final_kernel(const void* __restric
                 f32x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = rs * (dz[i][e] - c1 - xh[i][e] * c2);
+                if constexpr (RES) o += rq[rr][i];
                 csum[i] += o;
                 *reinterpret_cast<f32x4*>(dx + xrowq[rr] + c4) = o;
                 const u32x2 pk = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
@@ -520,23 +411,9 @@ __global__ __launch_bounds__(256) void ln_bwd_final_kernel(const void* __restric
         }
     }
     if (!partial) return;
-    float* rg = red + (size_t)w * 3 * dim;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c4 = 4 * (lane + 64 * i);
-        *reinterpret_cast<f32x4*>(rg + c4) = gsum[i];
-        *reinterpret_cast<f32x4*>(rg + dim + c4) = bsum[i];
-        *reinterpret_cast<f32x4*>(rg + 2 * dim + c4) = csum[i];
-    }
-    __syncthreads();
-    float* prow = partial + (size_t)blockIdx.x * 3 * dim;
-    for (int c = threadIdx.x; c < 3 * dim; c += 256)
-        prow[c] = red[c] + red[3 * dim + c] + red[6 * dim + c] + red[9 * dim + c];
+    ln_bwd_store_partial<NV, true>(red, partial, gsum, bsum, csum, w, lane, dim);
 }
 
-#ifndef LN_BWD_DEPTH
-#define LN_BWD_DEPTH 4    // rows of operands in flight per wave before the first is reduced (dim <= 768)
-#endif
 constexpr int RED_ROWS = 8;   // 8 partial rows per thread: short dependent-free load chains, 4x more (cheap) atomics
 __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restrict__ partial, int nblk, int dim,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -578,6 +455,19 @@ __global__ __launch_bounds__(256) void colsum_batched_kernel(const MhColsumJob* 
 }  // namespace
 
 static int ln_nv(int dim) { const int v = (dim / 4 + 63) / 64; return v <= 4 ? v : 8; }
+// f(std::integral_constant<int, NV>) for the value of ln_nv: the one place that turns the row width into a template argument.
+// WIDE: the generic kernels, which also have the NV = 8 form (dim <= 2048); the straight-line ones end at NV = 4.
+template <int V> using ln_c = std::integral_constant<int, V>;
+template <bool WIDE, class F>
+static void ln_for_nv(int nvs, F f) {
+    switch (nvs) {
+        case 1: f(ln_c<1>{}); break;
+        case 2: f(ln_c<2>{}); break;
+        case 3: f(ln_c<3>{}); break;
+        case 4: f(ln_c<4>{}); break;
+        default: if constexpr (WIDE) f(ln_c<8>{});
+    }
+}
 
 static int layernorm_fwd_impl(const float* x, int x_L, int x_off, const float* gamma, const float* beta, void* y, int y_L,
                               int y_off, int y_is_f32, float* mean, float* rstd, int B, int n, int dim, float eps, void* y8,
@@ -617,27 +507,23 @@ static int layernorm_fwd_impl(const float* x, int x_L, int x_off, const float* g
     const int rows = B * n;
     dim3 grid(ceil_div(rows, 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
-#define LN_FWD(NV) hipLaunchKernelGGL(ln_fwd_kernel<NV>, grid, block, 0, s, x, RowMap{x_L, x_off}, gamma, beta, y, \
-                                      RowMap{y_L, y_off}, y_is_f32, mean, rstd, B, n, dim, eps, (uint8_t*)y8, y8_scale, y8_amax, \
-                                      (uint8_t*)y8s, ld_y8s)
-#define LN_FWD_FAST_(NV, FP8) hipLaunchKernelGGL((ln_fwd_fast_kernel<NV, FP8>), grid, block, 0, s, x, RowMap{x_L, x_off}, gamma, beta, \
-                                                 (bf16_t*)y, RowMap{y_L, y_off}, mean, rstd, B, n, eps, (uint8_t*)y8, y8_scale, y8_amax)
-#define LN_FWD_FAST_MX(NV) hipLaunchKernelGGL((ln_fwd_fast_mx_kernel<NV>), grid, block, 0, s, x, RowMap{x_L, x_off}, gamma, beta, \
-                                              (bf16_t*)y, RowMap{y_L, y_off}, mean, rstd, B, n, eps, (uint8_t*)y8, (uint8_t*)y8s, ld_y8s)
-#define LN_FWD_FAST(NV) do { if (y8s) LN_FWD_FAST_MX(NV); else if (y8) LN_FWD_FAST_(NV, true); else LN_FWD_FAST_(NV, false); } while (0)
+    const RowMap xm{x_L, x_off}, ym{y_L, y_off};
     const int nvs = ln_nv(dim);
     MH_CHECK_ARG(!y8s || (dim % 32 == 0 && !y_is_f32), "mh_layernorm_fwd_mx: dim %% 32 == 0 required, got %d", dim);
-    if (MH_LN_FAST && nvs <= 4 && dim == 256 * nvs && !y_is_f32) {     // the step's own case: straight-line kernel (with or without the e4m3 copy)
-        switch (nvs) { case 1: LN_FWD_FAST(1); break; case 2: LN_FWD_FAST(2); break; case 3: LN_FWD_FAST(3); break;
-                       default: LN_FWD_FAST(4); }
+    if (nvs <= 4 && dim == 256 * nvs && !y_is_f32) {     // the step's own case: straight-line kernel (with or without an e4m3 / MX copy)
+        auto fast = [&](auto y8_form) {
+            ln_for_nv<false>(nvs, [&](auto nv) {
+                hipLaunchKernelGGL((ln_fwd_fast_kernel<decltype(nv)::value, decltype(y8_form)::value>), grid, block, 0, s, x, xm, gamma,
+                                   beta, (bf16_t*)y, ym, mean, rstd, B, n, eps, (uint8_t*)y8, y8_scale, y8_amax, (uint8_t*)y8s, ld_y8s);
+            });
+        };
+        if (y8s) fast(ln_c<LN_Y8_MX>{}); else if (y8) fast(ln_c<LN_Y8_TENSOR>{}); else fast(ln_c<LN_Y8_NONE>{});
     } else {
-        switch (nvs) { case 1: LN_FWD(1); break; case 2: LN_FWD(2); break; case 3: LN_FWD(3); break;
-                       case 4: LN_FWD(4); break; default: LN_FWD(8); }
+        ln_for_nv<true>(nvs, [&](auto nv) {
+            hipLaunchKernelGGL(ln_fwd_kernel<decltype(nv)::value>, grid, block, 0, s, x, xm, gamma, beta, y, ym, y_is_f32, mean, rstd, B, n,
+                               dim, eps, (uint8_t*)y8, y8_scale, y8_amax, (uint8_t*)y8s, ld_y8s);
+        });
     }
-#undef LN_FWD_FAST
-#undef LN_FWD_FAST_MX
-#undef LN_FWD_FAST_
-#undef LN_FWD
     MH_LAUNCH_CHECK();
     return 0;
 }
@@ -655,35 +541,26 @@ static int layernorm_bwd_impl(const void* dy, int dy_L, int dy_off, int dy_is_f3
     dim3 grid(nblk), block(256);
     hipStream_t s = (hipStream_t)stream;
     float* part = (dgamma || partial_only) ? workspace : nullptr;
-#define LN_BWD(NV) hipLaunchKernelGGL(ln_bwd_kernel<NV>, grid, block, lds, s, dy, RowMap{dy_L, dy_off}, dy_is_f32, x, \
-                                      RowMap{x_L, x_off}, gamma, mean, rstd, dres, dx, (bf16_t*)dx_bf16, part, B, n, dim)
-#define LN_BWD_FAST(NV, DEPTH) hipLaunchKernelGGL((ln_bwd_fast_kernel<NV, DEPTH>), grid, block, lds, s, (const bf16_t*)dy, \
-                                                  RowMap{dy_L, dy_off}, x, RowMap{x_L, x_off}, gamma, mean, rstd, dres, dx, \
-                                                  (bf16_t*)dx_bf16, part, B, n)
-#define LN_BWD_FINAL(NV, DEPTH) do { \
-        if (dy_is_f32) hipLaunchKernelGGL((ln_bwd_final_kernel<NV, DEPTH, true>), grid, block, lds, s, dy, RowMap{dy_L, dy_off}, x, \
-                                          RowMap{x_L, x_off}, gamma, mean, rstd, dx, (bf16_t*)dx_bf16, part, B, n); \
-        else hipLaunchKernelGGL((ln_bwd_final_kernel<NV, DEPTH, false>), grid, block, lds, s, dy, RowMap{dy_L, dy_off}, x, \
-                                RowMap{x_L, x_off}, gamma, mean, rstd, dx, (bf16_t*)dx_bf16, part, B, n); } while (0)
+    const RowMap dym{dy_L, dy_off}, xm{x_L, x_off};
     const int nvs = ln_nv(dim);
-    const bool fast = MH_LN_FAST && nvs <= 4 && dim == 256 * nvs && dx_bf16 && rows % ROWS_PER_WAVE == 0;
-    if (fast && !dres) {
-        // the final LayerNorms: no residual gradient, dy bf16 or fp32
-        constexpr int DEPTH = LN_BWD_DEPTH < ROWS_PER_WAVE ? LN_BWD_DEPTH : ROWS_PER_WAVE, DEPTH4 = 2 < ROWS_PER_WAVE ? 2 : ROWS_PER_WAVE;
-        switch (nvs) { case 1: LN_BWD_FINAL(1, DEPTH); break; case 2: LN_BWD_FINAL(2, DEPTH); break;
-                       case 3: LN_BWD_FINAL(3, DEPTH); break; default: LN_BWD_FINAL(4, DEPTH4); }
-    } else if (fast && !dy_is_f32) {
-        // the transformer blocks' own case: straight-line kernel, all of a wave's rows in flight (two at dim 1024: registers)
-        constexpr int DEPTH = LN_BWD_DEPTH < ROWS_PER_WAVE ? LN_BWD_DEPTH : ROWS_PER_WAVE, DEPTH4 = 2 < ROWS_PER_WAVE ? 2 : ROWS_PER_WAVE;
-        switch (nvs) { case 1: LN_BWD_FAST(1, DEPTH); break; case 2: LN_BWD_FAST(2, DEPTH); break;
-                       case 3: LN_BWD_FAST(3, DEPTH); break; default: LN_BWD_FAST(4, DEPTH4); }
+    const bool fast = nvs <= 4 && dim == 256 * nvs && dx_bf16 && rows % ROWS_PER_WAVE == 0;
+    auto fast_form = [&](auto dy_f32, auto res) {      // straight-line kernel, all of a wave's rows in flight (two at dim 1024)
+        ln_for_nv<false>(nvs, [&](auto nv) {
+            constexpr int NV = decltype(nv)::value;
+            hipLaunchKernelGGL((ln_bwd_fast_kernel<NV, ln_bwd_depth(NV), decltype(dy_f32)::value, decltype(res)::value>), grid, block,
+                               lds, s, dy, dym, x, xm, gamma, mean, rstd, dres, dx, (bf16_t*)dx_bf16, part, B, n);
+        });
+    };
+    if (fast && !dres) {              // the final LayerNorms: no residual gradient, dy bf16 or fp32
+        if (dy_is_f32) fast_form(std::true_type{}, std::false_type{}); else fast_form(std::false_type{}, std::false_type{});
+    } else if (fast && !dy_is_f32) {  // the transformer blocks' own case
+        fast_form(std::false_type{}, std::true_type{});
     } else {
-        switch (nvs) { case 1: LN_BWD(1); break; case 2: LN_BWD(2); break; case 3: LN_BWD(3); break;
-                       case 4: LN_BWD(4); break; default: LN_BWD(8); }
+        ln_for_nv<true>(nvs, [&](auto nv) {
+            hipLaunchKernelGGL(ln_bwd_kernel<decltype(nv)::value>, grid, block, lds, s, dy, dym, dy_is_f32, x, xm, gamma, mean, rstd, dres,
+                               dx, (bf16_t*)dx_bf16, part, B, n, dim);
+        });
     }
-#undef LN_BWD_FAST
-#undef LN_BWD_FINAL
-#undef LN_BWD
     if (dgamma && !partial_only)
         hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(ceil_div(3 * dim, 256), ceil_div(nblk, RED_ROWS)), dim3(256), 0, s,
                            workspace, nblk, dim, dgamma, dbeta, dcol);

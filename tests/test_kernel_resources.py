@@ -43,10 +43,11 @@ def test_lds_fits_a_cu_and_workgroups_fit_their_registers(kernels):
 def test_straight_line_layernorm_kernels_are_in_the_library(kernels):
     names = {k["kernel"]: k for k in kernels}
     for nv in (1, 2, 3, 4):
-        for fp8 in ("false", "true"):       # with and without the e4m3 copy (mh_layernorm_fwd_fp8): one kernel, two instantiations
-            form = f"ln_fwd_fast_kernel<{nv}, {fp8}>"
-            assert form in names and names[form]["private_segment_fixed_size"] == 0, form
-    for form in ("ln_bwd_fast_kernel<1, 4>", "ln_bwd_fast_kernel<2, 4>", "ln_bwd_fast_kernel<3, 4>", "ln_bwd_fast_kernel<4, 2>"):
+        for y8 in (0, 1, 2):       # no fp8 copy, the e4m3 copy (mh_layernorm_fwd_fp8), the MX copy (mh_layernorm_fwd_mx): one kernel template
+            form = f"ln_fwd_fast_kernel<{nv}, {y8}>"
+            assert form in names and names[form]["vgpr_count"] <= 256 and names[form]["private_segment_fixed_size"] == 0, form
+    for form in ("ln_bwd_fast_kernel<1, 4, false, true>", "ln_bwd_fast_kernel<2, 4, false, true>", "ln_bwd_fast_kernel<3, 4, false, true>",
+                 "ln_bwd_fast_kernel<4, 2, false, true>"):
         assert form in names and names[form]["vgpr_count"] <= 256 and names[form]["private_segment_fixed_size"] == 0, form
 
 
@@ -104,13 +105,16 @@ def test_straight_line_kernels_issue_their_loads_before_the_first_wait():
         hits = [b for n, b in bodies.items() if fragment in n]
         assert len(hits) == 1, (fragment, [n for n in bodies if fragment in n])
         return hits[0]
-    # backward, dim 768: gamma (3) + 4 rows x (x, dy, dres) x 3 chunks = 39 loads in flight before anything is waited for
-    assert _loads_before_first_vm_wait(body_of("ln_bwd_fast_kernelILi3ELi4E")) >= 39
-    assert _loads_before_first_vm_wait(body_of("ln_bwd_fast_kernelILi2ELi4E")) >= 26
-    # forward: the whole row (and at least part of gamma / beta) before the first wait
-    for fp8 in ("Lb0E", "Lb1E"):
-        assert _loads_before_first_vm_wait(body_of("ln_fwd_fast_kernelILi3E" + fp8)) >= 3
-        assert _loads_before_first_vm_wait(body_of("ln_fwd_fast_kernelILi2E" + fp8)) >= 2
+    # backward with a residual gradient, dim 768: gamma (3) + 4 rows x (x, dy, dres) x 3 chunks = 39 loads in flight before anything
+    # is waited for; 13 per chunk at every width
+    for nv, depth in ((1, 4), (2, 4), (3, 4), (4, 2)):
+        blocks = body_of(f"ln_bwd_fast_kernelILi{nv}ELi{depth}ELb0ELb1E")
+        assert _loads_before_first_vm_wait(blocks) >= 13 * nv, nv
+        assert not any("s_waitcnt vmcnt(0)" in ln for ln in blocks), nv      # every wait inside the pipeline carries a count
+    # forward (no fp8 copy, e4m3 copy, MX copy): the whole row (and at least part of gamma / beta) before the first wait
+    for y8 in ("Li0E", "Li1E", "Li2E"):
+        assert _loads_before_first_vm_wait(body_of("ln_fwd_fast_kernelILi3E" + y8)) >= 3
+        assert _loads_before_first_vm_wait(body_of("ln_fwd_fast_kernelILi2E" + y8)) >= 2
     # batched column sums: the chunk's 16 row loads together
     assert _loads_before_first_vm_wait(body_of("colsum_batched_kernel")) >= 16
     # and the generic backward still shows the pattern the straight-line form removes (documents the finding; if a compiler

@@ -122,14 +122,23 @@ def _ln_check(dev, c, B, n, dim):  # noqa: N803
 
 @pytest.mark.parametrize("dy_f32", [False, True], ids=["dy_bf16", "dy_f32"])
 @pytest.mark.parametrize("B,n", [(2, 4), (3, 8)])
-@pytest.mark.parametrize("dim", [512, 768])
+@pytest.mark.parametrize("dim", [256, 512, 768, 1024])
 def test_final_layernorm_backward_forms(dim, B, n, dy_f32):  # noqa: N803
-    """The straight-line forms without a residual gradient (bf16 and fp32 dy): rows % 4 == 0, dim = 256 NV; 8 rows = one
-    workgroup with two idle waves, 24 rows = two workgroups."""
+    """The straight-line forms without a residual gradient (bf16 and fp32 dy): rows % 4 == 0, dim = 256 NV for every NV (1024:
+    two rows in flight instead of four); 8 rows = one workgroup with two idle waves, 24 rows = two workgroups.  Then the same
+    operands without parameter gradients (no workspace: the kernel leaves before its block tail): the same dx, bit for bit."""
+    from maestro_amd import hip
     dev = _dev()
     c = _ln_case(dev, B, n, dim, dy_f32, seed=100 + dim + 10 * B + int(dy_f32))
     _ln_partial(c, B, n, dim)
     _ln_check(dev, c, B, n, dim)
+    dy_L, dy_off, x_L, x_off = c["maps"]  # noqa: N806
+    gs = guards.GuardSet(dev)
+    dx, dx16 = gs.out((B * x_L, dim), F32, name="dx (no sums)"), gs.out((B * x_L, dim), BF16, name="dx_bf16 (no sums)")
+    hip.layernorm_bwd(c["dy"], dy_L, dy_off, c["x"], x_L, x_off, c["gamma"], c["mean"], c["rstd"], None, dx, dx16, None, None, None, None,
+                      B, n, dim)
+    gs.check()
+    assert guards.bits_equal(dx[c["rows_x"]], c["dx"][c["rows_x"]]) and guards.bits_equal(dx16[c["rows_x"]], c["dx16"][c["rows_x"]])
 
 
 @pytest.mark.parametrize("dy_f32", [False, True], ids=["dy_bf16", "dy_f32"])

@@ -24,7 +24,7 @@ def test_final_layernorm_forms_are_in_the_library_without_scratch():
     names = {k["kernel"]: k for k in kr.library_kernels()}
     for nv, depth in ((1, 4), (2, 4), (3, 4), (4, 2)):
         for f32 in ("false", "true"):
-            form = f"ln_bwd_final_kernel<{nv}, {depth}, {f32}>"
+            form = f"ln_bwd_fast_kernel<{nv}, {depth}, {f32}, false>"
             assert form in names, form
             k = names[form]
             assert k["vgpr_count"] <= 256 and k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
@@ -42,9 +42,9 @@ def test_final_layernorm_forms_issue_their_loads_before_the_first_wait():
     r = subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-o", "-", str(B.CSRC / "norm.hip")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     bodies = _kernel_bodies(r.stdout)
-    for nv, depth in ((2, 4), (3, 4)):
+    for nv, depth in ((1, 4), (2, 4), (3, 4), (4, 2)):
         for f32 in (0, 1):
-            hits = [b for n, b in bodies.items() if f"ln_bwd_final_kernelILi{nv}ELi{depth}ELb{f32}E" in n]
+            hits = [b for n, b in bodies.items() if f"ln_bwd_fast_kernelILi{nv}ELi{depth}ELb{f32}ELb0E" in n]
             assert len(hits) == 1
             # gamma (NV) + 4 rows x (x, dy) x NV chunks in flight before anything is waited for; every later wait is counted
             assert _loads_before_first_vm_wait(hits[0]) >= 9 * nv, (nv, f32)
