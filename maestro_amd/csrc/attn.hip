@@ -16,66 +16,28 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-// Softmax VALU arithmetic on four scores at a time.  ATTN_SCALAR_VALU=1 (with -fno-slp-vectorize) keeps every operation a
-// scalar v_fma_f32 / v_add_f32 / v_mul_f32; 0 writes whole-vector expressions, which the compiler turns into packed
-// v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32 (two floats per instruction).
-#ifndef ATTN_SCALAR_VALU
-#define ATTN_SCALAR_VALU 1
-#endif
-// ATTN_DIAG (diagnostic builds only, WRONG results; MH_ATTN_FLAGS="-DATTN_DIAG=n"): what is one VALU issue slot per score worth?
-//   bit 0: forward without the row-sum adds;  bit 1: backward without the scale / lse FMA and without the "- delta" add;
-//   bit 2: forward (D = 32) without the four denominator MFMAs per tile
-#ifndef ATTN_DIAG
-#define ATTN_DIAG 0
-#endif
-// ATTN_LAZY_MAX = 1 (round 6): the forward does NOT follow a running maximum while the scores stay in range.  Every query has a REFERENCE
-// exponent m2 (log2 units, 0 at first); the exp2 argument of a score is s * scale * log2(e) - m2 (one FMA, as before), and as long as every
-// lane's largest argument of the tile lies within ATTN_LAZY_RANGE of it the probabilities are exp2 of that as it stands: no cross-lane
-// maximum, no exp2 for the correction factor, no rescaling of O and of the denominator (fp32 sums and bf16 probabilities keep their
-// RELATIVE precision whatever the common factor 2^-m2 is; the normalisation removes it, lse = (m2 + log2 l) ln 2 carries it).  A tile
-// that leaves the range (wave-uniform branch) moves the reference to its row maximum the classic way -- up at any tile, down only at the
-// first one.  Same box, scripts/bench_attn.py: forward D = 32, N = 1024 155 -> 122 us, N = 400 34.9 -> 31.4; D = 64, N = 256 18.1 -> 16.2.
-// What it costs: the row's largest probability is no longer exactly 1.0 but a bf16-rounded 2^t, so lse / the output carry up to 2^-9
-// relative from it (observed lse 2e-3 -> 3e-3, output 1.9e-2 -> 2.3e-2 on tests/test_kernels_gpu.py's inputs).  Folding scale x log2(e)
-// into Q (bf16) to drop the FMA as well measured no faster and costs 1.5e-2 on lse: not kept.
-// 0 (MH_ATTN_FLAGS="-DATTN_LAZY_MAX=0") keeps the classic online softmax (A/B aid).
-#ifndef ATTN_LAZY_MAX
-#define ATTN_LAZY_MAX 1
-#endif
-#ifndef ATTN_LAZY_RANGE
-#define ATTN_LAZY_RANGE 24.f
-#endif
-// ATTN_SUM_MFMA = 1: the forward's softmax denominators come out of the matrix cores -- one more 16-row block of "V^T" whose row 0 is all
-// ones, so that O^T's extra row 0 is sum_k P^T[k][q] -- instead of one v_add_f32 per score (the kernel is VALU-bound: 5 -> 4 issue slots per
-// score at D = 32; the 4 extra MFMAs per key tile hold the issue port for 32 cycles).  The sum is then over the bf16-rounded probabilities,
-// the same values the P V product uses.  D = 32 only: same-box A/B -6 % (N = 1024: 155 -> 145 us; N = 400: 36.5 -> 34.5); at D = 64 the
-// kernel is less VALU-bound and the fifth accumulator block is a wash (-4 % ... +2 %), so the fp32 adds stay there.  0
-// (MH_ATTN_FLAGS="-DATTN_SUM_MFMA=0") keeps the fp32 adds everywhere (A/B aid).
-#ifndef ATTN_SUM_MFMA
-#define ATTN_SUM_MFMA 1
-#endif
+// The forward's softmax (profiles/r06_experiments.md).  Every query has a REFERENCE exponent m (log2 units, 0 at first); the exp2
+// argument of a score is s * scale * log2(e) - m, one FMA.  While every lane's largest argument of a tile lies within LAZY_RANGE of the
+// reference, the probabilities are exp2 of that as it stands: no cross-lane maximum, no correction factor, no rescaling of O and of the
+// denominator (fp32 sums and bf16 probabilities keep their RELATIVE precision whatever the common factor 2^-m is; the normalisation
+// removes it, lse = (m + log2 l) ln 2 carries it).  A tile that leaves the range (wave-uniform branch) moves the reference to its row
+// maximum -- up at any tile, down only at the first one: see the branch.  What it costs: the row's largest probability is not exactly
+// 1.0 but a bf16-rounded 2^t, so lse and the output carry up to 2^-9 relative from it (tests/numerics.py has the error model).
+constexpr float LAZY_RANGE = 24.f;
+// Denominators (profiles/r04_attn_bwd.txt, D): at D = 32 they come out of the matrix cores -- one more 16-row block of "V^T" whose row 0
+// is all ones, so that the extra accumulator's row 0 is sum_k P^T[k][q] over the bf16-rounded probabilities, the values the P V product
+// uses -- instead of one v_add_f32 per score (the kernel is VALU-bound there: 5 -> 4 issue slots per score).  At D = 64 the fifth
+// accumulator block measured a wash, so the denominators are fp32 adds of the unrounded probabilities.
+//
+// Softmax VALU arithmetic on four scores at a time stays scalar (v_fma_f32 / v_add_f32 / v_mul_f32, one element per expression, built
+// with -fno-slp-vectorize): beside MFMAs the packed v_pk_* forms are no faster than two scalar instructions on gfx950 and measured
+// 0-6 % slower here (csrc/build.py; what one issue slot per score is worth: profiles/r03_attn_diag.txt).
 __device__ __forceinline__ f32x4 fms4(f32x4 a, float c, f32x4 b) {   // a * c - b
-#if ATTN_SCALAR_VALU
     return (f32x4){__builtin_fmaf(a[0], c, -b[0]), __builtin_fmaf(a[1], c, -b[1]), __builtin_fmaf(a[2], c, -b[2]),
                    __builtin_fmaf(a[3], c, -b[3])};
-#else
-    return a * (f32x4){c, c, c, c} - b;
-#endif
 }
-__device__ __forceinline__ f32x4 scale4(f32x4 a, float c) {
-#if ATTN_SCALAR_VALU
-    return (f32x4){a[0] * c, a[1] * c, a[2] * c, a[3] * c};
-#else
-    return a * c;
-#endif
-}
-__device__ __forceinline__ f32x4 mul4(f32x4 p, f32x4 a) {   // p * a
-#if ATTN_SCALAR_VALU
-    return (f32x4){p[0] * a[0], p[1] * a[1], p[2] * a[2], p[3] * a[3]};
-#else
-    return p * a;
-#endif
-}
+__device__ __forceinline__ f32x4 scale4(f32x4 a, float c) { return (f32x4){a[0] * c, a[1] * c, a[2] * c, a[3] * c}; }
+__device__ __forceinline__ f32x4 mul4(f32x4 p, f32x4 a) { return (f32x4){p[0] * a[0], p[1] * a[1], p[2] * a[2], p[3] * a[3]}; }
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
 
 template <int D> __device__ __forceinline__ int row_swz(int row) {
@@ -162,6 +124,31 @@ __device__ __forceinline__ bf16x8 scale_frag(bf16x8 f, float c) {
     for (int e = 0; e < 4; ++e) r[e] = pack_bf2(__uint_as_float(u[e] << 16) * c, __uint_as_float(u[e] & 0xffff0000u) * c);
     return __builtin_bit_cast(bf16x8, r);
 }
+__device__ __forceinline__ f32x4 exp2_4(f32x4 t) { return (f32x4){exp2_fast(t[0]), exp2_fast(t[1]), exp2_fast(t[2]), exp2_fast(t[3])}; }
+// keys >= N of one query tile's scores (row = key kv0 + 16*kt + 4*g + r): -inf, probability exp2(-inf) = 0
+__device__ __forceinline__ void mask_key_tail(f32x4 (&s)[4], int kv0, int g, int N) {
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (kv0 + 16 * kt + 4 * g + r >= N) s[kt][r] = -INFINITY;
+}
+// epilogue of the forward and of dQ: four accumulator rows 4g .. 4g+3 of tile dt -> bf16, 8 bytes of the output row.  The callers
+// multiply in the argument, vector * scalar (a packed multiply: outside the KV loop it costs nothing).
+__device__ __forceinline__ void store_row(bf16_t* row, int dt, int g, f32x4 v) {
+    u32x2 pk = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+    *reinterpret_cast<u32x2*>(row + 16 * dt + 4 * g) = pk;
+}
+// XCD-aware work order: workgroup ids go round-robin over the 8 XCDs, so consecutive ids (the blocks of ONE head) would
+// each pull that head's K / V through a different L2 (measured: 3.2x the algorithmic bytes at N = 1024).  xcd_remap
+// gives every XCD a contiguous run of (batch, head, block) items: a head's blocks, and the neighbouring head that shares
+// its 128-byte lines at D = 32, stay under one L2.
+struct WorkItem { int b, h, blk; };      // batch, head, first row (query or key) of the workgroup's 128
+__device__ __forceinline__ WorkItem work_item(int N, int H) {
+    const int gx = (N + 127) >> 7;
+    const int wid = xcd_remap(blockIdx.x, gridDim.x);
+    return {wid / (gx * H), (wid / gx) % H, (wid % gx) * 128};
+}
 
 // =============================================================================================== forward
 template <int D>
@@ -171,14 +158,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * TB];  // K row image | V transpose image
     unsigned char* k_img = smem;
     unsigned char* v_img = smem + TB;
-    // XCD-aware work order: workgroup ids go round-robin over the 8 XCDs, so consecutive ids (the blocks of ONE head) would
-    // each pull that head's K / V through a different L2 (measured: 3.2x the algorithmic bytes at N = 1024).  xcd_remap
-    // gives every XCD a contiguous run of (batch, head, block) items: a head's blocks, and the neighbouring head that shares
-    // its 128-byte lines at D = 32, stay under one L2.
-    const int gx = (N + 127) >> 7;
-    const int wid = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = wid / (gx * H), h = (wid / gx) % H;
-    const int q_blk = (wid % gx) * 128;
+    const WorkItem wi = work_item(N, H);
+    const int b = wi.b, h = wi.h, q_blk = wi.blk;
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, lq = l & 15;
     const size_t rs = (size_t)3 * H * D;                              // token stride in qkv
     const bf16_t* qb = qkv + (size_t)b * N * rs + (size_t)h * D;       // q part
@@ -194,7 +175,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
 
     f32x4 o[2][DT];
     float m[2], lsum[2];
-    constexpr bool SUM_MFMA = ATTN_SUM_MFMA && D == 32;
+    constexpr bool SUM_MFMA = D == 32;
     f32x4 ol[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // SUM_MFMA: row 0 (lanes 0-15, element 0) = the running denominator of query column lq
     bf16x8 ones;
     {
@@ -204,7 +185,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
     }
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-        m[qt] = ATTN_LAZY_MAX ? 0.f : -INFINITY; lsum[qt] = 0.f;      // lazy: the reference exponent (log2 units), else the raw-score maximum
+        m[qt] = 0.f; lsum[qt] = 0.f;      // m: the reference exponent (log2 units)
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) o[qt][dt] = (f32x4){0, 0, 0, 0};
     }
@@ -243,7 +224,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
                 for (int qt = 0; qt < 2; ++qt) s[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][ks], s[qt][kt], 0, 0, 0);
             }
         bf16x8 pf[2][2];
-#if ATTN_LAZY_MAX
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             {
@@ -251,13 +231,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt) s[qt][kt] = fms4(s[qt][kt], c, m4);     // the exp2 argument relative to the reference
             }
-            if constexpr (TAIL) {   // keys >= N: probability exp2(-inf) = 0
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (kv0 + 16 * kt + 4 * g + r >= N) s[qt][kt][r] = -INFINITY;
-            }
+            if constexpr (TAIL) mask_key_tail(s[qt], kv0, g, N);
             float mx = s[qt][0][0];                                  // this lane's largest exp2 argument of the tile
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
@@ -270,7 +244,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
             // left alone (moving down with mass accumulated would scale O up by 2^|shift|).  A NaN score compares false and flows
             // through exp2 into the output, as it does in the reference.
             const bool first = it == 0;
-            const bool leave = mx > ATTN_LAZY_RANGE || (first && mx < -ATTN_LAZY_RANGE);
+            const bool leave = mx > LAZY_RANGE || (first && mx < -LAZY_RANGE);
             if (__builtin_amdgcn_ballot_w64(leave) != 0) {
                 mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
                 mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -288,8 +262,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
             float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
-                const f32x4 t = s[qt][kt];
-                const f32x4 pv = {exp2_fast(t[0]), exp2_fast(t[1]), exp2_fast(t[2]), exp2_fast(t[3])};
+                const f32x4 pv = exp2_4(s[qt][kt]);
                 s[qt][kt] = pv;
                 if constexpr (!SUM_MFMA) { p0 += pv[0]; p1 += pv[1]; p2 += pv[2]; p3 += pv[3]; }
             }
@@ -297,72 +270,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
             pf[qt][0] = pack_acc(s[qt][0], s[qt][1]);
             pf[qt][1] = pack_acc(s[qt][2], s[qt][3]);
         }
-#else
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            // running max on the RAW scores (scale > 0 commutes with max); scale and max folded into one FMA per element
-            if constexpr (TAIL) {
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (kv0 + 16 * kt + 4 * g + r >= N) s[qt][kt][r] = -INFINITY;
-            }
-            float mx = m[qt];
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) {   // two v_max3_f32 per four scores
-                mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[qt][kt][0]), s[qt][kt][1]);
-                mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[qt][kt][2]), s[qt][kt][3]);
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float alpha = exp2_fast((m[qt] - mx) * c);  // first tile: exp2(-inf) = 0
-            m[qt] = mx;
-            const float mc = mx * c;
-            // the softmax is VALU-bound (D = 32: ~4 VALU cycles per MFMA cycle): whole-vector expressions so that the
-            // scale / shift and the row sum become packed v_pk_fma_f32 / v_pk_add_f32 (two floats per instruction)
-            const f32x4 mc4 = {mc, mc, mc, mc};
-            if constexpr (SUM_MFMA) {
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    const f32x4 t = fms4(s[qt][kt], c, mc4);
-                    s[qt][kt] = (f32x4){exp2_fast(t[0]), exp2_fast(t[1]), exp2_fast(t[2]), exp2_fast(t[3])};
-                }
-                ol[qt][0] *= alpha;
-            } else {
-#if ATTN_SCALAR_VALU
-            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-#else
-            f32x4 ps4 = {0.f, 0.f, 0.f, 0.f};
-#endif
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) {
-                const f32x4 t = fms4(s[qt][kt], c, mc4);
-                const f32x4 pv = {exp2_fast(t[0]), exp2_fast(t[1]), exp2_fast(t[2]), exp2_fast(t[3])};
-                s[qt][kt] = pv;
-#if ATTN_DIAG & 1
-                p0 = pv[0];
-#elif ATTN_SCALAR_VALU
-                p0 += pv[0]; p1 += pv[1]; p2 += pv[2]; p3 += pv[3];
-#else
-                ps4 += pv;
-#endif
-            }
-#if ATTN_SCALAR_VALU
-            const float ps = (p0 + p1) + (p2 + p3);
-#else
-            const float ps = (ps4[0] + ps4[1]) + (ps4[2] + ps4[3]);
-#endif
-            lsum[qt] = lsum[qt] * alpha + ps;
-            }
-            // (skipping these multiplies under a wave-uniform `alpha == 1` test -- bit-identical, 9 % fewer VALU instructions on tiles
-            //  whose maximum did not move -- measured no gain: profiles/r04_experiments.txt)
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) o[qt][dt] = scale4(o[qt][dt], alpha);
-            pf[qt][0] = pack_acc(s[qt][0], s[qt][1]);
-            pf[qt][1] = pack_acc(s[qt][2], s[qt][3]);
-        }
-#endif
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -371,16 +278,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
 #pragma unroll
                 for (int qt = 0; qt < 2; ++qt) o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt][u], o[qt][dt], 0, 0, 0);
             }
-#if !(ATTN_DIAG & 4)       // (bit 2, WRONG results: the forward without the denominator MFMAs -- what are 4 of its 20 MFMAs per tile worth?)
         if constexpr (SUM_MFMA) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int qt = 0; qt < 2; ++qt) ol[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qt][u], ol[qt], 0, 0, 0);
         }
-#else
-        if constexpr (SUM_MFMA) { ol[0][0] = 1.f; ol[1][0] = 1.f; }
-#endif
     };
     const int nfull = N / 64;
     for (int it = 0; it < nfull; ++it) kv_tile(it, std::false_type{});
@@ -400,16 +303,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
         const float inv = 1.f / lt;
         bf16_t* orow = out + ((size_t)b * N + q) * H * D + (size_t)h * D;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const f32x4 v = o[qt][dt] * inv;
-            u32x2 pk = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-            *reinterpret_cast<u32x2*>(orow + 16 * dt + 4 * g) = pk;
-        }
-#if ATTN_LAZY_MAX
-        if (g == 0) lse[((size_t)b * H + h) * N + q] = m[qt] * 0.6931471805599453f + logf(lt);  // m is the reference exponent, log2 units
-#else
-        if (g == 0) lse[((size_t)b * H + h) * N + q] = m[qt] * scale + logf(lt);  // m is a raw-score max
-#endif
+        for (int dt = 0; dt < DT; ++dt) store_row(orow, dt, g, o[qt][dt] * inv);
+        if (g == 0) lse[((size_t)b * H + h) * N + q] = m[qt] * 0.6931471805599453f + logf(lt);  // the lse store: m is the reference exponent, log2 units
     }
 }
 
@@ -424,14 +319,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     unsigned char* k_row = smem;
     unsigned char* k_tr = smem + TB;
     unsigned char* v_row = smem + 2 * TB;
-    // XCD-aware work order: workgroup ids go round-robin over the 8 XCDs, so consecutive ids (the blocks of ONE head) would
-    // each pull that head's K / V through a different L2 (measured: 3.2x the algorithmic bytes at N = 1024).  xcd_remap
-    // gives every XCD a contiguous run of (batch, head, block) items: a head's blocks, and the neighbouring head that shares
-    // its 128-byte lines at D = 32, stay under one L2.
-    const int gx = (N + 127) >> 7;
-    const int wid = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = wid / (gx * H), h = (wid / gx) % H;
-    const int q_blk = (wid % gx) * 128;
+    const WorkItem wi = work_item(N, H);
+    const int b = wi.b, h = wi.h, q_blk = wi.blk;
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, lq = l & 15;
     const size_t rs = (size_t)3 * H * D, os = (size_t)H * D;
     const bf16_t* qb = qkv + (size_t)b * N * rs + (size_t)h * D;
@@ -497,11 +386,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 s[qt][kt] = (f32x4){-lse2[qt], -lse2[qt], -lse2[qt], -lse2[qt]};
-#if ATTN_DIAG & 2
-                dp[qt][kt] = (f32x4){0, 0, 0, 0};
-#else
                 dp[qt][kt] = (f32x4){-dlt[qt], -dlt[qt], -dlt[qt], -dlt[qt]};
-#endif
             }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
@@ -515,24 +400,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
                     dp[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dof[qt][ks], dp[qt][kt], 0, 0, 0);
                 }
             }
-        if constexpr (TAIL) {   // last KV tile only: keys >= N get probability exp2(-inf) = 0
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (kv0 + 16 * kt + 4 * g + r >= N) s[qt][kt][r] = -INFINITY;
+        if constexpr (TAIL) {   // (two calls, not a loop over qt: from the loop the compiler schedules 270-360 lines of this kernel elsewhere)
+            mask_key_tail(s[0], kv0, g, N);
+            mask_key_tail(s[1], kv0, g, N);
         }
         bf16x8 dsf[2][2];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
 #pragma unroll
-            for (int kt = 0; kt < 4; ++kt) {
-                const f32x4 t = s[qt][kt];
-                const f32x4 pv = {exp2_fast(t[0]), exp2_fast(t[1]), exp2_fast(t[2]), exp2_fast(t[3])};
-                s[qt][kt] = mul4(pv, dp[qt][kt]);           // dS / scale = P (dP - delta); the factor is applied to dQ once at the end
-            }
+            for (int kt = 0; kt < 4; ++kt)
+                s[qt][kt] = mul4(exp2_4(s[qt][kt]), dp[qt][kt]);     // dS / scale = P (dP - delta); the factor is applied to dQ once at the end
             dsf[qt][0] = pack_acc(s[qt][0], s[qt][1]);
             dsf[qt][1] = pack_acc(s[qt][2], s[qt][3]);
         }
@@ -554,11 +431,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
         if (q >= N) continue;
         bf16_t* drow = dqkv + ((size_t)b * N + q) * rs + (size_t)h * D;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const f32x4 v = dq[qt][dt] * scale;
-            u32x2 pk = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-            *reinterpret_cast<u32x2*>(drow + 16 * dt + 4 * g) = pk;
-        }
+        for (int dt = 0; dt < DT; ++dt) store_row(drow, dt, g, dq[qt][dt] * scale);
     }
 }
 
@@ -576,14 +449,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
     unsigned char* do_tr = smem + 3 * TB;
     float* s_lse = reinterpret_cast<float*>(smem + 4 * TB);
     float* s_dlt = s_lse + 64;
-    // XCD-aware work order: workgroup ids go round-robin over the 8 XCDs, so consecutive ids (the blocks of ONE head) would
-    // each pull that head's K / V through a different L2 (measured: 3.2x the algorithmic bytes at N = 1024).  xcd_remap
-    // gives every XCD a contiguous run of (batch, head, block) items: a head's blocks, and the neighbouring head that shares
-    // its 128-byte lines at D = 32, stay under one L2.
-    const int gx = (N + 127) >> 7;
-    const int wid = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = wid / (gx * H), h = (wid / gx) % H;
-    const int k_blk = (wid % gx) * 128;
+    const WorkItem wi = work_item(N, H);
+    const int b = wi.b, h = wi.h, k_blk = wi.blk;
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, lk = l & 15;
     const size_t rs = (size_t)3 * H * D, os = (size_t)H * D;
     const bf16_t* qb = qkv + (size_t)b * N * rs + (size_t)h * D;
@@ -648,11 +515,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
         f32x4 s[4][2], dp[4][2];
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt) {
-#if ATTN_DIAG & 2
-            const f32x4 nd4 = {0, 0, 0, 0};
-#else
             const f32x4 nd4 = *reinterpret_cast<const f32x4*>(s_dlt + 16 * qt + 4 * g);
-#endif
             const f32x4 nl4 = *reinterpret_cast<const f32x4*>(s_lse + 16 * qt + 4 * g);
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) { s[qt][kt] = nl4; dp[qt][kt] = nd4; }
@@ -674,8 +537,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
         for (int qt = 0; qt < 4; ++qt) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) {
-                const f32x4 t = s[qt][kt];
-                const f32x4 pv = {exp2_fast(t[0]), exp2_fast(t[1]), exp2_fast(t[2]), exp2_fast(t[3])};
+                const f32x4 pv = exp2_4(s[qt][kt]);
                 s[qt][kt] = pv;
                 dp[qt][kt] = mul4(pv, dp[qt][kt]);                     // dS / scale = P (dP - delta) (scale applied to dK at the end)
             }
@@ -708,6 +570,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
         bf16_t* vrow = krow + (size_t)H * D;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
+            // written out, not store_row: through the helper (or scale4) the four multiplies leave their place between the packs, or
+            // dV's pack moves behind dK's store, and the scheduler reorders 60-370 lines of this kernel (profiles/attn_straightline.md)
             u32x2 pk = {pack_bf2(dk[kt][dt][0] * scale, dk[kt][dt][1] * scale), pack_bf2(dk[kt][dt][2] * scale, dk[kt][dt][3] * scale)};
             u32x2 pv = {pack_bf2(dv[kt][dt][0], dv[kt][dt][1]), pack_bf2(dv[kt][dt][2], dv[kt][dt][3])};
             *reinterpret_cast<u32x2*>(krow + 16 * dt + 4 * g) = pk;
@@ -716,19 +580,25 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
     }
 }
 
-
 // (Round 4's single-pass backward -- one workgroup per (batch, head), dQ summed in an fp32 LDS image -- measured at parity with the two
 // kernels at N = 1024 and slower below (profiles/r04_attn_bwd.txt) and was removed in round 5.)
 
 }  // namespace
+
+// One dispatch on the head dimension for the three launches: f receives std::integral_constant<int, D>.
+template <class F> void for_head_dim(int D, F&& f) {
+    if (D == 64) f(std::integral_constant<int, 64>{});
+    else f(std::integral_constant<int, 32>{});
+}
 
 extern "C" int mh_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, int D, float scale, void* stream) {
     MH_CHECK_ARG(qkv && out && lse, "mh_attn_fwd: null pointer");
     MH_CHECK_ARG(B > 0 && N > 0 && H > 0 && (D == 32 || D == 64), "mh_attn_fwd: unsupported shape B=%d N=%d H=%d D=%d", B, N, H, D);
     MH_CHECK_ARG(H <= 65535 && B <= 65535, "mh_attn_fwd: grid limit");
     dim3 grid(ceil_div(N, 128) * H * B), block(256);
-    if (D == 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, scale);
-    else hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, scale);
+    for_head_dim(D, [&](auto d) {
+        hipLaunchKernelGGL(attn_fwd_kernel<d()>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, scale);
+    });
     MH_LAUNCH_CHECK();
     return 0;
 }
@@ -739,13 +609,11 @@ extern "C" int mh_attn_bwd(const void* qkv, const void* out, const void* dout, c
     MH_CHECK_ARG(B > 0 && N > 0 && H > 0 && (D == 32 || D == 64), "mh_attn_bwd: unsupported shape B=%d N=%d H=%d D=%d", B, N, H, D);
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(ceil_div(N, 128) * H * B), block(256);
-    if (D == 64) {
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<64>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, scale);
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<64>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, scale);
-    } else {
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<32>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, scale);
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<32>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, scale);
-    }
+    for_head_dim(D, [&](auto d) {
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<d()>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, scale);
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<d()>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, N, H, scale);
+    });
     MH_LAUNCH_CHECK();
     return 0;
 }
+

@@ -385,6 +385,17 @@ def _hbm_call(kind: str, nbytes: float, name: str, *args) -> None:
     e1.record()
 
 
+def _flop_call(kind: str, flops: float, shape, name: str, *args) -> None:
+    """``call`` bracketed by HIP events when a ``KernelTimer`` is active: an MFMA kernel's launch under its kind, algorithmic
+    FLOPs and shape (bench.py's roofline leg)."""
+    if _timer is None:
+        return call(name, *args)
+    e0, e1 = _timer.record(kind, flops, shape)
+    e0.record()
+    call(name, *args)
+    e1.record()
+
+
 def _esz(t) -> int:
     return 0 if t is None else t.element_size()
 
@@ -804,11 +815,13 @@ def gemm_tn_slabs(M, N, K, A, lda, B, ldb, slabs):  # noqa: N803
 
 
 def attn_fwd(qkv, out, lse, B, N, H, D, scale):
-    call("mh_attn_fwd", qkv, out, lse, _I(B), _I(N), _I(H), _I(D), _F(scale))
+    _flop_call("attn_fwd", 4.0 * B * H * N * N * D, (B, N, H, D), "mh_attn_fwd", qkv, out, lse, _I(B), _I(N), _I(H), _I(D), _F(scale))
 
 
 def attn_bwd(qkv, out, dout, lse, delta, dqkv, B, N, H, D, scale):
-    call("mh_attn_bwd", qkv, out, dout, lse, delta, dqkv, _I(B), _I(N), _I(H), _I(D), _F(scale))
+    # algorithmic 5 matmuls (the two-kernel form recomputes 2 more)
+    _flop_call("attn_bwd", 10.0 * B * H * N * N * D, (B, N, H, D), "mh_attn_bwd", qkv, out, dout, lse, delta, dqkv, _I(B), _I(N), _I(H),
+               _I(D), _F(scale))
 
 
 def patchify(img, cols, target, BD, Ctot, S, P, Kpad, norm_bands, n_groups, normalise, rescale_elev):
@@ -1374,27 +1387,6 @@ def set_kernel_timer(t: KernelTimer | None) -> None:
 
 def kernel_timer_active() -> bool:
     return _timer is not None
-
-
-_attn_fwd_raw, _attn_bwd_raw = attn_fwd, attn_bwd
-
-
-def attn_fwd(qkv, out, lse, B, N, H, D, scale):  # noqa: F811
-    if _timer is None:
-        return _attn_fwd_raw(qkv, out, lse, B, N, H, D, scale)
-    e0, e1 = _timer.record("attn_fwd", 4.0 * B * H * N * N * D, (B, N, H, D))
-    e0.record()
-    _attn_fwd_raw(qkv, out, lse, B, N, H, D, scale)
-    e1.record()
-
-
-def attn_bwd(qkv, out, dout, lse, delta, dqkv, B, N, H, D, scale):  # noqa: F811
-    if _timer is None:
-        return _attn_bwd_raw(qkv, out, dout, lse, delta, dqkv, B, N, H, D, scale)
-    e0, e1 = _timer.record("attn_bwd", 10.0 * B * H * N * N * D, (B, N, H, D))  # algorithmic 5 matmuls (the two-kernel form recomputes 2 more)
-    e0.record()
-    _attn_bwd_raw(qkv, out, dout, lse, delta, dqkv, B, N, H, D, scale)
-    e1.record()
 
 
 # ------------------------------------------------------------------------------------------------ grouped wgrad

@@ -273,7 +273,7 @@ LOG2E = 1.4426950408889634
 LN2 = 0.6931471805599453
 FLUSH_F32 = 2.0 ** -126     # smallest normal fp32: v_exp_f32 and the matrix cores return 0 below it
 ATTN_TILE = 64              # keys per forward tile
-ATTN_RANGE = 24.0           # ATTN_LAZY_RANGE
+ATTN_RANGE = 24.0           # LAZY_RANGE of csrc/attn.hip
 ATTN_KINDS = ("randn1.5", "randn3", "offset", "neg", "rising", "peaked", "spike_late", "low_after_high")
 # terms of attn_bounds that the self-check removes one at a time to show that each is needed
 ATTN_BOUND_TERMS = ("fold", "fl_E", "fl_EP", "fl_store")
@@ -345,27 +345,31 @@ def attn_ref64(q, k, v, do):
 
 
 # The error model, to first order (expm1 where an exponent error is exponentiated); u = 2^-24, HB = 2^-8, FL = 2^-126, 2^-23 per
-# accumulated fp32 term as in gemm_bound.  Line numbers: csrc/attn.hip.
+# accumulated fp32 term as in gemm_bound.  Sites of csrc/attn.hip by the name of their helper or statement.
 #
-# Forward (attn_fwd_kernel).  The exp2 argument of score j of query i is fma(s, c, -m) - mx (fms4, :252 and :282): s is an fp32
-# sum of D exact products (c D 2^-23 Sabs in log2 units), c = fl(scale log2e) (u |A| log2e), the two FMAs round a value of at most
-# (|A| + amax) log2e + 24 (the reference m lies within 24 of a score that was there): together dt.  m itself is common to the row
-# and cancels in P / l; in lse it is multiplied by ln 2 once (:409).  v_exp_f32 is good to one ulp (2^-22 covers it), and every
-# move of the reference multiplies what was accumulated by alpha = exp2(-mx), one exp2 and one product per tile: nt 2^-22.
-# eta is the relative error of an fp32 probability, eta_b = eta + HB (1 + eta) that of its bf16 image (pack_bf2, :297).
-# O = (sum_j pb_j v_j) / l: the numerator is an fp32 sum of N exact products of erroneous pb; the denominator is the same sum
-# against ones at D = 32 (ATTN_SUM_MFMA, :379: eta_b) and an fp32 sum of the unrounded p at D = 64 (:294-296: eta).  1 / l and
-# the product with it (:400, :404) are 2^-22 |O|, the store (:405) HB.
-# lse = m ln2 + logf(l) (:409): the relative error of l, one ulp of logf and of the sum at |lse|, the product m ln2 with
+# Forward (attn_fwd_kernel).  The exp2 argument of score j of query i is fma(s, c, -m) - mx (fms4 against the reference exponent,
+# and fms4 again in the branch that moves it): s is an fp32 sum of D exact products (c D 2^-23 Sabs in log2 units),
+# c = fl(scale log2e) (u |A| log2e), the two FMAs round a value of at most (|A| + amax) log2e + 24 (the reference m lies within
+# LAZY_RANGE = 24 of a score that was there): together dt.  m itself is common to the row and cancels in P / l; in lse it is
+# multiplied by ln 2 once (the lse store).  v_exp_f32 (exp2_4) is good to one ulp (2^-22 covers it), and every move of the
+# reference multiplies what was accumulated by alpha = exp2(-mx), one exp2 and one product per tile: nt 2^-22.
+# eta is the relative error of an fp32 probability, eta_b = eta + HB (1 + eta) that of its bf16 image (pack_acc of the
+# probabilities).  O = (sum_j pb_j v_j) / l: the numerator is an fp32 sum of N exact products of erroneous pb; the denominator is
+# the same sum against ones at D = 32 (SUM_MFMA, the MFMAs into ol: eta_b) and an fp32 sum of the unrounded p at D = 64 (the
+# p0 .. p3 adds into lsum: eta).  1 / l and the product with it (inv, the argument of store_row) are 2^-22 |O|, the store
+# (pack_bf2 in store_row) HB.
+# lse = m ln2 + logf(l) (the lse store): the relative error of l, one ulp of logf and of the sum at |lse|, the product m ln2 with
 # |m ln2| <= amax + 24: b_lse.  (ocml's logf is stated at 1 ulp; 4 u (|lse| + ...) has room for that, not widened.)
 #
 # Backward (attn_bwd_dq_kernel / attn_bwd_dkv_kernel).  Both recompute P = exp2(q' k^T - lse log2e) with ONE operand folded:
-# q' = bf16(fl(q fl(c))) (scale_frag, :162, called at :456 resp. :600 on k): HB + 3u relative per product, so (HB + 3u) c Sabs --
-# the FOLD term.  The MFMA chain starts at -fl(lse log2e) (:464/:499, :635/:656) and adds D products: (D + 2) 2^-23 of the
-# magnitudes; the lse it is given is off by lse_err.  rho is the relative error of a recomputed probability.
-# delta (:460-463) is an fp32 sum of D products of the bf16 out (off from O64 by out_err) with dO.  dP - delta is a chain that
-# starts at -delta and adds D products (:503, :515): eg.  dS / scale = bf16(p g) (:534/:680 mul4, pack_acc): E.  dQ, dK are fp32
-# sums over N of exact products, times scale (:558, :711), stored as bf16.  dV uses bf16(p) (:687): EP.
+# q' = bf16(fl(q fl(c))) (scale_frag, called on the Q fragments in the dQ kernel and on the K fragments in the dK / dV kernel):
+# HB + 3u relative per product, so (HB + 3u) c Sabs -- the FOLD term.  The MFMA chain starts at -fl(lse log2e) (lse2 and the initial
+# s in the dQ kernel, s_lse and nl4 in the dK / dV kernel) and adds D products: (D + 2) 2^-23 of the magnitudes; the lse it is
+# given is off by lse_err.  rho is the relative error of a recomputed probability.
+# delta (the `part` sum of the dQ kernel) is an fp32 sum of D products of the bf16 out (off from O64 by out_err) with dO.
+# dP - delta is a chain that starts at -delta and adds D products (the initial dp and the dP MFMAs): eg.  dS / scale = bf16(p g)
+# (mul4 in both kernels, then pack_acc): E.  dQ, dK are fp32 sums over N of exact products, times scale (the argument of dQ's
+# store_row, the written-out dK store), stored as bf16.  dV uses bf16(p) (pack_acc into pf of the dK / dV kernel): EP.
 # Underflow: a probability, a product p g or a bf16 image below 2^-126 is returned as 0 by the hardware (and an fp64 reference
 # keeps it): FL per element of E and EP (fl_E, fl_EP), and FL on each stored gradient / output (fl_store).
 def attn_bounds(ref, q, k, v, do, lse_err=None, out_err=None, drop=()):
@@ -433,7 +437,7 @@ def _c32(D: int) -> torch.Tensor:  # noqa: N803
 
 
 def attn_emulated_fwd(q, k, v, defect=None):
-    """torch fp32 emulation of attn_fwd_kernel as written (ATTN_LAZY_MAX = 1): groups of 16 queries (one ``qt`` of a wave) over
+    """torch fp32 emulation of attn_fwd_kernel as written (reference exponent, LAZY_RANGE): groups of 16 queries (one ``qt`` of a wave) over
     64-key tiles, the range test per lane (16 keys of the tile) as in the kernel; returns ``out`` (bf16 values) and ``lse``.  ``defect`` = "p_trunc": the WRONG form that truncates P to bf16."""
     N, D = q.shape  # noqa: N806
     c = _c32(D)

@@ -51,6 +51,20 @@ def test_straight_line_layernorm_kernels_are_in_the_library(kernels):
         assert form in names and names[form]["vgpr_count"] <= 256 and names[form]["private_segment_fixed_size"] == 0, form
 
 
+def test_attention_kernels_stay_inside_their_occupancy_step(kernels):
+    """The six attention kernels (csrc/attn.hip) by name, spill-free, and inside the occupancy step they hold: 512 registers per
+    SIMD lane give four waves up to 128 VGPR, three up to 168, two up to 256 (profiles/attn_straightline.md has the counts)."""
+    names = {k["kernel"]: k for k in kernels}
+    limits = {"attn_fwd_kernel<32>": 128,
+              "attn_fwd_kernel<64>": 168, "attn_bwd_dq_kernel<32>": 168, "attn_bwd_dkv_kernel<32>": 168,
+              "attn_bwd_dq_kernel<64>": 256, "attn_bwd_dkv_kernel<64>": 256}
+    for form, limit in limits.items():
+        k = names.get(form)
+        assert k is not None, (form, sorted(n for n in names if n.startswith("attn_")))
+        assert k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
+        assert k["vgpr_count"] <= limit, k
+
+
 def test_stream_k_kernels_keep_their_accumulators_in_registers(kernels):
     """Round 6: the eight-wave stream-K kernel has 256 registers per lane, 128 of them accumulators; written the obvious way
     (accumulators updated inside one arm of a branch) it spilled 30-250 registers -- some of them the K loop's fragment addresses,

@@ -126,7 +126,7 @@ def test_attention_fwd_bwd(dev, B, N, H, D):
     hip.attn_fwd(qkv, out, lse, B, N, H, D, scale)
     ref = qkv.float().requires_grad_(True)
     want, want_lse = _attn_ref(ref, scale)
-    # (round 6: the forward no longer normalises the probabilities of a tile by its row maximum -- csrc/attn.hip, ATTN_LAZY_MAX -- so a
+    # (round 6: the forward no longer normalises the probabilities of a tile by its row maximum -- csrc/attn.hip, LAZY_RANGE -- so a
     #  row's largest probability is a bf16-rounded 2^t instead of exactly 1.0: observed lse 2.0e-3 -> 3.1e-3, output 1.9e-2 -> 2.3e-2)
     assert (out.float() - want).abs().max() < 3e-2, (out.float() - want).abs().max().item()
     assert (lse - want_lse).abs().max() < 5e-3
@@ -166,7 +166,7 @@ def test_attention_softmax_spike(dev):
 @pytest.mark.parametrize("case", ["all_low", "all_high", "rising", "low_then_spike_then_low", "short_low"])
 def test_attention_reference_exponent_moves(dev, case):
     """The forward keeps a per-query REFERENCE exponent instead of a running maximum and only moves it when a tile's scores leave
-    +-ATTN_LAZY_RANGE around it (csrc/attn.hip): down at the first tile only, up at any tile.  Each case forces one of those moves."""
+    +-LAZY_RANGE around it (csrc/attn.hip): down at the first tile only, up at any tile.  Each case forces one of those moves."""
     from maestro_amd import hip
     B, N, H, D = 1, 64 if case == "short_low" else 320, 2, 32
     g = torch.Generator().manual_seed(11)
