@@ -4,14 +4,11 @@
 // Everything here is integer: LDS histograms of 32-bit counters per workgroup, flushed with 64-bit integer atomics (plain vector
 // memory).  The result does not depend on the launch order and there is no float atomic.
 #include "common.hpp"
+#include "logits_walk.hpp"
 #include "../../include/maestro_hip.h"
 
 namespace {
 
-constexpr int CF_THREADS = 256;
-constexpr int CF_TILE = 4096;             // floats of one staged logits tile (16 KiB): 4 16-byte loads per thread
-constexpr int CF_VEC = CF_TILE / 4 / CF_THREADS;
-constexpr int CF_MAX_PIX = 1024;          // pixels of one tile at most (small C)
 constexpr long CF_WG_PIXELS = 1L << 31;   // pixels one workgroup counts at most: its 32-bit LDS counters cannot wrap
 
 __device__ __forceinline__ long load_int(const void* p, long i, int bytes) {
@@ -20,54 +17,6 @@ __device__ __forceinline__ long load_int(const void* p, long i, int bytes) {
         case 2: return reinterpret_cast<const int16_t*>(p)[i];
         case 4: return reinterpret_cast<const int32_t*>(p)[i];
         default: return reinterpret_cast<const int64_t*>(p)[i];
-    }
-}
-
-// How the [n_rows, ld] logits are cut into tiles, in memory order.  A row holds PP = P * P pixels of C floats.  PP <= npt: a tile is
-// `rows_per_tile` whole rows; otherwise a tile is one chunk of `npt` pixels (a multiple of 4: every chunk starts on a 16-byte
-// boundary of its row) of one row, the last chunk of a row shorter.
-struct CfGeom {
-    long n_rows, n_tiles;
-    int g, P, C, Cs, ld, PP, npt, rows_per_tile, chunks_per_row, vec;
-};
-
-struct CfTile {
-    long row0;      // first logits row
-    int nr;         // rows
-    int pix0;       // first pixel inside the row(s)
-    int pps;        // pixels per row segment; the segment is n = pps * C floats from column pix0 * C
-};
-
-__device__ __forceinline__ CfTile cf_tile(const CfGeom& G, long t) {
-    CfTile T;
-    if (G.chunks_per_row == 1) {
-        T.row0 = t * G.rows_per_tile;
-        T.nr = (int)min((long)G.rows_per_tile, G.n_rows - T.row0);
-        T.pix0 = 0;
-        T.pps = G.PP;
-    } else {
-        T.row0 = t / G.chunks_per_row;
-        const int ch = (int)(t - T.row0 * G.chunks_per_row);
-        T.nr = 1;
-        T.pix0 = ch * G.npt;
-        T.pps = min(G.npt, G.PP - T.pix0);
-    }
-    return T;
-}
-
-// Local element e of a tile (rows concatenated, pad columns left out) -> its address.
-__device__ __forceinline__ const float* cf_addr(const float* logits, const CfGeom& G, const CfTile& T, unsigned e) {
-    const unsigned n = (unsigned)T.pps * G.C, r = e / n, o = e - r * n;
-    return logits + (size_t)(T.row0 + r) * G.ld + (size_t)T.pix0 * G.C + o;
-}
-
-// Element e goes to tile[(e / C) * Cs + e % C]: Cs = C | 1 is odd, so the 64 lanes that each scan one pixel hit 64 different banks.
-__device__ __forceinline__ void cf_stage4(float* tile, const CfGeom& G, unsigned e, const f32x4 v) {
-    unsigned p = e / G.C, c = e - p * G.C;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        tile[p * G.Cs + c] = v[j];
-        if (++c == (unsigned)G.C) { c = 0; ++p; }
     }
 }
 
@@ -84,47 +33,20 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_ce_kernel(const float* _
     const int tid = threadIdx.x, C = G.C, CC = C * C;
     for (int i = tid; i < CC; i += CF_THREADS) hist[i] = 0;
 
-    f32x4 pre[CF_VEC];
-    float pre_tail = 0.f;
-    auto prefetch = [&](const CfTile& T) {          // vec only: 16-byte loads of the tile into registers
-        const unsigned total = (unsigned)T.nr * T.pps * C, nvec = total >> 2, tail = total & 3;
-#pragma unroll
-        for (int k = 0; k < CF_VEC; ++k) {
-            const unsigned i = tid + k * CF_THREADS;
-            if (i < nvec) pre[k] = *reinterpret_cast<const f32x4*>(cf_addr(logits, G, T, i * 4));
-        }
-        if ((unsigned)tid < tail) pre_tail = *cf_addr(logits, G, T, nvec * 4 + tid);
-    };
+    CfPrefetch pre;
 
     long t = blockIdx.x;
     CfTile T = cf_tile(G, t < G.n_tiles ? t : 0);
-    if (G.vec && t < G.n_tiles) prefetch(T);
+    if (G.vec && t < G.n_tiles) cf_prefetch(pre, logits, G, T, tid);
     __syncthreads();                                 // histogram zeroed
     for (; t < G.n_tiles; t += gridDim.x) {
-        const unsigned total = (unsigned)T.nr * T.pps * C;
-        if (G.vec) {
-            const unsigned nvec = total >> 2, tail = total & 3;
-#pragma unroll
-            for (int k = 0; k < CF_VEC; ++k) {
-                const unsigned i = tid + k * CF_THREADS;
-                if (i < nvec) cf_stage4(tile, G, i * 4, pre[k]);
-            }
-            if ((unsigned)tid < tail) {
-                const unsigned e = nvec * 4 + tid, p = e / C;
-                tile[p * G.Cs + (e - p * C)] = pre_tail;
-            }
-        } else {
-            for (unsigned e = tid; e < total; e += CF_THREADS) {
-                const unsigned p = e / C;
-                tile[p * G.Cs + (e - p * C)] = *cf_addr(logits, G, T, e);
-            }
-        }
+        cf_stage(tile, pre, logits, G, T, tid);
         __syncthreads();
         const CfTile cur = T;
         const long nt = t + gridDim.x;
         if (nt < G.n_tiles) {
             T = cf_tile(G, nt);
-            if (G.vec) prefetch(T);
+            if (G.vec) cf_prefetch(pre, logits, G, T, tid);
         }
         const int npl = cur.nr * cur.pps, S = G.g * G.P, gg = G.g * G.g;
         for (int p = tid; p < npl; p += CF_THREADS) {
@@ -133,14 +55,8 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_ce_kernel(const float* _
             const int tok = (int)(row - b * gg), ty = tok / G.g, tx = tok - ty * G.g, p1 = q / G.P, p2 = q - p1 * G.P;
             const long tv = load_int(target, (b * S + (ty * G.P + p1)) * S + (tx * G.P + p2), tbytes);
             if (tv == missing || tv < 0 || tv >= C) continue;
-            // torch.argmax: the lowest index among equal maxima; a NaN is the maximum and the first NaN wins
-            const float* x = tile + p * G.Cs;
-            float best = x[0];
-            int arg = 0;
-            for (int c = 1; c < C; ++c) {
-                const float v = x[c];
-                if (v > best || (v != v && best == best)) { best = v; arg = c; }
-            }
+            float best;
+            const int arg = argmax_torch(tile + p * G.Cs, C, 1, best);
             atomicAdd(&hist[(int)tv * C + arg], 1u);
         }
         __syncthreads();
@@ -188,21 +104,7 @@ extern "C" int mh_confusion_ce(const float* logits, const void* target, int targ
                  "mh_confusion_ce: target width %d (1, 2, 4 or 8 bytes)", target_bytes);
     MH_CHECK_ARG((long)P * P * C <= (long)ld, "mh_confusion_ce: ld %d < P * P * C = %ld", ld, (long)P * P * C);
     MH_CHECK_ARG((long)g * P <= 46340 && (long)g * g <= (1L << 30), "mh_confusion_ce: raster side g * P = %ld too large", (long)g * P);
-    CfGeom G;
-    G.n_rows = (long)B * g * g;
-    G.g = g; G.P = P; G.C = C; G.Cs = C | 1; G.ld = ld; G.PP = P * P;
-    G.npt = min(CF_MAX_PIX, CF_TILE / G.Cs) & ~3;      // >= 28 (C = 128)
-    if (G.PP <= G.npt) {
-        G.rows_per_tile = G.npt / G.PP;
-        G.chunks_per_row = 1;
-        G.n_tiles = (G.n_rows + G.rows_per_tile - 1) / G.rows_per_tile;
-    } else {
-        G.rows_per_tile = 1;
-        G.chunks_per_row = (G.PP + G.npt - 1) / G.npt;
-        G.n_tiles = G.n_rows * G.chunks_per_row;
-    }
-    // 16-byte loads: every row and every chunk start on a 16-byte boundary, and a tile of several rows has whole vectors per row
-    G.vec = ((uintptr_t)logits % 16 == 0 && ld % 4 == 0 && (G.rows_per_tile == 1 || (G.PP * C) % 4 == 0)) ? 1 : 0;
+    const CfGeom G = cf_geometry(logits, (long)B * g * g, g, P, C, ld, false);
     // grid: workgroups resident at once (LDS: histogram + tile), each walking tiles blockIdx.x, + gridDim.x, ...; more of them
     // only when a workgroup would otherwise count more than CF_WG_PIXELS pixels into its 32-bit counters
     const int hw = C * C <= 1024 ? 1024 : (C * C <= 8192 ? 8192 : 16384);

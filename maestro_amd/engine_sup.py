@@ -14,6 +14,7 @@ on their second run like the pretrain engine's, groups run on parallel HIP strea
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -34,6 +35,29 @@ def ordered_parameters(m):
         ordered += [(f"encoder_inter.{k}", p) for k, p in m.encoder_inter.named_parameters()]
     head_params = [(f"heads.{t}.{k}", p) for t in m.heads for k, p in m.heads[t].named_parameters()]
     return ordered + head_params, head_params
+
+
+class Prediction(NamedTuple):
+    """One target's prediction (``SupervisedEngine.predict``): device tensors, engine-owned -- valid until the next ``predict``."""
+    cls: torch.Tensor
+    conf: torch.Tensor
+    probs: torch.Tensor | None
+
+
+def parse_views(views) -> tuple:
+    """``views`` of ``SupervisedEngine.predict`` as a tuple of dihedral flag bytes: a non-empty sequence of distinct values 0..7
+    (bit 0 flips the rows, bit 1 the columns, bit 2 then swaps the axes: ``dataset.py:224-257``), or ``"d4"`` for all eight."""
+    if isinstance(views, str):
+        if views != "d4":
+            raise ValueError(f"views={views!r}: a sequence of dihedral flags 0..7 or \"d4\"")
+        return tuple(range(8))
+    try:
+        out = tuple(views)
+    except TypeError:
+        raise ValueError(f"views={views!r}: a sequence of dihedral flags 0..7 or \"d4\"") from None
+    if not out or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 7 for v in out) or len(set(out)) != len(out):
+        raise ValueError(f"views={views!r}: a non-empty sequence of distinct dihedral flags 0..7 or \"d4\"")
+    return out
 
 
 class SupervisedEngine(EngineBase):
@@ -154,6 +178,7 @@ class SupervisedEngine(EngineBase):
         batch = self._stage_inputs(batch)
         with self._tuning_pass("forward"):
             self._segment("sup_forward", self._cur_key, lambda: self._forward_launches(batch))
+        self._saved_for_backward = True
         return self.loss_acc
 
     def _embed_encode(self, g, batch) -> None:
@@ -169,9 +194,9 @@ class SupervisedEngine(EngineBase):
         hip.layernorm_fwd(st.x_last, Lb, 0, nrm.weight, nrm.bias, dst, self.JL, self.goff[g.name], gbuf["mean_e"], gbuf["rstd_e"],
                           B, Lb, E)
 
-    def _forward_launches(self, batch: dict) -> None:
-        m, E, B, ps = self.model, self.E, self.B, self.store  # noqa: N806
-        self.loss_acc.zero_()
+    def _encode_launches(self, batch: dict) -> None:
+        """Embed + encoders (+ the joint encoder) + the token grids on the reference grid: everything in front of the heads."""
+        E, B = self.E, self.B  # noqa: N806
         self._run_parallel([lambda g=g: self._embed_encode(g, batch) for g in self.groups])
         if self.joint is not None:
             self.joint.forward()
@@ -183,44 +208,152 @@ class SupervisedEngine(EngineBase):
                 hip.token_resize(self.xenc, self.JL, self.goff[s.group] + s.tok_off, r["x"], r["TD"] * r["Lr"], d0 * r["Lr"], B,
                                  s.Dates, s.g, r["G"], E)
                 d0 += s.Dates
-        for t, hb in self.hb.items():
-            head = m.heads[t]
-            x = self.ref["x"] if hb["kind"] == "segment" else self.xenc
-            R, n = hb["R"], B * hb["Lr"]  # noqa: N806
-            if hb["attentive"]:
-                red = head.reduce
-                hip.layernorm_fwd(x, R, 0, red.norm.weight, red.norm.bias, hb["xn"], R, 0, hb["mean_n"], hb["rstd_n"], 1, R, E)
-                hip.gemm(hip.GEMM_NT, R, 2 * E, E, hb["xn"], E, ps.h(red.to_kv.weight), E, hb["kv"], 2 * E)
-                hip.attn_reduce_fwd(hb["kv"], red.query, hb["red"], hb["lse"], B, hb["T"], hb["Lr"], E, red.heads)
-                out = hb["hfc"] if hb["kind"] == "segment" else hb["h"]
-                hip.layernorm_fwd(hb["red"], n, 0, red.norm_fc.weight, red.norm_fc.bias, out, n, 0, hb["mean_f"], hb["rstd_f"], 1, n, E)
-            else:
-                hip.mean_reduce_fwd(x, hb["red"], B, hb["T"], hb["Lr"], E)
-                if hb["kind"] == "segment":
-                    hip.cast_bf16(hb["red"], hb["hfc"], n * E)
-            tgt = batch[t]
+
+    def _head_logits(self, t: str) -> None:
+        """Head ``t`` from the encoded tokens up to and including its logits buffer."""
+        m, E, B, ps = self.model, self.E, self.B, self.store  # noqa: N806
+        hb, head = self.hb[t], m.heads[t]
+        x = self.ref["x"] if hb["kind"] == "segment" else self.xenc
+        R, n = hb["R"], B * hb["Lr"]  # noqa: N806
+        if hb["attentive"]:
+            red = head.reduce
+            hip.layernorm_fwd(x, R, 0, red.norm.weight, red.norm.bias, hb["xn"], R, 0, hb["mean_n"], hb["rstd_n"], 1, R, E)
+            hip.gemm(hip.GEMM_NT, R, 2 * E, E, hb["xn"], E, ps.h(red.to_kv.weight), E, hb["kv"], 2 * E)
+            hip.attn_reduce_fwd(hb["kv"], red.query, hb["red"], hb["lse"], B, hb["T"], hb["Lr"], E, red.heads)
+            out = hb["hfc"] if hb["kind"] == "segment" else hb["h"]
+            hip.layernorm_fwd(hb["red"], n, 0, red.norm_fc.weight, red.norm_fc.bias, out, n, 0, hb["mean_f"], hb["rstd_f"], 1, n, E)
+        else:
+            hip.mean_reduce_fwd(x, hb["red"], B, hb["T"], hb["Lr"], E)
             if hb["kind"] == "segment":
-                W = hb["PPCp"]  # noqa: N806
-                if "w16p" in hb:
-                    hip.cast_bf16(head.conv.weight, hb["w16p"], hb["PPC"] * E)
-                    hb["biasp"][: hb["PPC"]].copy_(head.conv.bias)
-                    w16, bias = hb["w16p"], hb["biasp"]
-                else:
-                    w16, bias = ps.h(head.conv.weight).view(W, E), head.conv.bias
-                hip.gemm(hip.GEMM_NT, n, W, E, hb["hfc"], E, w16, E, hb["logits"], W, hip.OUT_F32 | hip.BIAS, bias=bias)
-                hb["cnt"].zero_()
-                hip.count_valid(tgt, hb["missing"], hb["cnt"])
-                hip.ce_loss(hb["logits"], tgt, hb["missing"], hb["cnt"], self.loss_acc, hb["dlogits"], B, self.ref["G"], hb["P"], hb["C"],
-                            ld=W)
+                hip.cast_bf16(hb["red"], hb["hfc"], n * E)
+        if hb["kind"] == "segment":
+            W = hb["PPCp"]  # noqa: N806
+            if "w16p" in hb:
+                hip.cast_bf16(head.conv.weight, hb["w16p"], hb["PPC"] * E)
+                hb["biasp"][: hb["PPC"]].copy_(head.conv.bias)
+                w16, bias = hb["w16p"], hb["biasp"]
             else:
-                feat = hb["h"] if hb["attentive"] else hb["red"]
-                hip.head_linear_fwd(feat, head.linear.weight, head.linear.bias, hb["logits"], B, hb["C"], E)
-                if hb["kind"] == "multilabel_classif":
-                    hip.bce_loss(hb["logits"], tgt, hb["missing"], self.loss_acc, hb["dlogits"], B, hb["C"])
-                else:
-                    hb["cnt"].zero_()
-                    hip.count_valid(tgt, hb["missing"], hb["cnt"])
-                    hip.ce_loss(hb["logits"], tgt, hb["missing"], hb["cnt"], self.loss_acc, hb["dlogits"], B, 1, 1, hb["C"])
+                w16, bias = ps.h(head.conv.weight).view(W, E), head.conv.bias
+            hip.gemm(hip.GEMM_NT, n, W, E, hb["hfc"], E, w16, E, hb["logits"], W, hip.OUT_F32 | hip.BIAS, bias=bias)
+        else:
+            feat = hb["h"] if hb["attentive"] else hb["red"]
+            hip.head_linear_fwd(feat, head.linear.weight, head.linear.bias, hb["logits"], B, hb["C"], E)
+
+    def _forward_launches(self, batch: dict) -> None:
+        B = self.B  # noqa: N806
+        self.loss_acc.zero_()
+        self._encode_launches(batch)
+        for t, hb in self.hb.items():
+            self._head_logits(t)
+            tgt = batch[t]
+            if hb["kind"] == "multilabel_classif":
+                hip.bce_loss(hb["logits"], tgt, hb["missing"], self.loss_acc, hb["dlogits"], B, hb["C"])
+                continue
+            hb["cnt"].zero_()
+            hip.count_valid(tgt, hb["missing"], hb["cnt"])
+            if hb["kind"] == "segment":
+                hip.ce_loss(hb["logits"], tgt, hb["missing"], hb["cnt"], self.loss_acc, hb["dlogits"], B, self.ref["G"], hb["P"], hb["C"],
+                            ld=hb["PPCp"])
+            else:
+                hip.ce_loss(hb["logits"], tgt, hb["missing"], hb["cnt"], self.loss_acc, hb["dlogits"], B, 1, 1, hb["C"])
+
+    # ------------------------------------------------------------------------------------------ prediction
+    def _head_geometry(self, hb) -> tuple:
+        """``(act, g, P, ld, map shape, prob shape)`` of a head's logits buffer as ``hip.predict_view`` takes it."""
+        B, C = self.B, hb["C"]  # noqa: N806
+        if hb["kind"] == "segment":
+            G, P = self.ref["G"], hb["P"]  # noqa: N806
+            return hip.PREDICT_SOFTMAX, G, P, hb["PPCp"], (B, G * P, G * P), (B, 1, C, G * P, G * P)
+        if hb["kind"] == "multilabel_classif":
+            return hip.PREDICT_SIGMOID, 1, 1, C, (B, C), (B, C)
+        return hip.PREDICT_SOFTMAX, 1, 1, C, (B,), (B, C)
+
+    def _predict_buffers(self, t: str, probs: bool) -> dict:
+        """Engine-owned outputs of ``predict`` (stable addresses for the captured segments), allocated when first needed."""
+        if not hasattr(self, "_pb"):
+            self._pb = {}
+        pb = self._pb.setdefault(t, {})
+        _, _, _, _, map_shape, prob_shape = self._head_geometry(self.hb[t])
+        if "cls" not in pb:
+            pb["cls"] = torch.empty(map_shape, dtype=torch.uint8, device=self.device)
+            pb["conf"] = torch.empty(map_shape, dtype=F32, device=self.device)
+        if probs and "prob" not in pb:
+            pb["prob"] = torch.empty(prob_shape, dtype=F32, device=self.device)
+        return pb
+
+    def _predict_view_launches(self, batch: dict, view: dict | None, mode: str, probs: bool, thr: dict) -> None:
+        """One view: the rasters under the view's flags (``view``: flag tensor and destination rasters; None = the batch as it
+        is), the forward up to every head's logits, ``mh_predict_view``.  ``mode``: "one" writes cls, conf (and prob when
+        ``probs``) at once, "first" / "acc" start / continue the accumulation in prob."""
+        flags = None
+        if view is not None:
+            flags, batch = view["flags"], dict(batch)
+            for src, dst in view["rasters"].items():
+                hip.dihedral(batch[src], dst, flags)
+                batch[src] = dst
+        self._encode_launches(batch)
+        for t, hb in self.hb.items():
+            self._head_logits(t)
+            act, g, P, ld, _, _ = self._head_geometry(hb)  # noqa: N806
+            pb = self._pb[t]
+            one = mode == "one"
+            hip.predict_view(hb["logits"], flags if act == hip.PREDICT_SOFTMAX else None, act, pb["prob"] if probs else None,
+                             mode == "acc", pb["cls"] if one else None, pb["conf"] if one else None, self.B, g, P, hb["C"], ld=ld,
+                             threshold=thr[t])
+
+    def predict(self, batch: dict, views=(0,), probs: bool = False, threshold=0.5) -> dict:
+        """Predictions ``{target: Prediction(cls, conf, probs)}`` for a batch WITHOUT labels: the rasters, their dates and
+        ``ref_date``; target keys are ignored.  Nothing is read on the host.
+
+        segment: ``cls`` u8 ``[B, S, S]`` (``torch.argmax`` of the logits), ``conf`` f32 ``[B, S, S]`` (the largest class
+        probability), ``probs`` f32 ``[B, 1, C, S, S]`` (the layout of ``logits()``) or None; classif: ``[B]``, ``[B]``,
+        ``[B, C]``; multilabel: ``cls`` u8 ``[B, C]`` = ``sigmoid > threshold`` (``threshold``: a float or ``{target: float}``,
+        the metric's ``threshold_detect``), ``conf`` = the sigmoid ``[B, C]``, ``probs`` the same values.
+
+        ``views``: dihedral flag bytes (``parse_views``; ``"d4"`` = all eight) for test-time augmentation -- every raster of the
+        batch is transformed by ``mh_dihedral`` under one flag byte per view, the class probabilities of the views are summed at
+        their places in the untransformed raster and ``cls`` / ``conf`` / ``probs`` are the arg-max, the largest mean and the mean.
+        The launch list is the forward's up to the logits and nothing after (no loss, no target count, no start-up passes); one
+        captured segment per kind of view.
+
+        The returned tensors are the engine's own buffers: the next ``predict`` overwrites them.  Weights, gradients,
+        ``loss_acc``, optimizer and metric state are untouched; the saved activations and ``logits()`` are those of the LAST
+        view, in that view's orientation, so ``backward()`` raises until the next ``forward``."""
+        views = parse_views(views)
+        ds = self.model.dataset
+        thr = {t: float(threshold[t] if isinstance(threshold, dict) else threshold) for t in self.hb}
+        if self.store.refresh_half():
+            self._pack_conv_weights()
+        batch = self._stage_inputs({k: v for k, v in batch.items() if k not in ds.targets})
+        self._saved_for_backward = False
+        direct = views == (0,)
+        need_prob = probs or len(views) > 1
+        for t in self.hb:
+            self._predict_buffers(t, need_prob)
+        view = None
+        if not direct:
+            view = getattr(self, "_pv", None)
+            if view is None:
+                sources = [parts[0] for parts in self.model.src_specs.values()]
+                view = self._pv = dict(flags=torch.zeros(self.B, dtype=torch.uint8, device=self.device),
+                                       rasters={s.src: torch.empty_like(batch[s.src]) for s in sources})
+        key = (self._cur_key, probs, tuple(sorted(thr.items())))
+        for i, v in enumerate(views):
+            mode = "one" if len(views) == 1 else ("first" if i == 0 else "acc")
+            if view is not None:
+                view["flags"].fill_(v)       # in front of the segment: a replayed graph reads the flags of THIS view
+            name = f"sup_predict:{'direct' if direct else mode}"
+            self._segment(name, key, lambda mode=mode: self._predict_view_launches(batch, view, mode, need_prob, thr))
+        out = {}
+        for t, hb in self.hb.items():
+            act, _, _, _, _, _ = self._head_geometry(hb)
+            pb = self._pb[t]
+            if len(views) > 1:
+                C = hb["C"]  # noqa: N806
+                hip.predict_finish(pb["prob"], len(views), act, pb["cls"], pb["conf"], self.B, C, pb["prob"].numel() // (self.B * C),
+                                   threshold=thr[t], mean=pb["prob"] if probs else None)
+            out[t] = Prediction(pb["cls"], pb["conf"], pb["prob"] if probs else None)
+        return out
 
     # ------------------------------------------------------------------------------------------ backward
     def zero_grad(self) -> None:
@@ -230,6 +363,8 @@ class SupervisedEngine(EngineBase):
         """Backward of the last ``forward`` (d loss = 1) into the flat grad buffer (zero it first).  probe: heads only."""
         if grad_scale != 1.0:
             raise NotImplementedError("loss scaling is not needed for bf16")
+        if not getattr(self, "_saved_for_backward", True):
+            raise RuntimeError("backward() after predict(): the saved activations are a prediction view's; run forward() first")
         key = getattr(self, "_cur_key", None)
         with self._tuning_pass("backward"):
             self._segment(f"sup_bwd_heads:{self.phase}", key, self._bwd_heads)
@@ -398,7 +533,8 @@ class SupervisedEngine(EngineBase):
 
     # ------------------------------------------------------------------------------------------ outputs
     def logits(self) -> dict:
-        """Logits in the reference's layout: raster targets ``[B, 1, C, S, S]`` (head.py:116-130), others ``[B, C]``."""
+        """Logits in the reference's layout: raster targets ``[B, 1, C, S, S]`` (head.py:116-130), others ``[B, C]``.  After
+        ``predict`` they are those of its LAST view, in that view's orientation (not moved back to the untransformed raster)."""
         out = {}
         for t, hb in self.hb.items():
             if hb["kind"] == "segment":
@@ -430,11 +566,9 @@ class SupervisedEngine(EngineBase):
 
     def logged_class_map(self, t: str) -> torch.Tensor:
         """Arg-max class map ``[S, S]`` of sample 0 of a raster target (the image logs of ``base.py:58-96`` keep only that
-        sample): depatchifies that sample's g x g tokens only."""
+        sample): ``mh_predict_view`` on that sample's g x g token rows of the logits buffer."""
         hb = self.hb[t]
         G, S = self.ref["G"], self.ref["G"] * hb["P"]  # noqa: N806
-        img = torch.empty(1, hb["C"], S, S, dtype=F32, device=self.device)
-        lg = hb["logits"][: G * G]
-        lg = lg if hb["PPCp"] == hb["PPC"] else lg[:, : hb["PPC"]].contiguous()
-        hip.depatchify(lg, img, 1, hb["C"], S, hb["P"])
-        return img[0].argmax(dim=0)
+        cls = torch.empty(1, S, S, dtype=torch.uint8, device=self.device)
+        hip.predict_view(hb["logits"][: G * G], None, hip.PREDICT_SOFTMAX, None, False, cls, None, 1, G, hb["P"], hb["C"], ld=hb["PPCp"])
+        return cls[0].long()

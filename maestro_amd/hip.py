@@ -46,6 +46,9 @@ def lib() -> ctypes.CDLL:
         _lib.mh_confusion_ce.argtypes = [vp, vp, ci, ctypes.c_long, vp, ci, ci, ci, ci, ci, vp]
         _lib.mh_confusion_bce.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp, ci, ci, vp]
         _lib.mh_confusion_ce.restype = _lib.mh_confusion_bce.restype = ci
+        _lib.mh_predict_view.argtypes = [vp, vp, ci, ctypes.c_float, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]     # csrc/predict_abi.hpp
+        _lib.mh_predict_finish.argtypes = [vp, ctypes.c_float, ci, ctypes.c_float, vp, vp, vp, ci, ci, ctypes.c_long, vp]
+        _lib.mh_predict_view.restype = _lib.mh_predict_finish.restype = ci
         _lib.mh_reduce_ordered.argtypes = [vp, vp, ci, vp, ci, vp]          # deterministic forms
         _lib.mh_colsum_partial_rows.argtypes = [ci]
         _lib.mh_masked_loss_partial_size.argtypes = _lib.mh_embed_bwd_partial_rows.argtypes = [ci, ci]
@@ -1084,6 +1087,111 @@ def confusion_bce(logits, target, missing_val, threshold, cm, B, C):  # noqa: N8
     if cm.dtype != torch.int64 or cm.numel() != C * 4 or not cm.is_contiguous():
         raise HipExtensionError(f"confusion_bce: cm must be a contiguous int64 [{C}, 2, 2] tensor")
     call("mh_confusion_bce", logits, target, _F(float(missing_val)), _F(logit_threshold(threshold)), cm, _I(B), _I(C))
+
+
+# ---- predictions (csrc/predict.hip, declarations in csrc/predict_abi.hpp)
+PREDICT_SOFTMAX, PREDICT_SIGMOID = 0, 1
+
+
+def _predict_out(what, name, t, dtype, numel):
+    if t is not None and (t.dtype != dtype or t.numel() != numel or not t.is_contiguous()):
+        raise HipExtensionError(f"{what}: {name} must be a contiguous {str(dtype).split('.')[-1]} tensor of {numel} elements")
+
+
+def predict_view(logits, flags, act, prob, accumulate, cls, conf, B, g, P, C, ld=None, threshold=0.5):  # noqa: N803
+    """One view of the batch from the head logits (f32 patch layout ``[B * g * g, ld >= P * P * C]``, the operand of ``ce_loss``).
+
+    ``act = PREDICT_SOFTMAX``: ``prob`` f32 ``[B, C, S, S]`` (+)= the class probabilities, ``cls`` u8 ``[B, S, S]`` = ``torch.argmax``
+    of the logits, ``conf`` f32 ``[B, S, S]`` = the largest probability, each pixel written where the ``mh_dihedral`` flag byte
+    ``flags[b]`` (u8 ``[B]``; ``None`` = identity) took it from (``predict_pixel_map``).  ``act = PREDICT_SIGMOID`` (``g = P = 1``):
+    ``prob`` / ``conf`` ``[B, C]`` = the sigmoid, ``cls`` = ``sigmoid > threshold``, decided on the logit as ``confusion_bce`` does.
+    Any of ``prob``, ``cls``, ``conf`` may be ``None``, not all three."""
+    ld = P * P * C if ld is None else ld
+    if logits.dtype != torch.float32 or logits.stride(-1) != 1:
+        raise HipExtensionError("predict_view: logits must be float32 with unit column stride")
+    if logits.dim() == 2 and (logits.shape[0] != B * g * g or (logits.shape[0] > 1 and logits.stride(0) != ld)):
+        raise HipExtensionError(f"predict_view: logits must be [{B * g * g}, >= {P * P * C}] with row stride ld = {ld}")
+    n_map = B * C if act == PREDICT_SIGMOID else B * g * P * g * P
+    _predict_out("predict_view", "prob", prob, torch.float32, B * C * g * P * g * P)
+    _predict_out("predict_view", "cls", cls, torch.uint8, n_map)
+    _predict_out("predict_view", "conf", conf, torch.float32, n_map)
+    _predict_out("predict_view", "flags", flags, torch.uint8, B)
+    thr = logit_threshold(threshold) if act == PREDICT_SIGMOID else 0.0
+    call("mh_predict_view", logits, flags, _I(act), _F(thr), prob, _I(1 if accumulate else 0), cls, conf, _I(B), _I(g), _I(P), _I(C),
+         _I(ld))
+
+
+def predict_finish(prob, n_views, act, cls, conf, B, C, n_pix, threshold=0.5, mean=None):  # noqa: N803
+    """After ``n_views`` accumulated ``predict_view`` calls on ``prob`` ``[B, C, n_pix]``: softmax -- ``cls`` = arg-max over the classes
+    (the rule of ``torch.argmax``), ``conf`` = the largest sum times ``fl(1 / n_views)``; sigmoid (``n_pix = 1``) -- ``conf`` = the sum
+    times ``fl(1 / n_views)``, ``cls`` = ``conf > threshold``.  ``mean`` (the shape of ``prob``, or ``prob`` itself) = ``prob`` times
+    ``fl(1 / n_views)``: the mean probabilities."""
+    if n_views < 1:
+        raise ValueError(f"predict_finish: {n_views} views")
+    n_map = B * C if act == PREDICT_SIGMOID else B * n_pix
+    _predict_out("predict_finish", "prob", prob, torch.float32, B * C * n_pix)
+    _predict_out("predict_finish", "cls", cls, torch.uint8, n_map)
+    _predict_out("predict_finish", "conf", conf, torch.float32, n_map)
+    _predict_out("predict_finish", "mean", mean, torch.float32, B * C * n_pix)
+    call("mh_predict_finish", prob, _F(1.0 / n_views), _I(act), _F(float(threshold)), cls, conf, mean, _I(B), _I(C), _L(n_pix))
+
+
+def predict_pixel_map(flag: int, S: int):  # noqa: N803
+    """``(y0, x0)``, two int ``[S, S]`` numpy arrays: where pixel ``(y, x)`` of a view made with dihedral flag byte ``flag`` (bit 0
+    flipped the rows, bit 1 the columns, bit 2 then swapped the axes: ``dataset.py:224-257``) lies in the untransformed raster."""
+    import numpy as np
+    y, x = np.meshgrid(np.arange(S), np.arange(S), indexing="ij")
+    y0, x0 = (x, y) if flag & 4 else (y, x)
+    if flag & 2:
+        x0 = S - 1 - x0
+    if flag & 1:
+        y0 = S - 1 - y0
+    return y0, x0
+
+
+def argmax_reference(x, axis: int):
+    """``torch.argmax`` as the kernels state it, in numpy: the lowest index among equal maxima; a NaN is the maximum and the first NaN
+    wins."""
+    import numpy as np
+    nan = np.isnan(x)
+    return np.where(nan.any(axis=axis), nan.argmax(axis=axis), np.where(nan, -np.inf, x).argmax(axis=axis)).astype(np.uint8)
+
+
+def predict_reference(logits, flags, act, *, g=1, P=1, C=None, threshold=0.5, prob=None, dtype=None):  # noqa: N803
+    """``predict_view`` restated in numpy (no GPU): the layout walk, the inverse dihedral map, the arg-max rule and the formulas, in
+    fp32 (or ``dtype=np.float64``: the reference the kernels' rounding is bounded against).  ``logits``: array ``[B * g * g, >= P * P * C]``
+    (further columns are padding and ignored); ``flags``: ``B`` flag bytes or ``None``; ``prob``: an earlier sum to accumulate onto.
+    Returns ``(prob, cls, conf)`` shaped as the kernel writes them (``[B, C, S, S]``, ``[B, S, S]``, ``[B, S, S]``; sigmoid: ``[B, C]``)."""
+    import numpy as np
+    dtype = np.float32 if dtype is None else dtype
+    logits = np.asarray(logits)
+    C = logits.shape[1] if C is None else C  # noqa: N806
+    S, rows = g * P, logits.shape[0]  # noqa: N806
+    B = rows // (g * g)  # noqa: N806
+    if act == PREDICT_SIGMOID:
+        if g != 1 or P != 1:
+            raise ValueError("predict_reference: the sigmoid is for classification heads (g = P = 1)")
+        x = logits[:, :C].astype(np.float32)
+        with np.errstate(over="ignore"):
+            p = (1 / (1 + np.exp(-x.astype(dtype)))).astype(dtype)
+        cls = (x > np.float32(logit_threshold(threshold))).astype(np.uint8)
+        return (p if prob is None else (prob + p).astype(dtype)), cls, p
+    if rows != B * g * g or logits.shape[1] < P * P * C:
+        raise ValueError(f"predict_reference: logits {logits.shape} for g = {g}, P = {P}, C = {C}")
+    # column (p1 * P + p2) * C + c of token row (b * g + ty) * g + tx  ->  view raster [B, C, ty * P + p1, tx * P + p2]
+    view = logits[:, : P * P * C].astype(np.float32).reshape(B, g, g, P, P, C).transpose(0, 5, 1, 3, 2, 4).reshape(B, C, S, S)
+    raster = np.empty_like(view)
+    for b in range(B):
+        y0, x0 = predict_pixel_map(0 if flags is None else int(flags[b]), S)
+        raster[b][:, y0, x0] = view[b]
+    cls = argmax_reference(raster, 1)
+    x = raster.astype(dtype)
+    with np.errstate(invalid="ignore"):
+        e = np.exp(x - x.max(axis=1, keepdims=True)).astype(dtype)      # (a NaN pixel is NaN throughout, as on the device)
+        s = e.sum(axis=1, dtype=dtype)
+        p = (e * (1 / s)[:, None]).astype(dtype) if dtype == np.float32 else e / s[:, None]
+        conf = (1 / s).astype(dtype)
+    return (p if prob is None else (prob + p).astype(dtype)), cls, conf
 
 
 def zero_spans(base, spans, n_spans, max_len):

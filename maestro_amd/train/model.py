@@ -480,6 +480,24 @@ class SSLModule(_Base):
     def test_step(self, batch: dict, batch_idx: int) -> dict:  # noqa: ARG002
         return self.shared_step(batch, stage="test")
 
+    predict_views = (0,)     # dihedral views of ``predict_step`` (``SupervisedEngine.predict``): flag bytes 0..7, or "d4"
+
+    def predict_step(self, batch: dict, batch_idx: int) -> dict:  # noqa: ARG002
+        """Lightning's prediction hook (the reference defines none): ``{target: Prediction(cls, conf, probs)}`` of
+        ``SupervisedEngine.predict`` under ``self.predict_views`` for a batch without labels, every multilabel target thresholded
+        at its metric's ``threshold_detect``.  Finetune with ``use_ema`` predicts with the EMA weights, swapped in as
+        ``probe_or_finetune_step`` does for val / test.  Probe / finetune only."""
+        phase = self._ssl_phase()
+        if phase not in ("probe", "finetune"):
+            raise ValueError(f"predict_step needs ssl phase 'probe' or 'finetune' (got {phase!r}): a pretrained model has no heads")
+        first = next(iter(self.dataset.inputs))
+        engine = self.model.sup_engine(batch[first].shape[0], batch[first].device, phase)
+        thr = {t: getattr(self.metrics[f"{t}_test"], "threshold_detect", 0.5) if f"{t}_test" in self.metrics else 0.5 for t in engine.hb}
+        if phase == "finetune" and self.ema_model is not None:
+            with engine.store.swapped(self._ema_flat(engine), engine._pack_conv_weights):
+                return engine.predict(batch, views=self.predict_views, threshold=thr)
+        return engine.predict(batch, views=self.predict_views, threshold=thr)
+
     def on_train_epoch_end(self) -> None:
         if self.ema_model is not None:
             self.update_ema()

@@ -315,6 +315,10 @@ class SupervisedLoop(_GuardSurface):
             return self.engine.loss_acc
         return self.engine.store.extra[:1] / self.sync.world
 
+    def predict(self, batch: dict, views=(0,), probs: bool = False, threshold=0.5) -> dict:
+        """``SupervisedEngine.predict`` with the loop's current weights (a batch without labels; no optimizer state moves)."""
+        return self.engine.predict(batch, views=views, probs=probs, threshold=threshold)
+
     def step(self, batch: dict) -> torch.Tensor:
         eng = self.engine
         loss = eng.forward(batch)
