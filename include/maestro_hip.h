@@ -348,7 +348,8 @@ int mh_embed_finish(const float* y, const float* stats, const float* gamma, cons
                     const float* date, int date_rows, int date_off, float* xg, int B, int D, int L, int E, int tok_off,
                     int Lgroup, void* stream);
 /* Backward of the above w.r.t. the conv output: dyc bf16 [B*D*L, E] (A operand of the patch-embed wgrad GEMM);
- * dgamma/dbeta atomically accumulated; sums: f32 workspace [B*D, 2]. */
+ * dgamma/dbeta atomically accumulated; sums: f32 workspace [B*D, 2].  Sizes positive, E % 4 == 0 (any width; above 1024
+ * in column passes), 0 <= tok_off, tok_off + D * L <= Lgroup -- the same checks in the two forms below. */
 int mh_embed_finish_bwd(const float* dxg, const float* y, const float* stats, const float* gamma, void* dyc,
                         float* dgamma, float* dbeta, float* sums, int B, int D, int L, int E, int tok_off, int Lgroup,
                         void* stream);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -36,6 +37,10 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {   // ONE v_cvt_pk_bf16_f32 (round-to-nearest-even)
     const f32x2 v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ f32x4 bf2x2_to_f32x4(uint32_t a, uint32_t b) {   // 4 bf16 (two packed words) -> 4 floats
+    return (f32x4){__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u), __uint_as_float(b << 16),
+                   __uint_as_float(b & 0xffff0000u)};
 }
 
 // ----------------------------------------------------------------------------- wave / block reductions
@@ -79,6 +84,20 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 #pragma unroll
     for (int i = 0; i < NW; ++i) t += red[i];
     return t;
+}
+
+// ----------------------------------------------------------------------------- rows of up to 1024 columns, 256-thread blocks
+// The row kernels that keep a row's columns in registers: lane l owns columns 4 l + 256 j .. + 3 for j < NV = ceil(ncols / 256).
+// f(std::integral_constant<int, NV>) for NV = 1 .. 4: the one place that turns such a width into a template argument (a wider row
+// gets NV = 4: the callers either refuse it or walk it in passes of 1024 columns).
+template <class F>
+static void for_row_nv(int ncols, F&& f) {
+    switch ((ncols + 255) / 256) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
 }
 
 // GELU (exact-erf form of nn.GELU) and its derivative with erf from Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7, far

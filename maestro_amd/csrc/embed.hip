@@ -262,45 +262,53 @@ __global__ __launch_bounds__(256) void embed_finish_kernel(const float* __restri
     }
 }
 
-// ---- backward pass 1: per image S1 = sum(dz), S2 = sum(dz*z); dgamma/dbeta (atomic). ROWS tokens per wave.
-constexpr int EB_ROWS = 8;
-// NV = ceil(E / 256) four-column chunks per lane (round 6): a lane owns the same columns in every row, so the dgamma / dbeta partial sums
-// of its EB_ROWS rows stay in registers and touch LDS once at the end (they used to be read-modify-written in LDS for every element:
-// two LDS round trips per element in a kernel that streams 8 bytes per element from HBM).  NV = 0: any E (the LDS form).
+// ---- GroupNorm backward of the patch embed, two passes (launch_embed_bwd).  Both keep a row's columns in registers: NV =
+// ceil(E / 256) four-column chunks per lane, a lane owns the same columns in every row of its wave.
+// WIDE (E > 1024, the plain and deterministic entry points only; no model size is that wide): the same body once per pass of
+// 256 NV = 1024 columns.
+// MAP (mh_embed_finish_bwd_ends): dxg is the gradient of the VISIBLE rows [B, n_vis, E] and inv [B, Lgroup] maps a group position
+// to its visible row (< 0: masked = a zero gradient).
+
+// ---- pass 1: per image S1 = sum(dz), S2 = sum(dz*z); dgamma/dbeta (atomic). EB_ROWS tokens per wave.
+// The dgamma / dbeta partial sums of a wave's EB_ROWS rows stay in registers and touch LDS once at the end (round 6; they used to be
+// read-modify-written in LDS for every element: two LDS round trips per element in a kernel that streams 8 bytes per element from
+// HBM).  WIDE: a lane adds its S1 / S2 terms pass by pass, i.e. columns outermost; the per-column sums keep their order.
 // DET (deterministic mode, mh_embed_finish_bwd_det): no atomics -- the block writes its (S1, S2) to sums[bd, blockIdx.x, 2] and its
 // dgamma | dbeta row to dgamma[(bd * gridDim.x + blockIdx.x), 2 E] (dbeta unused); LDS then carries 8 more floats for the waves' sums.
-// MAP (mh_embed_finish_bwd_ends, NV > 0 only): dxg is the gradient of the VISIBLE rows [B, n_vis, E] and inv [B, Lgroup] maps a group
-// position to its visible row (< 0: masked = a zero gradient).  A masked row adds nothing to any of the sums: the wave skips it
-// (the branch is wave-uniform) and issues none of its loads.
-template <int NV, bool DET, bool MAP = false>
+// MAP: a masked row adds nothing to any of the sums: the wave skips it (the branch is wave-uniform) and issues none of its loads.
+constexpr int EB_ROWS = 8;
+template <int NV, bool DET, bool MAP, bool WIDE = false>
 __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __restrict__ dxg, const float* __restrict__ y,
                                                               const float* __restrict__ stats, const float* __restrict__ gamma,
                                                               float* __restrict__ sums, float* __restrict__ dgamma,
                                                               float* __restrict__ dbeta, int B, int D, int L, int E,
-                                                              int tok_off, int Lgroup, const int* __restrict__ inv = nullptr,
-                                                              int n_vis = 0) {
-    static_assert(!MAP || NV > 0, "the position-map form keeps its sums in registers");
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [4][2][E]
+                                                              int tok_off, int Lgroup, const int* __restrict__ inv, int n_vis) {
+    static_assert(!WIDE || (NV == 4 && !MAP), "column passes: full-width ones, without the position map");
+    extern __shared__ __attribute__((aligned(16))) float red[];  // [4][2][P]; DET: + the waves' [4][2] (S1, S2)
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int bd = blockIdx.y, b = bd / D, d = bd - b * D;
     const float mu = stats[bd * 2], rs = stats[bd * 2 + 1];
-    float* rg = red + (size_t)w * 2 * E;
+    const int P = WIDE ? 256 * NV : E;           // a pass's columns = the pitch of the LDS rows
+    float* rg = red + (size_t)w * 2 * P;         // (a fixed pitch, so that this stays in front of the loop: the !WIDE forms then compile
+                                                 //  to the instructions they had without it)
     float s1 = 0.f, s2 = 0.f;
     const int l0 = (blockIdx.x * 4 + w) * EB_ROWS;
-    if constexpr (NV > 0) {
+    int c0 = 0;
+    do {                                         // columns c0 .. c0 + W of every row; !WIDE: the one pass, W = E
+        const int W = WIDE ? min(E - c0, P) : E;
         f32x4 gz[NV], gd[NV], gm[NV];
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int c = lane * 4 + 256 * j;
             gz[j] = (f32x4){0, 0, 0, 0}; gd[j] = (f32x4){0, 0, 0, 0};
-            gm[j] = c < E ? *reinterpret_cast<const f32x4*>(gamma + c) : (f32x4){0, 0, 0, 0};
+            gm[j] = c < W ? *reinterpret_cast<const f32x4*>(gamma + c0 + c) : (f32x4){0, 0, 0, 0};
         }
 #pragma unroll 2
         for (int rr = 0; rr < EB_ROWS; ++rr) {
             const int l = l0 + rr;
             if (l >= L) break;
-            const float* yr = y + ((size_t)bd * L + l) * E;
-            const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
+            const float* yr = y + ((size_t)bd * L + l) * E + c0;
+            const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E + c0;
             if constexpr (MAP) {
                 const int iv = inv[(size_t)b * Lgroup + tok_off + d * L + l];
                 if (iv < 0) continue;
@@ -309,7 +317,7 @@ __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __res
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 const int c = lane * 4 + 256 * j;
-                if (c < E) {
+                if (c < W) {
                     const f32x4 v = *reinterpret_cast<const f32x4*>(yr + c);
                     const f32x4 dd = *reinterpret_cast<const f32x4*>(gr + c);
 #pragma unroll
@@ -325,50 +333,35 @@ __global__ __launch_bounds__(256) void embed_bwd_stats_kernel(const float* __res
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int c = lane * 4 + 256 * j;
-            if (c < E) {
+            if (c < W) {
                 *reinterpret_cast<f32x4*>(rg + c) = gz[j];
-                *reinterpret_cast<f32x4*>(rg + E + c) = gd[j];
+                *reinterpret_cast<f32x4*>(rg + P + c) = gd[j];
             }
         }
-    } else {
-        for (int c = lane; c < 2 * E; c += 64) rg[c] = 0.f;
-        for (int rr = 0; rr < EB_ROWS; ++rr) {
-            const int l = l0 + rr;
-            if (l >= L) break;
-            const float* yr = y + ((size_t)bd * L + l) * E;
-            const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
-            for (int c = lane * 4; c < E; c += 256) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(yr + c);
-                const f32x4 dd = *reinterpret_cast<const f32x4*>(gr + c);
-                const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float z = (v[e] - mu) * rs, dz = dd[e] * gm[e];
-                    s1 += dz; s2 += dz * z;
-                    rg[c + e] += dd[e] * z;       // lane-private columns: no race inside the wave
-                    rg[E + c + e] += dd[e];
-                }
+        if (!WIDE || c0 + 256 * NV >= E) {       // the last pass: the lane's S1, S2 are complete
+            s1 = wave_sum(s1); s2 = wave_sum(s2);
+            if constexpr (DET) {
+                if (lane == 0) { red[8 * P + 2 * w] = s1; red[8 * P + 2 * w + 1] = s2; }
+            } else {
+            if (lane == 0) { atomicAdd(sums + bd * 2, s1); atomicAdd(sums + bd * 2 + 1, s2); }
             }
         }
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    if constexpr (DET) {
-        if (lane == 0) { red[8 * E + 2 * w] = s1; red[8 * E + 2 * w + 1] = s2; }
-    } else {
-    if (lane == 0) { atomicAdd(sums + bd * 2, s1); atomicAdd(sums + bd * 2 + 1, s2); }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < 2 * E; c += 256) {
-        const float t = red[c] + red[2 * E + c] + red[4 * E + c] + red[6 * E + c];
-        if constexpr (DET) {
-            dgamma[((size_t)bd * gridDim.x + blockIdx.x) * 2 * E + c] = t;
-        } else {
-        if (c < E) atomicAdd(dgamma + c, t); else atomicAdd(dbeta + (c - E), t);
+        __syncthreads();
+        for (int c = threadIdx.x; c < 2 * W; c += 256) {
+            const int i = WIDE && c >= W ? P + (c - W) : c;                  // of a wave's dgamma[0 .. P) | dbeta[0 .. P) in LDS
+            const float t = red[i] + red[2 * P + i] + red[4 * P + i] + red[6 * P + i];
+            const int col = WIDE ? c0 + (c < W ? c : E + (c - W)) : c;      // of the row dgamma[0 .. E) | dbeta[0 .. E)
+            if constexpr (DET) {
+                dgamma[((size_t)bd * gridDim.x + blockIdx.x) * 2 * E + col] = t;
+            } else {
+            if (col < E) atomicAdd(dgamma + col, t); else atomicAdd(dbeta + (col - E), t);
+            }
         }
-    }
+        if constexpr (WIDE) __syncthreads();     // (the next pass overwrites the waves' rows)
+    } while (WIDE && (c0 += 256 * NV) < E);
     if constexpr (DET) {
         if (threadIdx.x < 2) {
-            const float* ws = red + 8 * E + threadIdx.x;
+            const float* ws = red + 8 * P + threadIdx.x;
             sums[((size_t)bd * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = ((ws[0] + ws[2]) + ws[4]) + ws[6];
         }
     }
@@ -385,99 +378,80 @@ __global__ __launch_bounds__(256) void zero_f32_kernel(float* __restrict__ p, in
     if (i < n) p[i] = 0.f;
 }
 
-// ---- backward pass 2: dy = rstd * (dz - S1/n - z*S2/n) as bf16 (A operand of the patch-embed wgrad GEMM)
-__global__ __launch_bounds__(256) void embed_bwd_apply_kernel(const float* __restrict__ dxg, const float* __restrict__ y,
-                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                              const float* __restrict__ sums, bf16_t* __restrict__ dyc,
-                                                              int B, int D, int L, int E, int tok_off, int Lgroup) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= B * D * L) return;
-    const int bd = row / L, l = row - bd * L, b = bd / D, d = bd - b * D;
-    const float mu = stats[bd * 2], rs = stats[bd * 2 + 1];
-    const float n = (float)L * (float)E;
-    const float c1 = sums[bd * 2] / n, c2 = sums[bd * 2 + 1] / n;
-    const float* yr = y + (size_t)row * E;
-    const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
-    bf16_t* o = dyc + (size_t)row * E;
-    for (int c = lane * 4; c < E; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(yr + c);
-        const f32x4 dd = *reinterpret_cast<const f32x4*>(gr + c);
-        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c);
-        float r[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float z = (v[e] - mu) * rs;
-            r[e] = rs * (dd[e] * gm[e] - c1 - z * c2);
-        }
-        u32x2 pk = {pack_bf2(r[0], r[1]), pack_bf2(r[2], r[3])};
-        *reinterpret_cast<u32x2*>(o + c) = pk;
-    }
-}
-
-// ---- backward pass 2 with the conv bias gradient (mh_embed_finish_bwd_ends): the same arithmetic per element, EA_ROWS rows per wave, so
-// that a lane owns the same columns in every row and the column sums of the bf16 values it stores stay in registers; the block's four
-// waves meet in LDS and store one partial row.  MAP: the gradient through the position map (see embed_bwd_stats_kernel); a masked
-// row is a zero gradient -- its dyc row still depends on yconv -- and its gradient loads are skipped.
+// ---- pass 2: dy = rstd * (dz - S1/n - z*S2/n) as bf16 (A operand of the patch-embed wgrad GEMM).
+// Rows per wave: EA_ROWS where the column sums want them, one otherwise -- with eight, the plain and deterministic calls took 1 - 5 us
+// longer at all three shapes of scripts/bench_embed_bwd.py (profiles/embed_bwd_unify.md: fewer, fatter workgroups for a pass that
+// only streams).
+// CS (mh_embed_finish_bwd_ends): with the conv bias gradient -- the column sums of the bf16 values a lane stores stay in its
+// registers; the block's four waves meet in LDS and store one partial row.
+// MAP: a masked row is a zero gradient -- its dyc row still depends on yconv -- and its gradient loads are skipped.
 constexpr int EA_ROWS = 8;
-template <int NV, bool MAP>
-__global__ __launch_bounds__(256) void embed_bwd_apply_cs_kernel(const float* __restrict__ dxg, const int* __restrict__ inv, int n_vis,
-                                                                 const float* __restrict__ y, const float* __restrict__ stats,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ sums,
-                                                                 bf16_t* __restrict__ dyc, float* __restrict__ cs_partial,
-                                                                 int B, int D, int L, int E, int tok_off, int Lgroup) {
-    __shared__ f32x4 red[4][64 * NV];
+template <int NV, bool MAP, bool CS, bool WIDE = false>
+__global__ __launch_bounds__(256) void embed_bwd_apply_kernel(const float* __restrict__ dxg, const int* __restrict__ inv, int n_vis,
+                                                              const float* __restrict__ y, const float* __restrict__ stats,
+                                                              const float* __restrict__ gamma, const float* __restrict__ sums,
+                                                              bf16_t* __restrict__ dyc, float* __restrict__ cs_partial,
+                                                              int B, int D, int L, int E, int tok_off, int Lgroup) {
+    static_assert(!WIDE || (NV == 4 && !MAP && !CS), "column passes: full-width ones, without the position map or the column sums");
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long rows = (long)B * D * L, row0 = ((long)blockIdx.x * 4 + w) * EA_ROWS;
+    constexpr int ROWS = CS ? EA_ROWS : 1;
+    const long rows = (long)B * D * L, row0 = ((long)blockIdx.x * 4 + w) * ROWS;
     const float n = (float)L * (float)E;
-    f32x4 gm[NV], cs[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int c = lane * 4 + 256 * j;
-        cs[j] = (f32x4){0, 0, 0, 0};
-        gm[j] = c < E ? *reinterpret_cast<const f32x4*>(gamma + c) : (f32x4){0, 0, 0, 0};
-    }
-#pragma unroll 2
-    for (int rr = 0; rr < EA_ROWS; ++rr) {
-        const long row = row0 + rr;
-        if (row >= rows) break;
-        const int bd = (int)(row / L), l = (int)(row - (long)bd * L), b = bd / D, d = bd - b * D;
-        const float mu = stats[bd * 2], rs = stats[bd * 2 + 1];
-        const float c1 = sums[bd * 2] / n, c2 = sums[bd * 2 + 1] / n;
-        const float* yr = y + (size_t)row * E;
-        const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
-        bool vis = true;
-        if constexpr (MAP) {
-            const int iv = inv[(size_t)b * Lgroup + tok_off + d * L + l];
-            vis = iv >= 0;
-            gr = dxg + ((size_t)b * n_vis + (vis ? iv : 0)) * E;
-        }
-        bf16_t* o = dyc + (size_t)row * E;
+    f32x4 cs[NV];
+    int c0 = 0;
+    do {                                         // columns c0 .. of every row; !WIDE: the one pass
+        f32x4 gm[NV];
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            const int c = lane * 4 + 256 * j;
-            if (c < E) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(yr + c);
-                f32x4 dd = {0.f, 0.f, 0.f, 0.f};
-                if (vis) dd = *reinterpret_cast<const f32x4*>(gr + c);
-                float r[4];
+            const int c = c0 + lane * 4 + 256 * j;
+            cs[j] = (f32x4){0, 0, 0, 0};
+            gm[j] = c < E ? *reinterpret_cast<const f32x4*>(gamma + c) : (f32x4){0, 0, 0, 0};
+        }
+#pragma unroll 2
+        for (int rr = 0; rr < ROWS; ++rr) {
+            const long row = row0 + rr;
+            if (row >= rows) break;
+            const int bd = (int)(row / L), l = (int)(row - (long)bd * L), b = bd / D, d = bd - b * D;
+            const float mu = stats[bd * 2], rs = stats[bd * 2 + 1];
+            const float c1 = sums[bd * 2] / n, c2 = sums[bd * 2 + 1] / n;
+            const float* yr = y + (size_t)row * E;
+            const float* gr = dxg + ((size_t)b * Lgroup + tok_off + d * L + l) * E;
+            bool vis = true;
+            if constexpr (MAP) {
+                const int iv = inv[(size_t)b * Lgroup + tok_off + d * L + l];
+                vis = iv >= 0;
+                gr = dxg + ((size_t)b * n_vis + (vis ? iv : 0)) * E;
+            }
+            bf16_t* o = dyc + (size_t)row * E;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float z = (v[e] - mu) * rs;
-                    r[e] = rs * (dd[e] * gm[j][e] - c1 - z * c2);
+            for (int j = 0; j < NV; ++j) {
+                const int c = c0 + lane * 4 + 256 * j;
+                if (c < E) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(yr + c);
+                    f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+                    if (vis) dd = *reinterpret_cast<const f32x4*>(gr + c);
+                    float r[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float z = (v[e] - mu) * rs;
+                        r[e] = rs * (dd[e] * gm[j][e] - c1 - z * c2);
+                    }
+                    const u32x2 pk = {pack_bf2(r[0], r[1]), pack_bf2(r[2], r[3])};
+                    *reinterpret_cast<u32x2*>(o + c) = pk;
+                    if constexpr (CS) cs[j] += bf2x2_to_f32x4(pk[0], pk[1]);
                 }
-                const u32x2 pk = {pack_bf2(r[0], r[1]), pack_bf2(r[2], r[3])};
-                *reinterpret_cast<u32x2*>(o + c) = pk;
-                cs[j] += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                 __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
             }
         }
-    }
+    } while (WIDE && (c0 += 256 * NV) < E);
+    if constexpr (CS) {     // (the tail of mask.hip's gather_rows_bf16_cs_kernel: see the note there)
+        __shared__ f32x4 red[4][64 * NV];
 #pragma unroll
-    for (int j = 0; j < NV; ++j) red[w][lane + 64 * j] = cs[j];
-    __syncthreads();
-    const float* cr = reinterpret_cast<const float*>(red);
-    for (int c = threadIdx.x; c < E; c += 256)
-        cs_partial[(size_t)blockIdx.x * E + c] = (cr[c] + cr[256 * NV + c]) + (cr[512 * NV + c] + cr[768 * NV + c]);
+        for (int j = 0; j < NV; ++j) red[w][lane + 64 * j] = cs[j];
+        __syncthreads();
+        const float* cr = reinterpret_cast<const float*>(red);
+        for (int c = threadIdx.x; c < E; c += 256)
+            cs_partial[(size_t)blockIdx.x * E + c] = (cr[c] + cr[256 * NV + c]) + (cr[512 * NV + c] + cr[768 * NV + c]);
+    }
 }
 
 // ---- patch layout -> image layout
@@ -706,32 +680,58 @@ extern "C" int mh_embed_finish(const float* y, const float* stats, const float* 
     return 0;
 }
 
+// Host side of the three GroupNorm-backward entries: the shared size checks, the width dispatch, the grids, the LDS size and the
+// launches -- always in this order, because the calls are captured into hipGraphs.  ``det``: blk_sums and the ordered finish instead of
+// the zeroed, atomically accumulated sums (dgamma is then the parameter partial, dbeta unused).  ``cs_partial``: the ends form (whose
+// entry refuses E > 1024), with ``inv`` / ``n_vis`` if the gradient comes through the position map.
+struct EmbedBwd {
+    const float* dxg; const int* inv; int n_vis;
+    const float *y, *stats, *gamma;
+    bf16_t* dyc; float *dgamma, *dbeta, *sums, *blk_sums, *cs_partial;
+    int B, D, L, E, tok_off, Lgroup;
+};
+
+template <int NV, bool DET, bool MAP, bool CS, bool WIDE>
+static void launch_embed_bwd_form(const EmbedBwd& a, hipStream_t s) {
+    const int nblk = ceil_div(a.L, 4 * EB_ROWS);
+    const dim3 grid(nblk, a.B * a.D), grid2(ceil_div((long)a.B * a.D * a.L, 4 * (CS ? EA_ROWS : 1))), block(256);
+    const size_t lds = (size_t)(8 * std::min(a.E, 256 * NV) + (DET ? 8 : 0)) * sizeof(float);
+    // (a KERNEL, not hipMemsetAsync: these entry points are captured into hipGraphs, and on ROCm 7.2 the 16-byte memset node of a
+    //  [B = 2, D = 1] modality replayed wrongly -- garbage in `sums` from the second replay on, found in round 3 by the order of
+    //  the GPU tests; every other node of the graph was fine)
+    if (!DET) hipLaunchKernelGGL(zero_f32_kernel, dim3(ceil_div((long)a.B * a.D * 2, 256)), block, 0, s, a.sums, a.B * a.D * 2);
+    hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, DET, MAP, WIDE>), grid, block, lds, s, a.dxg, a.y, a.stats, a.gamma,
+                       DET ? a.blk_sums : a.sums, a.dgamma, a.dbeta, a.B, a.D, a.L, a.E, a.tok_off, a.Lgroup, a.inv, a.n_vis);
+    if (DET) hipLaunchKernelGGL(embed_bwd_sums_det_kernel, dim3(a.B * a.D), dim3(64), 0, s, a.blk_sums, a.sums, nblk);
+    hipLaunchKernelGGL((embed_bwd_apply_kernel<NV, MAP, CS, WIDE>), grid2, block, 0, s, a.dxg, a.inv, a.n_vis, a.y, a.stats, a.gamma,
+                       a.sums, a.dyc, a.cs_partial, a.B, a.D, a.L, a.E, a.tok_off, a.Lgroup);
+}
+
+static int launch_embed_bwd(const char* name, bool det, const EmbedBwd& a, void* stream) {
+    MH_CHECK_ARG(a.B > 0 && a.D > 0 && a.L > 0 && a.E > 0 && a.E % 4 == 0 && a.tok_off >= 0 && a.tok_off + a.D * a.L <= a.Lgroup,
+                 "%s: bad sizes B=%d D=%d L=%d E=%d (E %% 4 == 0) tok_off=%d Lgroup=%d", name, a.B, a.D, a.L, a.E, a.tok_off, a.Lgroup);
+    hipStream_t s = (hipStream_t)stream;
+    for_row_nv(a.E, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if (a.cs_partial) {
+            if (a.inv) launch_embed_bwd_form<NV, false, true, true, false>(a, s); else launch_embed_bwd_form<NV, false, false, true, false>(a, s);
+        } else if (a.E <= 256 * NV) {
+            if (det) launch_embed_bwd_form<NV, true, false, false, false>(a, s); else launch_embed_bwd_form<NV, false, false, false, false>(a, s);
+        } else if constexpr (NV == 4) {          // E > 1024: column passes
+            if (det) launch_embed_bwd_form<4, true, false, false, true>(a, s); else launch_embed_bwd_form<4, false, false, false, true>(a, s);
+        }
+    });
+    MH_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int mh_embed_finish_bwd(const float* dxg, const float* y, const float* stats, const float* gamma, void* dyc,
                                    float* dgamma, float* dbeta, float* sums, int B, int D, int L, int E, int tok_off,
                                    int Lgroup, void* stream) {
-    MH_CHECK_ARG(dxg && y && stats && gamma && dyc && dgamma && dbeta && sums && E % 4 == 0, "mh_embed_finish_bwd: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    // (a KERNEL, not hipMemsetAsync: this entry point is captured into hipGraphs, and on ROCm 7.2 the 16-byte memset node of a
-    //  [B = 2, D = 1] modality replayed wrongly -- garbage in `sums` from the second replay on, found in round 3 by the order of
-    //  the GPU tests; every other node of the graph was fine)
-    hipLaunchKernelGGL(zero_f32_kernel, dim3(ceil_div((long)B * D * 2, 256)), dim3(256), 0, s, sums, B * D * 2);
-    {
-        const dim3 grid(ceil_div(L, 4 * EB_ROWS), B * D), block(256);
-        const size_t lds = (size_t)8 * E * sizeof(float);
-#define MH_EB_LAUNCH(NV) hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, false>), grid, block, lds, s, dxg, y, stats, gamma, sums, dgamma, dbeta, B, D, L, E, tok_off, Lgroup)
-        switch ((E + 255) / 256) {
-            case 1: MH_EB_LAUNCH(1); break;
-            case 2: MH_EB_LAUNCH(2); break;
-            case 3: MH_EB_LAUNCH(3); break;
-            case 4: MH_EB_LAUNCH(4); break;
-            default: MH_EB_LAUNCH(0); break;
-        }
-#undef MH_EB_LAUNCH
-    }
-    hipLaunchKernelGGL(embed_bwd_apply_kernel, dim3(ceil_div((long)B * D * L, 4)), dim3(256), 0, s, dxg, y, stats, gamma, sums,
-                       (bf16_t*)dyc, B, D, L, E, tok_off, Lgroup);
-    MH_LAUNCH_CHECK();
-    return 0;
+    MH_CHECK_ARG(dxg && y && stats && gamma && dyc && dgamma && dbeta && sums, "mh_embed_finish_bwd: null pointer");
+    return launch_embed_bwd("mh_embed_finish_bwd", false,
+                            {dxg, nullptr, 0, y, stats, gamma, (bf16_t*)dyc, dgamma, dbeta, sums, nullptr, nullptr, B, D, L, E, tok_off, Lgroup},
+                            stream);
 }
 
 extern "C" int mh_embed_bwd_cs_rows(long rows) { return rows > 0 ? (int)ceil_div(rows, (long)(4 * EA_ROWS)) : 0; }
@@ -740,30 +740,11 @@ extern "C" int mh_embed_finish_bwd_ends(const float* dx, const int* inv, int n_v
                                         const float* gamma, void* dyc, float* dgamma, float* dbeta, float* sums, float* cs_partial,
                                         int B, int D, int L, int E, int tok_off, int Lgroup, void* stream) {
     MH_CHECK_ARG(dx && y && stats && gamma && dyc && dgamma && dbeta && sums && cs_partial, "mh_embed_finish_bwd_ends: null pointer");
-    MH_CHECK_ARG(B > 0 && D > 0 && L > 0 && E > 0 && E % 4 == 0 && E <= 1024 && tok_off >= 0 && tok_off + D * L <= Lgroup &&
-                 (!inv || (n_vis > 0 && n_vis <= Lgroup)),
-                 "mh_embed_finish_bwd_ends: bad sizes B=%d D=%d L=%d E=%d (E %% 4 == 0, E <= 1024) tok_off=%d Lgroup=%d n_vis=%d", B, D, L, E,
-                 tok_off, Lgroup, n_vis);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(zero_f32_kernel, dim3(ceil_div((long)B * D * 2, 256)), dim3(256), 0, s, sums, B * D * 2);   // (a kernel: see mh_embed_finish_bwd)
-    const dim3 grid(ceil_div(L, 4 * EB_ROWS), B * D), block(256), grid2(mh_embed_bwd_cs_rows((long)B * D * L));
-    const size_t lds = (size_t)8 * E * sizeof(float);
-#define MH_EB_LAUNCH(NV, MAP) do { \
-        hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, false, MAP>), grid, block, lds, s, dx, y, stats, gamma, sums, dgamma, dbeta, B, D, L, \
-                           E, tok_off, Lgroup, inv, n_vis); \
-        hipLaunchKernelGGL((embed_bwd_apply_cs_kernel<NV, MAP>), grid2, block, 0, s, dx, inv, n_vis, y, stats, gamma, sums, (bf16_t*)dyc, \
-                           cs_partial, B, D, L, E, tok_off, Lgroup); } while (0)
-#define MH_EB_FORMS(NV) do { if (inv) MH_EB_LAUNCH(NV, true); else MH_EB_LAUNCH(NV, false); } while (0)
-    switch ((E + 255) / 256) {
-        case 1: MH_EB_FORMS(1); break;
-        case 2: MH_EB_FORMS(2); break;
-        case 3: MH_EB_FORMS(3); break;
-        default: MH_EB_FORMS(4); break;
-    }
-#undef MH_EB_FORMS
-#undef MH_EB_LAUNCH
-    MH_LAUNCH_CHECK();
-    return 0;
+    MH_CHECK_ARG(E <= 1024 && (!inv || (n_vis > 0 && n_vis <= Lgroup)), "mh_embed_finish_bwd_ends: bad sizes E=%d (E <= 1024) n_vis=%d Lgroup=%d",
+                 E, n_vis, Lgroup);
+    return launch_embed_bwd("mh_embed_finish_bwd_ends", false,
+                            {dx, inv, n_vis, y, stats, gamma, (bf16_t*)dyc, dgamma, dbeta, sums, nullptr, cs_partial, B, D, L, E, tok_off, Lgroup},
+                            stream);
 }
 
 extern "C" int mh_embed_bwd_partial_rows(int BD, int L) { return BD > 0 && L > 0 ? BD * ceil_div(L, 4 * EB_ROWS) : 0; }
@@ -772,28 +753,10 @@ extern "C" int mh_embed_finish_bwd_det(const float* dxg, const float* y, const f
                                        float* param_partial, float* blk_sums, float* sums, int B, int D, int L, int E, int tok_off,
                                        int Lgroup, void* stream) {
     MH_CHECK_ARG(dxg && y && stats && gamma && dyc && param_partial && blk_sums && sums, "mh_embed_finish_bwd_det: null pointer");
-    MH_CHECK_ARG(B > 0 && D > 0 && L > 0 && E > 0 && E % 4 == 0 && tok_off >= 0 && tok_off + D * L <= Lgroup,
-                 "mh_embed_finish_bwd_det: bad sizes B=%d D=%d L=%d E=%d tok_off=%d Lgroup=%d", B, D, L, E, tok_off, Lgroup);
-    hipStream_t s = (hipStream_t)stream;
-    const int nblk = ceil_div(L, 4 * EB_ROWS);
-    {
-        const dim3 grid(nblk, B * D), block(256);
-        const size_t lds = (size_t)(8 * E + 8) * sizeof(float);
-#define MH_EB_LAUNCH(NV) hipLaunchKernelGGL((embed_bwd_stats_kernel<NV, true>), grid, block, lds, s, dxg, y, stats, gamma, blk_sums, param_partial, (float*)nullptr, B, D, L, E, tok_off, Lgroup)
-        switch ((E + 255) / 256) {
-            case 1: MH_EB_LAUNCH(1); break;
-            case 2: MH_EB_LAUNCH(2); break;
-            case 3: MH_EB_LAUNCH(3); break;
-            case 4: MH_EB_LAUNCH(4); break;
-            default: MH_EB_LAUNCH(0); break;
-        }
-#undef MH_EB_LAUNCH
-    }
-    hipLaunchKernelGGL(embed_bwd_sums_det_kernel, dim3(B * D), dim3(64), 0, s, blk_sums, sums, nblk);
-    hipLaunchKernelGGL(embed_bwd_apply_kernel, dim3(ceil_div((long)B * D * L, 4)), dim3(256), 0, s, dxg, y, stats, gamma, sums,
-                       (bf16_t*)dyc, B, D, L, E, tok_off, Lgroup);
-    MH_LAUNCH_CHECK();
-    return 0;
+    return launch_embed_bwd("mh_embed_finish_bwd_det", true,
+                            {dxg, nullptr, 0, y, stats, gamma, (bf16_t*)dyc, param_partial, nullptr, sums, blk_sums, nullptr, B, D, L, E, tok_off,
+                             Lgroup},
+                            stream);
 }
 
 extern "C" int mh_depatchify(const float* patches, float* img, int BD, int C, int S, int P, void* stream) {

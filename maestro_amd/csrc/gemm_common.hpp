@@ -98,10 +98,6 @@ __device__ __forceinline__ float group_amax(float v) {
     for (int o = 1; o < LANES; o <<= 1) u = max(u, (uint32_t)__shfl_xor((int)u, o, 64));
     return __uint_as_float(u);
 }
-__device__ __forceinline__ f32x4 bf2x2_to_f32x4(uint32_t a, uint32_t b) {   // 4 bf16 (two packed words) -> 4 floats
-    return (f32x4){__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u), __uint_as_float(b << 16),
-                   __uint_as_float(b & 0xffff0000u)};
-}
 
 // Fold an absmax (v >= 0 or NaN: the int order of the bits is the float order, NaN on top: see amax_fold) into a slot's amax ROW (MH_FP8_AMAX_PITCH floats).
 // Atomics on one cache line retire at ~10 ns apiece whatever the address inside it (scripts/micro_amax.hip; a look-before-

@@ -62,9 +62,7 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
             }
             u32x2 pk = {pack_bf2(dd[0], dd[1]), pack_bf2(dd[2], dd[3])};
             if (d) *reinterpret_cast<u32x2*>(d + c) = pk;
-            if (CS && masked)
-                *colsum += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                   __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+            if (CS && masked) *colsum += bf2x2_to_f32x4(pk[0], pk[1]);
         };
         if constexpr (CS) {
 #pragma unroll
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
             for (int c = lane * 4; c < PPC; c += 256) chunk(c, nullptr);
         }
     }
-    if constexpr (CS) {
+    if constexpr (CS) {     // (the tail of mask.hip's gather_rows_bf16_cs_kernel: see the note there)
         __shared__ f32x4 csred[4][64 * LOSS_CS_NV];
 #pragma unroll
         for (int j = 0; j < LOSS_CS_NV; ++j) csred[w][lane + 64 * j] = cs[j];
@@ -123,8 +121,7 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const void* __restrict__ x
 #pragma unroll 8
             for (int r = r0 + w; r < r1; r += nw) {
                 const u32x2 pk = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(x) + (size_t)r * ld + c);
-                acc += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                               __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+                acc += bf2x2_to_f32x4(pk[0], pk[1]);
             }
         }
     }

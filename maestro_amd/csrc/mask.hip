@@ -116,11 +116,12 @@ __global__ __launch_bounds__(256) void gather_rows_bf16_cs_kernel(const float* _
             if (c < dim) {
                 const u32x2 pk = {pack_bf2(v[r][j][0], v[r][j][1]), pack_bf2(v[r][j][2], v[r][j][3])};
                 *reinterpret_cast<u32x2*>(dst + (size_t)row * dim + c) = pk;
-                cs[j] += (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                 __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
+                cs[j] += bf2x2_to_f32x4(pk[0], pk[1]);
             }
         }
     }
+    // (this tail is the same in mask.hip, loss.hip and embed.hip; through a shared helper none of the three compiles to the
+    //  instructions it has written out: profiles/embed_bwd_unify.md)
 #pragma unroll
     for (int j = 0; j < NV; ++j) red[w][lane + 64 * j] = cs[j];
     __syncthreads();
@@ -282,15 +283,10 @@ extern "C" int mh_gather_rows_bf16_cs(const float* src, const int* idx, void* ds
     MH_CHECK_ARG(B > 0 && src_L > 0 && n_idx > 0 && n_idx <= src_L && dim > 0 && dim % 4 == 0 && dim <= 1024,
                  "mh_gather_rows_bf16_cs: bad sizes B=%d src_L=%d n_idx=%d dim=%d (dim %% 4 == 0, dim <= 1024)", B, src_L, n_idx, dim);
     const dim3 grid(mh_gather_rows_cs_rows((long)B * n_idx)), block(256);
-#define MH_GC_LAUNCH(NV) hipLaunchKernelGGL((gather_rows_bf16_cs_kernel<NV>), grid, block, 0, (hipStream_t)stream, src, idx, \
-                                            (bf16_t*)dst16, cs_partial, B, src_L, n_idx, dim)
-    switch ((dim + 255) / 256) {
-        case 1: MH_GC_LAUNCH(1); break;
-        case 2: MH_GC_LAUNCH(2); break;
-        case 3: MH_GC_LAUNCH(3); break;
-        default: MH_GC_LAUNCH(4); break;
-    }
-#undef MH_GC_LAUNCH
+    for_row_nv(dim, [&](auto nv) {
+        hipLaunchKernelGGL(gather_rows_bf16_cs_kernel<decltype(nv)::value>, grid, block, 0, (hipStream_t)stream, src, idx, (bf16_t*)dst16,
+                           cs_partial, B, src_L, n_idx, dim);
+    });
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -320,7 +320,7 @@ def test_unmask_token_grad_det(dev, per_sample, L):  # noqa: N803
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm backward
-@pytest.mark.parametrize("E", [64, 192])
+@pytest.mark.parametrize("E", [64, 192, 1028])      # 1028: two column passes (E > 1024)
 def test_embed_finish_bwd_det(dev, E):  # noqa: N803
     from maestro_amd import hip
     B, D, L, tok_off, Lg = 3, 1, 33, 2, 38  # noqa: N806

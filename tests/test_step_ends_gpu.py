@@ -245,6 +245,25 @@ def test_embed_apply_leaves_the_conv_bias_gradient_as_partial_rows():
     _assert_colsum("embed_bwd_apply", _reduce(dev, outs[1][4], rows, E), outs[1][0], B * D * L)
 
 
+def test_embed_ends_form_refuses_a_width_above_1024():
+    """E = 1028 is a width the plain and deterministic forms take (in two column passes); the ends form keeps its columns' sums in
+    registers and refuses it before any launch: the outputs keep the values they were given."""
+    from maestro_amd import hip
+    dev = _dev()
+    B, D, L, E = 1, 1, 3, 1028  # noqa: N806
+    g = torch.Generator().manual_seed(22)
+    gs = guards.GuardSet(dev)
+    dxg, y = gs.inp(torch.randn(B * L, E, generator=g), name="dxg"), gs.inp(torch.randn(B * L, E, generator=g), name="y")
+    stats, gamma = gs.inp(torch.tensor([[0.1, 0.9]]), name="stats"), gs.inp(torch.ones(E), name="gamma")
+    outs = [gs.out((B * L, E), BF16, init=3.0, name="dyc"), gs.out((E,), F32, init=3.0, name="dgamma"), gs.out((E,), F32, init=3.0, name="dbeta"),
+            gs.out((B * D, 2), F32, init=3.0, name="sums"), gs.out((hip.embed_bwd_cs_rows(B * L), E), F32, init=3.0, name="cs_partial")]
+    with pytest.raises(hip.HipExtensionError):
+        hip.embed_finish_bwd_ends(dxg, None, 0, y, stats, gamma, *outs, B, D, L, E, 0, L)
+    torch.cuda.synchronize()
+    gs.check()
+    assert all(bool((o == 3.0).all()) for o in outs)
+
+
 def test_gather_writes_the_bf16_rows_and_their_column_sums():
     """M = 6 rows (B = 2, three visible of five) at Dd = 512: dst16 = cast_bf16(gather_rows(src)) bit for bit."""
     from maestro_amd import hip

@@ -29,7 +29,7 @@ def test_final_layernorm_forms_are_in_the_library_without_scratch():
             k = names[form]
             assert k["vgpr_count"] <= 256 and k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
     for form, k in names.items():       # the producers with fused column sums and the position-map forms
-        if any(t in form for t in ("masked_loss_kernel", "gather_rows_bf16_cs_kernel", "embed_bwd_apply_cs_kernel", "embed_bwd_stats_kernel")):
+        if any(t in form for t in ("masked_loss_kernel", "gather_rows_bf16_cs_kernel", "embed_bwd_apply_kernel", "embed_bwd_stats_kernel")):
             assert k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0 and k["vgpr_count"] <= 256, k
 
 
@@ -70,3 +70,26 @@ def test_ends_entry_points_are_declared_exported_and_bound():
         assert hasattr(handle, n), n
         assert n in binding, f"{n} is not bound in maestro_amd/hip.py"
     assert hip.COLSUM_ROWS == 16
+
+
+def test_plain_embed_backward_checks_its_sizes_like_its_siblings():
+    """``mh_embed_finish_bwd`` refuses a modality that does not fit its group sequence, and sizes that are not positive, as the
+    deterministic and ends forms do.  Every call here fails its check: nothing is launched, the pointers are host addresses that
+    nothing dereferences."""
+    import ctypes
+
+    from maestro_amd.csrc.build import LIB
+    if not LIB.exists():
+        pytest.skip("needs the built library")
+    lib = ctypes.CDLL(str(LIB))
+    lib.mh_last_error.restype = ctypes.c_char_p
+    buf = (ctypes.c_float * 16)()
+    p, i = ctypes.c_void_p(ctypes.addressof(buf)), ctypes.c_int
+
+    def call(B, D, L, E, tok_off, Lgroup):  # noqa: N803
+        return lib.mh_embed_finish_bwd(p, p, p, p, p, p, p, p, i(B), i(D), i(L), i(E), i(tok_off), i(Lgroup), None)
+
+    assert call(1, 2, 3, 8, 1, 6) < 0 and b"mh_embed_finish_bwd: bad sizes" in lib.mh_last_error()        # 1 + 2 * 3 > 6
+    for bad in ((0, 2, 3, 8, 0, 6), (1, 0, 3, 8, 0, 6), (1, 2, 0, 8, 0, 6), (1, 2, 3, 0, 0, 6), (1, 2, 3, 6, 0, 6), (1, 2, 3, 8, -1, 6)):
+        assert call(*bad) < 0 and b"bad sizes" in lib.mh_last_error(), bad
+    assert lib.mh_embed_finish_bwd(None, p, p, p, p, p, p, p, i(1), i(2), i(3), i(8), i(0), i(6), None) < 0 and b"null" in lib.mh_last_error()
