@@ -92,12 +92,12 @@ int mh_gemm_bf16(int layout, int M, int N, int K, const void* A, int lda, const 
  * eligible tiles once per distinct (layout, M, N, K, flags) and remembers the fastest (maestro_amd/hip.py). */
 enum { MH_TILE_AUTO = -1, MH_TILE_REG_128 = 0, MH_TILE_DMA_256 = 1, MH_TILE_DMA_256x128 = 2, MH_TILE_DMA_128x256 = 3,
        MH_TILE_DMA_128 = 4, MH_TILE_DMA_128x4 = 5, MH_TILE_DMA_256_LOCKSTEP = 6, MH_TILE_PP_128 = 7,
-       /* diagnostic builds of MH_TILE_PP_128 (NT only; outputs are NOT the GEMM's): main loop only / epilogue arithmetic without
-        * its stores / stores without the GELU arithmetic -- the ablation under profiles/ (scripts/bench_pp_ablate.py).  They exist
-        * only in a library built with -DMH_DIAG_TILES (MH_BUILD_FLAGS); the shipped library returns -2 for these ids (nothing
-        * launched), so no caller of the C ABI can get a wrong-output kernel by passing a tile id. */
+       /* retired ids, reserved: they named diagnostic builds of MH_TILE_PP_128 whose outputs were NOT the GEMM's (main loop only /
+        * epilogue arithmetic without its stores / stores without the GELU arithmetic / other instruction placements: the ablation
+        * under profiles/r03_gemm_pp_diag.txt).  No library contains those kernels: every library returns -2 for these ids (nothing
+        * launched, output untouched), so no caller of the C ABI can get a wrong-output kernel by passing a tile id. */
        MH_TILE_PP_128_DIAG1 = 8, MH_TILE_PP_128_DIAG2 = 9, MH_TILE_PP_128_DIAG3 = 10,
-       MH_TILE_PP_128_DIAG4 = 11, MH_TILE_PP_128_DIAG5 = 12,  /* full epilogue, other instruction placements */
+       MH_TILE_PP_128_DIAG4 = 11, MH_TILE_PP_128_DIAG5 = 12,
        /* MH_TILE_REG_128's kernel with 64 x 128 tiles (three workgroups per CU) / 192 x 128 tiles: for outputs whose 128 x 128
         * tiling fills the chip's workgroup slots badly (N = 512 / 768).  NT / NN without MH_GEMM_COLSUM; otherwise = REG_128. */
        MH_TILE_REG_64 = 13, MH_TILE_REG_192 = 14,

@@ -81,8 +81,8 @@ __global__ __launch_bounds__(NT, MT == 2 ? 3 : 2) void gemm_kernel(GemmParams p)
         __builtin_amdgcn_s_setprio(0);
     };
     if (p.fast) {
-        const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra_src = buffer_rsrc(p.A, (int)p.a_bytes);
+        const __amdgpu_buffer_rsrc_t rb_src = buffer_rsrc(p.B, (int)p.b_bytes);
         int va[NA], vb[4];
         tile_offsets<A_KMAJOR, NA>(p.lda, m0, va);
         tile_offsets<B_KMAJOR>(p.ldb, n0, vb);
@@ -201,34 +201,26 @@ static int gemm_reg_launch(int tile, int layout, GemmParams& p, hipStream_t s) {
     const int mt = tile == MH_TILE_REG_64 ? 2 : tile == MH_TILE_REG_192 ? 6 : 4;
     const int tbm = 32 * mt;
     p.tiles_m = ceil_div(p.M, tbm); p.tiles_n = ceil_div(p.N, BN);
-    int splits = 1;
-    if (p.flags & MH_GEMM_ATOMIC) {  // fill the 256 CUs (2 workgroups each) when the output has few tiles
-        const int tiles = p.tiles_m * p.tiles_n;
-        const int ksteps = ceil_div(K, BK);
-        splits = max(1, min(min(512 / max(tiles, 1), ksteps / 4), 32));
-    }
-    const int ksteps_per = ceil_div(ceil_div(K, BK), splits);
-    p.k_per_split = ksteps_per * BK;
-    splits = ceil_div(K, p.k_per_split);
+    // split-K fills the 256 CUs (2 workgroups each) when an atomic-accumulate output has few tiles
+    const int ksteps = ceil_div(K, BK);
+    const SplitK sk = (p.flags & MH_GEMM_ATOMIC) ? split_k(p.tiles_m * p.tiles_n, ksteps, 512, 4) : SplitK{ksteps, 1};
+    p.k_per_split = sk.ksteps_per * BK;
     // Buffer-load fast path: K-minor operands must have no K tail inside a K step (it would wrap into the next row
     // instead of reading zero); K-major operands zero-fill beyond K by the descriptor extent.  Split ranges are whole
     // K steps, so the only tail is the global one.
     const bool a_kmajor = layout == 2, b_kmajor = layout != 0;
-    const long k_rows = (long)ceil_div(K, BK) * BK;
+    const long k_rows = (long)ksteps * BK;
     const bool tail_ok = (a_kmajor && b_kmajor) || K % BK == 0;
     p.fast = tail_ok && gemm_in_reach((a_kmajor ? k_rows : (long)p.tiles_m * tbm) * p.lda * 2, 4096) &&
              gemm_in_reach((b_kmajor ? k_rows : (long)p.tiles_n * BN) * p.ldb * 2, 4096);
     gemm_set_extents(p, layout);
-    dim3 grid(p.tiles_m * p.tiles_n, splits), block(NT);
-    switch (layout * 8 + mt) {
-        case 0 * 8 + 4: hipLaunchKernelGGL((gemm_kernel<false, false, 4>), grid, block, 0, s, p); break;
-        case 0 * 8 + 2: hipLaunchKernelGGL((gemm_kernel<false, false, 2>), grid, block, 0, s, p); break;
-        case 0 * 8 + 6: hipLaunchKernelGGL((gemm_kernel<false, false, 6>), grid, block, 0, s, p); break;
-        case 1 * 8 + 4: hipLaunchKernelGGL((gemm_kernel<false, true, 4>), grid, block, 0, s, p); break;
-        case 1 * 8 + 2: hipLaunchKernelGGL((gemm_kernel<false, true, 2>), grid, block, 0, s, p); break;
-        case 1 * 8 + 6: hipLaunchKernelGGL((gemm_kernel<false, true, 6>), grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL((gemm_kernel<true, true, 4>), grid, block, 0, s, p); break;
-    }
+    dim3 grid(p.tiles_m * p.tiles_n, sk.splits), block(NT);
+    for_layout(layout, [&](auto a_kmajor_c, auto b_kmajor_c) {
+        constexpr bool AK = decltype(a_kmajor_c)::value, BKM = decltype(b_kmajor_c)::value;
+        if (AK || mt == 4) hipLaunchKernelGGL((gemm_kernel<AK, BKM, 4>), grid, block, 0, s, p);   // (TN: the K-major A image is 128 columns wide)
+        else if (mt == 2) hipLaunchKernelGGL((gemm_kernel<false, BKM, 2>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((gemm_kernel<false, BKM, 6>), grid, block, 0, s, p);
+    });
     MH_LAUNCH_CHECK();
     return 0;
 }

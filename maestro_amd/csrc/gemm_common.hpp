@@ -23,6 +23,33 @@ struct GemmParams {
     uint8_t* c8_scales = nullptr; int ldc8s = 0;
 };
 
+// ---- device idioms every GEMM file spells the same way
+// Raw buffer descriptor over `bytes` bytes from `ptr`: accesses beyond the extent read as zero / are dropped.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* ptr, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)ptr, (short)0, bytes, 0x00020000);
+}
+// Bytes from the base of a `rows` x `cols` matrix of pitch `ld` to the end of its last element
+__host__ __device__ __forceinline__ long matrix_bytes(int rows, int cols, int ld, int esize) { return ((long)(rows - 1) * ld + cols) * esize; }
+// rows of 16 lanes: the odd rows of a are exchanged with the even rows of b (v_permlane16_swap_b32)
+__device__ __forceinline__ void swap16(uint32_t& a, uint32_t& b) {
+    const u32x2 r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0]; b = r[1];
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// Lane id without a live register (mbcnt): the work-item id VGPR need not survive the K loop (the eight-wave stream-K kernel spilled
+// it and reloaded it from scratch -- behind a vmcnt(0) that drained the DMA ring -- in every K step).  lane_id_opaque: behind an
+// opaque asm, so that what is computed from it is computed where it is asked for, not hoisted into (and kept live across) a K loop.
+// (The plain form serves the two lane-0 tests of gemm_sk_dma.hip: opaque there, all four of its kernels change length.)
+__device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ int lane_id_opaque() {
+    int lane = lane_id();
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+// 32-byte chunk swizzle of a K-major LDS image's row k (gemm_reg.hpp: 128-column tiles; gemm_ring.hpp: the DMA ring)
+__device__ __forceinline__ int kmajor_sw(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
+
 // Output-tile coordinates of raster id `id` (ids already XCD-remapped: every XCD owns a contiguous run).  Ids walk GROUP_M m-tiles
 // before moving to the next n-tile, so the workgroups co-resident under one XCD's L2 cover a GROUP_M x (64 / GROUP_M) block of tiles
 // and sweep the B operand (the weight matrix of a forward / dgrad GEMM) panel by panel.  Group g starts its sweep at n-tile
@@ -110,10 +137,10 @@ __device__ __forceinline__ void atomic_max_pos(float* row, float v) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---- host side, shared by every GEMM entry point (gemm*.hip)
+// ---- host side, shared by every GEMM entry point (gemm*.hip); gemm_fill and gemm_extent also serve the grouped launch's kernel
 // The operand / epilogue half of the parameter block.  The family that launches sets tiles_m, tiles_n, k_per_split, fast and the
 // operand extents.
-static inline void gemm_fill(GemmParams& p, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
+__host__ __device__ static inline void gemm_fill(GemmParams& p, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
                              int flags, const float* bias, const float* res, int ldr, const void* aux_in, void* aux_out, int ldaux,
                              float* colsum) {
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
@@ -122,8 +149,8 @@ static inline void gemm_fill(GemmParams& p, int M, int N, int K, const void* A, 
 }
 // Bytes from the base of an operand to the end of its last element (the buffer descriptor's extent: everything beyond reads as
 // zero): `rows` x K with K contiguous (K-minor), or K x `rows` with the rows contiguous (K-major); `esize` bytes per element.
-static inline long gemm_extent(bool kmajor, int rows, int K, int ld, int esize = 2) {
-    return (kmajor ? (long)(K - 1) * ld + rows : (long)(rows - 1) * ld + K) * esize;
+__host__ __device__ static inline long gemm_extent(bool kmajor, int rows, int K, int ld, int esize = 2) {
+    return kmajor ? matrix_bytes(K, rows, ld, esize) : matrix_bytes(rows, K, ld, esize);
 }
 // a_bytes / b_bytes of bf16 operands in `layout` (0 NT, 1 NN, 2 TN)
 static inline void gemm_set_extents(GemmParams& p, int layout) {
@@ -133,6 +160,25 @@ static inline void gemm_set_extents(GemmParams& p, int layout) {
 // A buffer descriptor addresses 2 GiB: `bytes` = what the kernel's whole tiles span from the base (tile rows x pitch, past M / N /
 // K), `margin` = room for the offsets it adds inside a tile row.
 static inline bool gemm_in_reach(long bytes, long margin = 65536) { return bytes < (1L << 31) - margin; }
+// Split-K of an atomic-accumulate launch: enough splits (at most 32, each at least `min_ksteps` K steps) to fill `slots` workgroup
+// slots when the output has few tiles; then whole K steps per split, and the splits that are not empty.
+struct SplitK { int ksteps_per, splits; };
+static inline SplitK split_k(int tiles, int ksteps, int slots, int min_ksteps) {
+    const int want = max(1, min(min(slots / max(tiles, 1), ksteps / min_ksteps), 32));
+    const int ksteps_per = ceil_div(ksteps, want);
+    return {ksteps_per, ceil_div(ksteps, ksteps_per)};
+}
+// fn(A_KMAJOR, B_KMAJOR) as std::integral_constant<bool>s for `layout` (0 NT, 1 NN, 2 TN): the one place that turns a layout into
+// template arguments
+template <class F>
+static void for_layout(int layout, F&& fn) {
+    using std::false_type; using std::true_type;
+    switch (layout) {
+        case 0: fn(false_type{}, false_type{}); break;
+        case 1: fn(false_type{}, true_type{}); break;
+        default: fn(true_type{}, true_type{}); break;
+    }
+}
 
 // Kernel families other than the register-staged tile: `serves` is the family's FULL eligibility for a problem (shapes, strides and
 // flags of `p` only: no pointer is read, nothing is launched) and is what mh_gemm_bf16_resolve_tile (gemm.hip) asks; `launch` runs
@@ -140,11 +186,13 @@ static inline bool gemm_in_reach(long bytes, long margin = 65536) { return bytes
 // gemm_dma.hip: the LDS-DMA tile family (tile = MH_TILE_DMA_*)
 bool gemm_dma_serves(int tile, int layout, const GemmParams& p);
 int gemm_dma_launch(int tile, int layout, GemmParams& p, hipStream_t stream);
-// gemm_pp.hip: the persistent 128x128 tile with a second accumulator set (tile = MH_TILE_PP_128, or one of its DIAG builds)
+// gemm_pp.hip: the persistent 128x128 tile with a second accumulator set (tile = MH_TILE_PP_128; the retired ids MH_TILE_PP_128_DIAG1..5 are declined)
 bool gemm_pp_serves(int tile, int layout, const GemmParams& p);
 int gemm_pp_launch(int tile, int layout, GemmParams& p, hipStream_t stream);
 
 // MH_GEMM_AUX_U8: the saved GELU derivative as a byte code, value = code / 200 - 0.13 (range [-0.129, 1.129] -> 0.2 .. 251.8)
+// (one loop over both halves: as two calls of a four-element half, 96-202 instruction lines of every gemm_fp8_kernel move, and
+//  gemm_pp.hip's GELU epilogue takes neither form: it keeps the sequence written out)
 __device__ __forceinline__ u32x2 pack_dgelu_u8x8(f32x4 lo, f32x4 hi) {
     unsigned a = 0, b = 0;
 #pragma unroll
@@ -294,14 +342,13 @@ __device__ __forceinline__ void gemm_epilogue_store(const GemmParams& p, const f
                             lo *= unpack_dgelu_u8x4(pk[0]);
                             hi *= unpack_dgelu_u8x4(pk[1]);
                         } else {
-                            lo *= (f32x4){__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
-                                          __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
-                            hi *= (f32x4){__uint_as_float(pk[2] << 16), __uint_as_float(pk[2] & 0xffff0000u),
-                                          __uint_as_float(pk[3] << 16), __uint_as_float(pk[3] & 0xffff0000u)};
+                            lo *= bf2x2_to_f32x4(pk[0], pk[1]);
+                            hi *= bf2x2_to_f32x4(pk[2], pk[3]);
                         }
                     }
                     if (p.flags & MH_GEMM_DGELU) {
                         const u32x4 pk = aux_pre[pass];
+                        // (written out: bf2x2_to_f32x4 here swaps the multiplicands of the 8 v_fmac of GELU' in every kernel of gemm.hip)
                         const f32x4 h_lo = {__uint_as_float(pk[0] << 16), __uint_as_float(pk[0] & 0xffff0000u),
                                             __uint_as_float(pk[1] << 16), __uint_as_float(pk[1] & 0xffff0000u)};
                         const f32x4 h_hi = {__uint_as_float(pk[2] << 16), __uint_as_float(pk[2] & 0xffff0000u),

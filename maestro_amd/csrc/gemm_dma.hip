@@ -16,19 +16,6 @@
 // Out-of-range rows / K rows read as zero through the buffer descriptor's extent (no predication anywhere).
 #include "gemm_ring.hpp"
 
-// MH_DMA_PRIO (A/B aid): 0 = raise the priority around every math phase (default); 1 = static priority for the second-dispatched half
-// (waves 4-7), no flips; 2 = no priority at all
-#ifndef MH_DMA_PRIO
-#define MH_DMA_PRIO 0
-#endif
-#if MH_DMA_PRIO == 0
-#define MH_PRIO_UP() __builtin_amdgcn_s_setprio(1)
-#define MH_PRIO_DOWN() __builtin_amdgcn_s_setprio(0)
-#else
-#define MH_PRIO_UP() ((void)0)
-#define MH_PRIO_DOWN() ((void)0)
-#endif
-
 namespace {
 
 // (CALLER only makes the instantiations of the two kernels distinct: the host pass of hipcc 7.2 rejects the second request
@@ -47,8 +34,8 @@ __device__ __forceinline__ void gemm_dma_tile(const GemmParams& p, int tile_m, i
     constexpr int MT = T::MT;
     const int wm = (w / T::WN) * (16 * MT), wn = (w % T::WN) * 64;
 
-    const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra_src = buffer_rsrc(p.A, (int)p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rb_src = buffer_rsrc(p.B, (int)p.b_bytes);
     int va[PA], vb[PB];
     piece_offsets<A_KMAJOR, T::BM, NW, PA>(p.lda, m0, w, l, va);
     piece_offsets<B_KMAJOR, T::BN, NW, PB>(p.ldb, n0, w, l, vb);
@@ -119,17 +106,16 @@ __device__ __forceinline__ void gemm_dma_tile(const GemmParams& p, int tile_m, i
         // Pieces of step t+1 are first read in phase 2t+2, behind the barrier that follows those waits; the slot refilled in
         // a load phase of step t (step t+S-1 -> slot of step t-1) was last read in phase 2t-1.  Same K order per output
         // element as the lockstep loop: bit-identical results.
+        // Every math phase runs at raised wave priority.  (A static priority for waves 4-7 without flips, and no priority at all,
+        // measured the same: profiles/r06_experiments.md #14.)
         wait_step(0);
         __builtin_amdgcn_s_barrier();
-#if MH_DMA_PRIO == 1
-        if (w >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
         if (w < 4) {                   // wave-uniform role; both roles execute 2 nk barriers
             for (int t = 0; t < nk; ++t) {
                 load_step(t);
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
-                MH_PRIO_UP(); math_step(); MH_PRIO_DOWN();
+                __builtin_amdgcn_s_setprio(1); math_step(); __builtin_amdgcn_s_setprio(0);
                 if (t + 1 < nk) wait_step(t + 1);
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
@@ -142,7 +128,7 @@ __device__ __forceinline__ void gemm_dma_tile(const GemmParams& p, int tile_m, i
                 if (t + 1 < nk) wait_step(t + 1);
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
-                MH_PRIO_UP(); math_step(); MH_PRIO_DOWN();   // phase 2t+2
+                __builtin_amdgcn_s_setprio(1); math_step(); __builtin_amdgcn_s_setprio(0);   // phase 2t+2
                 if (t + 1 < nk) {
                     __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_sched_barrier(0);
@@ -199,13 +185,11 @@ __global__ __launch_bounds__(T::NT) void gemm_dma_grouped_tn_kernel(const MhGrou
     if (e == 0xFFFFFFFFu || (int)(e >> 16) >= n_problems) return;
     const MhGroupedGemm g = table[e >> 16];
     GemmParams p;
-    p.A = (const bf16_t*)g.A; p.B = (const bf16_t*)g.B; p.C = g.C;
-    p.bias = nullptr; p.res = nullptr; p.aux_in = nullptr; p.aux_out = nullptr; p.colsum = nullptr;
-    p.M = g.M; p.N = g.N; p.K = g.K; p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldr = 0; p.ldaux = 0;
-    p.flags = MH_GEMM_OUT_F32 | (g.accumulate ? MH_GEMM_ATOMIC : 0);
+    gemm_fill(p, g.M, g.N, g.K, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, MH_GEMM_OUT_F32 | (g.accumulate ? MH_GEMM_ATOMIC : 0), nullptr, nullptr, 0,
+              nullptr, nullptr, 0, nullptr);
     p.tiles_m = (g.M + T::BM - 1) / T::BM; p.tiles_n = (g.N + T::BN - 1) / T::BN; p.k_per_split = g.K; p.fast = 1;
-    p.a_bytes = (unsigned)(((long)(g.K - 1) * g.lda + g.M) * 2);
-    p.b_bytes = (unsigned)(((long)(g.K - 1) * g.ldb + g.N) * 2);
+    p.a_bytes = (unsigned)gemm_extent(true, g.M, g.K, g.lda);
+    p.b_bytes = (unsigned)gemm_extent(true, g.N, g.K, g.ldb);
     const int tile_m = (e >> 8) & 0xff, tile_n = e & 0xff;
     if (tile_m >= p.tiles_m || tile_n >= p.tiles_n) return;
     gemm_dma_tile<T, true, true, 1, STAGGER>(p, tile_m, tile_n, 0, g.K, smem);
@@ -215,29 +199,18 @@ template <class T>
 void launch_dma(int layout, GemmParams& p, hipStream_t s, bool stagger = true) {
     const int K = p.K;
     p.tiles_m = ceil_div(p.M, T::BM); p.tiles_n = ceil_div(p.N, T::BN);
-    int splits = 1;
-    if (p.flags & MH_GEMM_ATOMIC) {
-        const int tiles = p.tiles_m * p.tiles_n, ksteps = ceil_div(K, BK);
-        const int slots = 256 * (T::LDS_BYTES > 80 * 1024 ? 1 : 2);
-        splits = max(1, min(min(slots / max(tiles, 1), ksteps / 8), 32));
-    }
-    const int ksteps_per = ceil_div(ceil_div(K, BK), splits);
-    p.k_per_split = ksteps_per * BK;
-    splits = ceil_div(K, p.k_per_split);
-    dim3 grid(p.tiles_m * p.tiles_n, splits), block(T::NT);
-    if (T::NW == 8 && stagger) {
-        switch (layout) {
-            case 0: hipLaunchKernelGGL((gemm_dma_kernel<T, false, false, T::NW == 8>), grid, block, 0, s, p); break;
-            case 1: hipLaunchKernelGGL((gemm_dma_kernel<T, false, true, T::NW == 8>), grid, block, 0, s, p); break;
-            default: hipLaunchKernelGGL((gemm_dma_kernel<T, true, true, T::NW == 8>), grid, block, 0, s, p); break;
-        }
-        return;
-    }
-    switch (layout) {
-        case 0: hipLaunchKernelGGL((gemm_dma_kernel<T, false, false, false>), grid, block, 0, s, p); break;
-        case 1: hipLaunchKernelGGL((gemm_dma_kernel<T, false, true, false>), grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL((gemm_dma_kernel<T, true, true, false>), grid, block, 0, s, p); break;
-    }
+    const int ksteps = ceil_div(K, BK), slots = 256 * (T::LDS_BYTES > 80 * 1024 ? 1 : 2);   // workgroups the chip holds at once
+    const SplitK sk = (p.flags & MH_GEMM_ATOMIC) ? split_k(p.tiles_m * p.tiles_n, ksteps, slots, 8) : SplitK{ksteps, 1};
+    p.k_per_split = sk.ksteps_per * BK;
+    dim3 grid(p.tiles_m * p.tiles_n, sk.splits), block(T::NT);
+    auto launch = [&](auto stagger_c) {
+        for_layout(layout, [&](auto a_kmajor_c, auto b_kmajor_c) {
+            hipLaunchKernelGGL((gemm_dma_kernel<T, decltype(a_kmajor_c)::value, decltype(b_kmajor_c)::value, decltype(stagger_c)::value>),
+                               grid, block, 0, s, p);
+        });
+    };
+    if (T::NW == 8 && stagger) launch(std::integral_constant<bool, T::NW == 8>{});   // (no staggered form of a four-wave tile is built)
+    else launch(std::false_type{});
 }
 
 }  // namespace

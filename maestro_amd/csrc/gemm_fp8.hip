@@ -67,9 +67,6 @@ typedef Tile8<2, 2, 4, 4> T8_128D;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((address_space(3))) void lds_void8;
 
-template <int N>
-__device__ __forceinline__ void wait_vm8() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // fragment of rows (rc0 + lane & 15): 32 bytes along k = 32 (lane >> 4) + j.  MX: the scaled MFMA reads byte j of lane group g as
 // k = 64 (j >> 4) + 16 g + (j & 15) -- its scale for block b (k = 32 b .. 32 b + 31) comes from lane group b (measured: one-hot
 // data, a distinct exponent per row and block) -- so that lane group g holds the 16-byte chunks g and g + 4 of the row: the
@@ -99,8 +96,8 @@ __device__ __forceinline__ void gemm_fp8_body(const GemmParams& p, unsigned char
 
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
     const int wm = (w / T::WN) * (16 * MT), wn = (w % T::WN) * 64;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(p.A, (int)p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(p.B, (int)p.b_bytes);
     int va[PA], vb[PB];   // per-lane source byte offsets of this wave's pieces (piece = 8 rows x 128 B), k = 0
 #pragma unroll
     for (int h = 0; h < PA; ++h) {
@@ -114,8 +111,7 @@ __device__ __forceinline__ void gemm_fp8_body(const GemmParams& p, unsigned char
     }
     // MX: waves 0 .. BM/64 - 1 fetch A scale rows 64 w + l, the others B scale rows (wave-uniform choice of descriptor)
     const bool is_a = w < T::BM / 64;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(is_a ? p.sa : p.sb), (short)0,
-                                                                        (int)(is_a ? p.sa_bytes : p.sb_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(is_a ? p.sa : p.sb, (int)(is_a ? p.sa_bytes : p.sb_bytes));
     const int vs = !MX ? 0 : is_a ? (m0 + 64 * w + l) * p.ldsa : (n0 + 64 * (w - T::BM / 64) + l) * p.ldsb;
     constexpr int S8 = T::S8, DEPTH = S8 - 1;     // K steps in flight
     auto issue = [&](int t) {
@@ -143,12 +139,12 @@ __device__ __forceinline__ void gemm_fp8_body(const GemmParams& p, unsigned char
     for (int t = 0; t < nk; ++t) {
         // my pieces of step t have landed: at most the later steps' pieces (PA + PB per step and wave) may still be in flight
         if constexpr (DEPTH == 1) {
-            wait_vm8<0>();
+            wait_vmcnt<0>();
         } else {
             const int later = min(nk - 1 - t, DEPTH - 1);
-            if (later >= 2) wait_vm8<2 * (PA + PB + PS)>();
-            else if (later == 1) wait_vm8<PA + PB + PS>();
-            else wait_vm8<0>();
+            if (later >= 2) wait_vmcnt<2 * (PA + PB + PS)>();
+            else if (later == 1) wait_vmcnt<PA + PB + PS>();
+            else wait_vmcnt<0>();
         }
         __builtin_amdgcn_s_barrier();     // everybody's have; step t-1 has been read by everybody -> its slot can be refilled
         const unsigned char* ta = smem + (t % S8) * STAGE;

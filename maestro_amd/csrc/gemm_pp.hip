@@ -1,7 +1,6 @@
 // Persistent 128x128x64 bf16 GEMM with TWO accumulator sets: the epilogue of output tile t runs INSIDE the main loop of tile
 // t + 1 (mh_gemm_bf16_tile, tile = MH_TILE_PP_128; picked by MH_TILE_AUTO for the wide, short-K problems of the transformer
-// blocks: qkv / fc1 forward, fc2 dgrad -- the call sites of vit_pytorch's Attention / FeedForward Linears constructed at
-// /root/reference/maestro/ssl/mae.py:135-174).
+// blocks: qkv / fc1 forward, fc2 dgrad -- the Linears of the reference model's Attention / FeedForward blocks).
 //
 // Why: at K = 512 ... 768 a 128x128 tile is 8 ... 12 K steps and its epilogue (bias, erf-GELU, the byte-coded GELU', packs,
 // stores: ~15-22 VALU issue slots per output element, 3 B ... 8 B of HBM per element) costs 30-45 % of the launch
@@ -26,28 +25,18 @@
 #include "gemm_reg.hpp"
 #include <type_traits>
 
-// MH_PP_PRIO = 1 (round 6): the wave raises its priority over the MFMA body of every K step and drops it before the barrier, as gemm.hip's
-// K loop does: of the two co-resident workgroups the one whose fragments have arrived issues its MFMAs back to back.  Same box, three
-// alternating rounds of 30 C3 steps: 17.24 / 17.12 / 17.15 -> 17.02 / 17.00 / 17.01 ms (profiles/r06_experiments.md #21).  0: A/B aid.
-#ifndef MH_PP_PRIO
-#define MH_PP_PRIO 1
-#endif
+// Wave priority (round 6): the wave raises its priority over the MFMA body of every K step -- behind the first-half fragment reads and
+// the epilogue's operand loads -- and drops it before the barrier, as gemm.hip's K loop does: of the two co-resident workgroups the one
+// whose fragments have arrived issues its MFMAs back to back.  Same box, three alternating rounds of 30 C3 steps: 17.24 / 17.12 / 17.15
+// -> 17.02 / 17.00 / 17.01 ms (profiles/r06_experiments.md #21; against it, a window opened before the step's first fragment reads:
+// 17.09 / 17.10 / 17.15, worse; level 3 instead of 1: 17.00 / 17.04 / 17.09, the same).
 
 namespace {
 
 enum { EPI_BF16 = 0, EPI_GELU = 1, EPI_MULAUX = 2, EPI_F32 = 3 };
 constexpr int EPI_STEPS = 8;   // K steps of tile t + 1 that carry tile t's epilogue (two accumulator blocks each)
 
-__device__ __forceinline__ void swap16(uint32_t& a, uint32_t& b) {
-    // rows of 16 lanes: the odd rows of a are exchanged with the even rows of b (v_permlane16_swap_b32)
-    const u32x2 r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-
-// DIAG (diagnostic builds for the ablation in profiles/: what does the interleaved epilogue cost, and which part of it?):
-//   0 the kernel;  1 no epilogue at all (main loop only: nothing is written);  2 the epilogue's arithmetic without its
-//   global stores (results kept alive by an empty asm);  3 its stores without the GELU arithmetic (raw accumulators packed)
-template <bool B_KMAJOR, int EPI, int DIAG = 0>
+template <bool B_KMAJOR, int EPI>
 __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * TILE_BYTES];  // A0 A1 B0 B1
     const int T = p.tiles_m * p.tiles_n, G = gridDim.x;
@@ -69,8 +58,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     const int wm = (w >> 1) * 64, wn = (w & 1) * 64;
 
     // ---- operand stream: per-thread byte offsets inside a tile (loop invariant) + a scalar cursor (tile, K step)
-    const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra_src = buffer_rsrc(p.A, (int)p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rb_src = buffer_rsrc(p.B, (int)p.b_bytes);
     const int a_v0 = ((tid >> 3) * p.lda + (tid & 7) * 8) * 2;                                   // row r, 16-B chunk c
     const int b_v0 = B_KMAJOR ? ((tid >> 4) * p.ldb + (tid & 15) * 8) * 2 : ((tid >> 3) * p.ldb + (tid & 7) * 8) * 2;
     const int a_i = 32 * p.lda * 2, b_i = (B_KMAJOR ? 16 : 32) * p.ldb * 2;                         // per i = 0..3
@@ -98,14 +87,13 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     int sidx = 0;                  // stream step (LDS buffer = sidx & 1)
 
     // ---- epilogue state of the FINISHED tile (per-lane byte offsets; everything else is scalar)
-    const __amdgpu_buffer_rsrc_t rc_dst = __builtin_amdgcn_make_buffer_rsrc(
-        p.C, (short)0, (int)(((long)(p.M - 1) * p.ldc + p.N) * (EPI == EPI_F32 ? 4 : 2)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t raux = __builtin_amdgcn_make_buffer_rsrc(
-        EPI == EPI_GELU ? (void*)p.aux_out : EPI == EPI_MULAUX ? (void*)p.aux_in : (void*)p.res, (short)0,
-        (int)(EPI == EPI_F32 ? ((long)(p.M - 1) * p.ldr + p.N) * 4 : EPI == EPI_BF16 ? 0 : (long)(p.M - 1) * p.ldaux + p.N), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, (short)0, p.bias ? p.N * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rcs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.colsum, (short)0, EPI == EPI_MULAUX ? (int)((long)((p.M + 63) / 64) * p.N * 4) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rc_dst = buffer_rsrc(p.C, (int)matrix_bytes(p.M, p.N, p.ldc, EPI == EPI_F32 ? 4 : 2));
+    // (extents written out: matrix_bytes here turns one s_add_i32 literal of the fp32 kernels into an inline constant)
+    const __amdgpu_buffer_rsrc_t raux = buffer_rsrc(
+        EPI == EPI_GELU ? (const void*)p.aux_out : EPI == EPI_MULAUX ? (const void*)p.aux_in : (const void*)p.res,
+        (int)(EPI == EPI_F32 ? ((long)(p.M - 1) * p.ldr + p.N) * 4 : EPI == EPI_BF16 ? 0 : (long)(p.M - 1) * p.ldaux + p.N));
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc(p.bias, p.bias ? p.N * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rcs = buffer_rsrc(p.colsum, EPI == EPI_MULAUX ? (int)((long)((p.M + 63) / 64) * p.N * 4) : 0);
     const int w_s = __builtin_amdgcn_readfirstlane(w);   // the wave's index as a scalar: epi_setup below rebuilds its lane constants
     int e_c = 0, e_aux = 0, e_bias = 0, e_cs = 0;        // per-lane byte offsets of the finished tile (row wm + lm, pair 0, i = 0)
     f32x4 bias_x = {0, 0, 0, 0}, bias_y = {0, 0, 0, 0};  // bias of the current pair's two column blocks
@@ -113,10 +101,9 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     u32x4 ld_x = {0, 0, 0, 0}, ld_y = {0, 0, 0, 0};      // residual (f32x4) / aux bytes (first dword) of the chunk in flight
     auto epi_setup = [&](int m0, int n0) {
         // The lane constants are rebuilt HERE, once per tile, from the lane id (mbcnt) behind an opaque asm: written against the kernel's
-        // `lm` / `g` they stayed live across the whole K loop, and with the priority window (MH_PP_PRIO) the GELU kernel spilled three
+        // `lm` / `g` they stayed live across the whole K loop, and with the priority window the GELU kernel spilled three
         // of them -- one scratch reload behind a vmcnt(0) at the head of every tile.
-        int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        asm volatile("" : "+v"(lane));
+        const int lane = lane_id_opaque();
         const int g = lane >> 4, lm = lane & 15;
         const int wm = (w_s >> 1) * 64, wn = (w_s & 1) * 64;
         const int col_nat = wn + 4 * g;                      // natural layout: block X of pair jp at + 32 jp, block Y at + 32 jp + 16
@@ -135,7 +122,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     // chunk c = 0..7: pair jp = c >> 2 (column blocks 2 jp, 2 jp + 1), row block i = c & 3
     auto epi_loads = [&](auto cc) {
         constexpr int c = decltype(cc)::value, jp = c >> 2, i = c & 3;
-        if constexpr (DIAG == 1) return;
         if constexpr (EPI == EPI_GELU || EPI == EPI_F32) {
             if constexpr (i == 0) {
                 bias_x = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, e_bias + 128 * jp, 0, 0));
@@ -156,10 +142,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     auto epi_math = [&](auto cc, const f32x4 (&src)[4][4]) {
         constexpr int c = decltype(cc)::value, jp = c >> 2, i = c & 3;
         f32x4 vx = src[2 * jp][i], vy = src[2 * jp + 1][i];
-        if constexpr (DIAG == 1) {   // keep the accumulators alive, do nothing with them
-            asm volatile("" ::"v"(vx), "v"(vy));
-            return;
-        }
         if constexpr (EPI == EPI_F32) {
             const int o = e_c + (16 * i * p.ldc + 32 * jp) * 4;
             vx = vx + (bias_x + __builtin_bit_cast(f32x4, ld_x));   // (the order of gemm_common.hpp's fp32 epilogue: same bits)
@@ -171,9 +153,10 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
             if constexpr (EPI == EPI_GELU) {
                 vx += bias_x; vy += bias_y;
                 f32x4 cx, dx, cy, dy;
-                if constexpr (DIAG == 3) { cx = vx; dx = vx; cy = vy; dy = vy; }
-                else { gelu_cdf_pdf4(vx, cx, dx); gelu_cdf_pdf4(vy, cy, dy); }
+                gelu_cdf_pdf4(vx, cx, dx); gelu_cdf_pdf4(vy, cy, dy);
                 const f32x4 gx = vx * dx + cx, gy = vy * dy + cy;      // GELU' = CDF + x PDF
+                // (gemm_common.hpp's byte code written out: pack_dgelu_u8x8, or a four-element half of it per block, reorders ~700-840
+                //  instruction lines of both GELU kernels and drops 2-4 of them)
                 uint32_t bx = 0, by = 0;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -181,8 +164,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
                     by = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(gy[e], 200.f, 26.f), e, by);
                 }
                 swap16(bx, by);
-                if constexpr (DIAG == 2) asm volatile("" ::"v"(bx), "v"(by));
-                else __builtin_amdgcn_raw_buffer_store_b64((u32x2){bx, by}, raux, e_aux + 16 * i * p.ldaux + 32 * jp, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64((u32x2){bx, by}, raux, e_aux + 16 * i * p.ldaux + 32 * jp, 0, 0);
                 vx *= cx; vy *= cy;
             }
             if constexpr (EPI == EPI_MULAUX) {
@@ -207,8 +189,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
             uint32_t y0 = pack_bf2(vy[0], vy[1]), y1 = pack_bf2(vy[2], vy[3]);
             swap16(x0, y0);
             swap16(x1, y1);
-            if constexpr (DIAG == 2) asm volatile("" ::"v"(x0), "v"(x1), "v"(y0), "v"(y1));
-            else __builtin_amdgcn_raw_buffer_store_b128((u32x4){x0, x1, y0, y1}, rc_dst, e_c + (16 * i * p.ldc + 32 * jp) * 2, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128((u32x4){x0, x1, y0, y1}, rc_dst, e_c + (16 * i * p.ldc + 32 * jp) * 2, 0, 0);
         }
     };
 
@@ -221,17 +202,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
         const unsigned char* ta = smem + cur * TILE_BYTES;
         const unsigned char* tb = smem + (2 + cur) * TILE_BYTES;
         bf16x8 fa[4], fb[4];
-#if MH_PP_PRIO == 2     // (A/B: the window opens before the step's first fragment reads)
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) fa[i] = read_frag<false>(ta, wm + 16 * i, 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) fb[j] = read_frag<B_KMAJOR>(tb, wn + 16 * j, 0);
         if constexpr (CHUNK >= 0) epi_loads(chunk_c);
-#if MH_PP_PRIO == 1 || MH_PP_PRIO == 3
-        __builtin_amdgcn_s_setprio(MH_PP_PRIO);      // (3, A/B: the highest level instead of 1)
-#endif
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -252,15 +228,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
         if constexpr (CHUNK >= 0) epi_math(chunk_c, prev);
         // schedule: [first-half fragment reads] [epilogue operand loads] [8 x (2 MFMA, 1 DS write, 1 VMEM read, VALU)]
         //           [second-half reads] [8 x (2 MFMA, VALU)] [epilogue stores]
-        // The epilogue's VALU instructions are NOT pinned: measured on the fc1 shapes (scripts/bench_pp_ablate.py, us):
+        // The epilogue's VALU instructions are NOT pinned: measured on the fc1 shapes (profiles/r03_gemm_pp_diag.txt, us), with
+        // NV0 = 14 (GELU) / 6 (MULAUX) / 2 (F32, BF16) VALU instructions per slot in sched_group_barrier(0x402, ...) groups:
         //   no VALU groups (the scheduler's own placement) 54.9 / 78.8 / 68.2 / 184.5   <- this
-        //   NV0 VALU behind every pair of MFMAs (DIAG 4)    57.7 / 80.7 / 70.4 / 184.7
-        //   2 NV0 behind each group of fragment reads + the rest behind the MFMA pairs (DIAG 5)  57.1 / 80.4 / 70.0 / 190.8
-        constexpr int NV0 = CHUNK < 0 ? 0 : EPI == EPI_GELU ? 14 : EPI == EPI_MULAUX ? 6 : EPI == EPI_F32 ? 2 : 2;   // VALU / slot
-        constexpr int NV = DIAG == 4 ? NV0 : DIAG == 5 ? (NV0 * 4 + 6) / 7 : 0;
-        constexpr int NR = DIAG == 5 ? NV0 * 2 : 0;                                   // VALU behind each read group
+        //   NV0 VALU behind every pair of MFMAs             57.7 / 80.7 / 70.4 / 184.7
+        //   2 NV0 behind each group of fragment reads + (4 NV0 + 6) / 7 behind the MFMA pairs  57.1 / 80.4 / 70.0 / 190.8
         __builtin_amdgcn_sched_group_barrier(0x100, B_KMAJOR ? 12 : 8, 0);
-        if constexpr (NR > 0) __builtin_amdgcn_sched_group_barrier(0x402, NR, 0);
         constexpr int NL = CHUNK < 0 ? 0 : (EPI == EPI_F32 || EPI == EPI_MULAUX ? 2 : 0) + ((EPI == EPI_F32 || EPI == EPI_GELU) && (CHUNK & 3) == 0 ? 2 : 0);
         if constexpr (NL > 0) __builtin_amdgcn_sched_group_barrier(0x020, NL, 0);   // the epilogue's operand loads
 #pragma unroll
@@ -268,19 +241,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            if constexpr (NV > 0) __builtin_amdgcn_sched_group_barrier(0x402, NV, 0);
         }
         __builtin_amdgcn_sched_group_barrier(0x100, B_KMAJOR ? 12 : 8, 0);
-        if constexpr (NR > 0) __builtin_amdgcn_sched_group_barrier(0x402, NR, 0);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-            if constexpr (NV > 0) __builtin_amdgcn_sched_group_barrier(0x402, NV, 0);
-        }
+        for (int r = 0; r < 8; ++r) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         ++sidx;
-#if MH_PP_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         __syncthreads();
         advance();
     };
@@ -326,7 +292,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
     // -- load latency + store completion, vmcnt(0) each -- at the end of every workgroup, ~10 us inside the step where the residual
     // stream is cold, on launches whose workgroups own one or two tiles (out-proj, fc2: 384 tiles for 512 workgroups).
     epi_setup(cm0, cn0);
-    if constexpr (DIAG == 0 && (EPI == EPI_F32 || EPI == EPI_MULAUX)) {
+    if constexpr (EPI == EPI_F32 || EPI == EPI_MULAUX) {
         u32x4 tx[8], ty[8];
         f32x4 tbx[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, tby[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
         auto fetch = [&](auto cc) {
@@ -355,20 +321,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_pp_kernel(GemmParams p) {
 }
 
 template <bool B_KMAJOR>
-void launch_pp(int epi, int grid, const GemmParams& p, hipStream_t s, int diag = 0) {
+void launch_pp(int epi, int grid, const GemmParams& p, hipStream_t s) {
     dim3 g(grid), b(NT);
-#ifdef MH_DIAG_TILES   // ablation builds only (MH_BUILD_FLAGS=-DMH_DIAG_TILES): the shipped library does not contain these kernels
-    if constexpr (!B_KMAJOR) {   // diagnostic builds: NT only, fc1 (GELU) and plain bf16 epilogues
-        if (diag == 1 && epi == EPI_GELU) { hipLaunchKernelGGL((gemm_pp_kernel<false, EPI_GELU, 1>), g, b, 0, s, p); return; }
-        if (diag == 2 && epi == EPI_GELU) { hipLaunchKernelGGL((gemm_pp_kernel<false, EPI_GELU, 2>), g, b, 0, s, p); return; }
-        if (diag == 3 && epi == EPI_GELU) { hipLaunchKernelGGL((gemm_pp_kernel<false, EPI_GELU, 3>), g, b, 0, s, p); return; }
-        if (diag == 4 && epi == EPI_GELU) { hipLaunchKernelGGL((gemm_pp_kernel<false, EPI_GELU, 4>), g, b, 0, s, p); return; }
-        if (diag == 5 && epi == EPI_GELU) { hipLaunchKernelGGL((gemm_pp_kernel<false, EPI_GELU, 5>), g, b, 0, s, p); return; }
-        if (diag == 1 && epi == EPI_BF16) { hipLaunchKernelGGL((gemm_pp_kernel<false, EPI_BF16, 1>), g, b, 0, s, p); return; }
-    }
-#else
-    (void)diag;
-#endif
     switch (epi) {
         case EPI_BF16: hipLaunchKernelGGL((gemm_pp_kernel<B_KMAJOR, EPI_BF16>), g, b, 0, s, p); break;
         case EPI_GELU: hipLaunchKernelGGL((gemm_pp_kernel<B_KMAJOR, EPI_GELU>), g, b, 0, s, p); break;
@@ -388,35 +342,29 @@ static int pp_epilogue(int flags) {
     return -1;
 }
 
-// Everything the kernel asks of a problem (mh_gemm_bf16_resolve_tile): NT / NN, whole K steps and at least the EPI_STEPS that carry an
-// epilogue, whole tiles along N (the B tile base is not clipped), one of the four epilogue forms, and every buffer descriptor's tiles
-// (A, B, C, residual / aux) inside the 2 GiB range.
+// Everything the kernel asks of a problem (mh_gemm_bf16_resolve_tile): the tile id MH_TILE_PP_128 itself (MH_TILE_PP_128_DIAG1..5 are
+// retired ids of ablation builds that wrote wrong outputs on purpose: declined), NT / NN, whole K steps and at least the EPI_STEPS that
+// carry an epilogue, whole tiles along N (the B tile base is not clipped), one of the four epilogue forms, and every buffer
+// descriptor's tiles (A, B, C, residual / aux) inside the 2 GiB range.
 bool gemm_pp_serves(int tile, int layout, const GemmParams& p) {
-    const int epi = pp_epilogue(p.flags), diag = tile - MH_TILE_PP_128;
-#ifndef MH_DIAG_TILES
-    if (diag != 0) return false;   // MH_TILE_PP_128_DIAG1..5 write wrong outputs on purpose: compiled only under -DMH_DIAG_TILES
-#else
-    if (diag != 0 && (layout != 0 || !(epi == EPI_GELU || (epi == EPI_BF16 && diag == 1)))) return false;   // no such ablation build
-#endif
+    const int epi = pp_epilogue(p.flags);
+    if (tile != MH_TILE_PP_128) return false;
     if (epi < 0 || layout == 2 || p.K % BK != 0 || p.K < EPI_STEPS * BK || p.N % BN != 0) return false;
     const long rows = (long)ceil_div(p.M, BM) * BM;
     return gemm_in_reach(rows * p.lda * 2) && gemm_in_reach((long)(layout == 1 ? p.K : p.N) * p.ldb * 2) &&
            gemm_in_reach(rows * p.ldc * (epi == EPI_F32 ? 4 : 2)) && gemm_in_reach(epi == EPI_F32 ? rows * p.ldr * 4 : rows * p.ldaux);
 }
 
+// Fully persistent: up to 512 workgroups walk all tiles.  (Round 3 also limited a workgroup to n tiles -- shorter-lived workgroups let
+// the dispatcher interleave another stream's kernel sooner, at one exposed epilogue per n tiles: n = 3 changed nothing in any phase of
+// the step, profiles/README.md.)
 int gemm_pp_launch(int tile, int layout, GemmParams& p, hipStream_t stream) {
+    (void)tile;   // (gemm_pp_serves: MH_TILE_PP_128)
     p.tiles_m = ceil_div(p.M, BM); p.tiles_n = p.N / BN; p.k_per_split = p.K; p.fast = 1;
     gemm_set_extents(p, layout);
     const int tiles = p.tiles_m * p.tiles_n;
-    // MH_PP_TILES_PER_WG (build time): 0 = fully persistent (512 workgroups walk all tiles); n > 0: a workgroup walks at most n tiles
-    // (shorter-lived workgroups let the dispatcher interleave another stream's kernel sooner, at one exposed epilogue per n tiles)
-#ifndef MH_PP_TILES_PER_WG
-#define MH_PP_TILES_PER_WG 0
-#endif
-    int grid = tiles >= 512 ? 512 : (tiles + 7) / 8 * 8;   // two workgroups per CU; a multiple of 8 (XCD runs)
-    if (MH_PP_TILES_PER_WG > 0) grid = max(grid, ((tiles + MH_PP_TILES_PER_WG - 1) / MH_PP_TILES_PER_WG + 7) / 8 * 8);
-    if (layout == 1) launch_pp<true>(pp_epilogue(p.flags), grid, p, stream);
-    else launch_pp<false>(pp_epilogue(p.flags), grid, p, stream, tile - MH_TILE_PP_128);
+    const int grid = tiles >= 512 ? 512 : (tiles + 7) / 8 * 8;   // two workgroups per CU; a multiple of 8 (XCD runs)
+    for_layout(layout, [&](auto, auto b_kmajor_c) { launch_pp<decltype(b_kmajor_c)::value>(pp_epilogue(p.flags), grid, p, stream); });
     MH_LAUNCH_CHECK();
     return 0;
 }

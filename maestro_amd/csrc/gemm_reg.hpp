@@ -14,8 +14,6 @@ constexpr int TILE_BYTES = 128 * 64 * 2;  // one operand tile, 16 KiB
 
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
 
-__device__ __forceinline__ int kmajor_f(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-
 // ---- global -> registers (4 x 16 B per thread per operand tile)
 // NI = 16-byte pieces per thread = (tile rows) / 32 for a K-minor operand (4: 128 rows; 2: 64; 6: 192); K-major tiles are 128 wide
 template <bool KMAJOR, int NI = 4>
@@ -86,7 +84,7 @@ __device__ __forceinline__ void store_tile(unsigned char* tile, const u32x4 (&v)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = kk + 16 * i;
-            *reinterpret_cast<u32x4*>(tile + k * 256 + ((((c >> 1) ^ kmajor_f(k)) << 5) | ((c & 1) << 4))) = v[i];
+            *reinterpret_cast<u32x4*>(tile + k * 256 + ((((c >> 1) ^ kmajor_sw(k)) << 5) | ((c & 1) << 4))) = v[i];
         }
     }
 }
@@ -103,9 +101,9 @@ __device__ __forceinline__ bf16x8 read_frag(const unsigned char* tile, int rc0, 
         const int k_lo = 32 * s + 8 * g + qrow, k_hi = k_lo + 4;
         const lds_u8* base = (const lds_u8*)tile;
         s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) s16x4*)(base + k_lo * 256 + (((q ^ kmajor_f(k_lo)) << 5) + p * 8)));
+            (__attribute__((address_space(3))) s16x4*)(base + k_lo * 256 + (((q ^ kmajor_sw(k_lo)) << 5) + p * 8)));
         s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) s16x4*)(base + k_hi * 256 + (((q ^ kmajor_f(k_hi)) << 5) + p * 8)));
+            (__attribute__((address_space(3))) s16x4*)(base + k_hi * 256 + (((q ^ kmajor_sw(k_hi)) << 5) + p * 8)));
         s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         return __builtin_bit_cast(bf16x8, r);
     }

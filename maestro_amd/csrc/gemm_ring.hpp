@@ -27,7 +27,6 @@ typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ int kminor_sw(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
-__device__ __forceinline__ int kmajor_sw(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
 
 // Per-lane source byte offsets (relative to the operand base at k = 0) of the NP DMA pieces a wave issues per K step for
 // an operand tile of BX rows / columns (NW waves share its BX / 16 pieces).
@@ -67,8 +66,5 @@ __device__ __forceinline__ bf16x8 read_frag(const unsigned char* img, int rc0, i
         return __builtin_bit_cast(bf16x8, r);
     }
 }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 }  // namespace

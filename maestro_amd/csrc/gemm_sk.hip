@@ -1,8 +1,8 @@
 // Stream-K bf16 GEMM for gfx950: ONE four-wave workgroup per CU, (32 MT) x 128 x 64 tiles with a (16 MT) x 64 wave tile,
 // a hand-placed software pipeline, and an in-kernel fix-up of the tiles that two or more workgroups share
 // (mh_gemm_bf16_sk; tiles MH_TILE_SK_192 / MH_TILE_SK_256).  Written for the long-K, narrow-N problems of the transformer
-// blocks -- fc2, out-proj and three of the four dgrads: the nn.Linear call sites of vit_pytorch's Attention / FeedForward
-// constructed at /root/reference/maestro/ssl/mae.py:135-174 -- whose 128 x 128 tilings leave a quarter of the workgroup
+// blocks -- fc2, out-proj and three of the four dgrads: the nn.Linears of the reference model's Attention / FeedForward
+// blocks -- whose 128 x 128 tilings leave a quarter of the workgroup
 // slots empty (M = 8192, N = 768: 384 tiles on 512 slots) and whose 64 x 64 wave tiles read 0.5 LDS fragments per MFMA.
 //
 // Work split, hand-off of the shared tiles' partials and the epilogues: gemm_sk_common.hpp.
@@ -45,8 +45,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_sk_kernel(GemmParams p, SkArgs sk)
     };
 
     // ---- operand stream: loop-invariant per-thread byte offsets + a uniform cursor (segment, K step)
-    const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra_src = buffer_rsrc(p.A, (int)p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rb_src = buffer_rsrc(p.B, (int)p.b_bytes);
     const int a_v0 = ((tid >> 3) * p.lda + (tid & 7) * 8) * 2;
     const int b_v0 = B_KMAJOR ? ((tid >> 4) * p.ldb + (tid & 15) * 8) * 2 : ((tid >> 3) * p.ldb + (tid & 7) * 8) * 2;
     const int a_i = 32 * p.lda * 2, b_i = (B_KMAJOR ? 16 : 32) * p.ldb * 2;
@@ -248,7 +248,6 @@ extern "C" int mh_gemm_bf16_sk(int tile, int layout, int M, int N, int K, const 
     if (epi < 0) return -2;                                                // -2: not served (the caller picks another tile)
     MH_CHECK_ARG(epi != SK_EPI_F32 || (bias && res && ldr % 4 == 0 && ldc % 4 == 0), "mh_gemm_bf16_sk: fp32 epilogue needs bias, res, ldr / ldc %% 4");
     MH_CHECK_ARG(epi != SK_EPI_BF16 || ldc % 8 == 0, "mh_gemm_bf16_sk: bf16 output needs ldc %% 8 == 0");
-    const bool b_kmajor = layout == 1;
     GemmParams p;
     gemm_fill(p, M, N, K, A, lda, B, ldb, C, ldc, flags, bias, res, ldr, nullptr, nullptr, 0, nullptr);
     if (tile == MH_TILE_SK_DMA_256) {
@@ -270,8 +269,11 @@ extern "C" int mh_gemm_bf16_sk(int tile, int layout, int M, int N, int K, const 
     sk.tiles = p.tiles_m * p.tiles_n;
     sk.P = (int)std::min<long>(grid, (long)sk.tiles * sk.nk);
     hipStream_t s = (hipStream_t)stream;
-    if (mt == 6) { if (b_kmajor) launch_sk<true, 6>(epi, p, sk, s); else launch_sk<false, 6>(epi, p, sk, s); }
-    else { if (b_kmajor) launch_sk<true, 8>(epi, p, sk, s); else launch_sk<false, 8>(epi, p, sk, s); }
+    for_layout(layout, [&](auto, auto b_kmajor_c) {
+        constexpr bool BKM = decltype(b_kmajor_c)::value;
+        if (mt == 6) launch_sk<BKM, 6>(epi, p, sk, s);
+        else launch_sk<BKM, 8>(epi, p, sk, s);
+    });
     MH_LAUNCH_CHECK();
     return 0;
 }

@@ -61,21 +61,14 @@ struct SkSplit {
     __device__ __forceinline__ int first_owner(const SkArgs& sk, int tile) const { return (int)((((long)tile * nk + 1) * sk.P - 1) / U); }
 };
 
-// Lane id without a live register: the work-item id VGPR need not survive the K loop (the eight-wave kernel spilled it and
-// reloaded it from scratch -- behind a vmcnt(0) that drained the DMA ring -- in every K step)
-__device__ __forceinline__ int sk_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-__device__ __forceinline__ void sk_swap16(uint32_t& a, uint32_t& b) {
-    const u32x2 r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-
 struct SkEpiDesc {
     __amdgpu_buffer_rsrc_t c, res, bias, ws;
 };
 template <int EPI>
 __device__ __forceinline__ SkEpiDesc sk_epi_desc(const GemmParams& p, const SkArgs& sk, long slot_bytes) {
     SkEpiDesc d;
+    // (the builtin written out: through buffer_rsrc / matrix_bytes the fp32-epilogue kernels compute M - 1 and the two extents in
+    //  another order -- 14 to 860 instruction lines move, the eight-wave kernels change length)
     d.c = __builtin_amdgcn_make_buffer_rsrc(p.C, (short)0, (int)(((long)(p.M - 1) * p.ldc + p.N) * (EPI == SK_EPI_F32 ? 4 : 2)), 0x00020000);
     d.res = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, (short)0, EPI == SK_EPI_F32 ? (int)(((long)(p.M - 1) * p.ldr + p.N) * 4) : 0,
                                               0x00020000);
@@ -89,8 +82,7 @@ __device__ __forceinline__ SkEpiDesc sk_epi_desc(const GemmParams& p, const SkAr
 // the descriptors (the voffset carries the whole (row, column) offset): no exec-mask branches.
 template <int MT, int EPI>
 __device__ __forceinline__ void sk_epilogue(const GemmParams& p, const SkEpiDesc& d, const f32x4 (&acc)[4][MT], int row0, int col0) {
-    int lane = sk_lane();
-    asm volatile("" : "+v"(lane));     // opaque: the per-lane offsets below are computed HERE, not hoisted into (and kept live across) the K loop
+    const int lane = lane_id_opaque();   // the per-lane offsets below are computed HERE, not hoisted into (and kept live across) the K loop
     const int l = lane & 63, g = l >> 4, lm = l & 15;
     const int row = row0 + lm;
     if constexpr (EPI == SK_EPI_F32) {
@@ -152,8 +144,8 @@ __device__ __forceinline__ void sk_epilogue(const GemmParams& p, const SkEpiDesc
                 const f32x4 vx = acc[2 * jp][i], vy = acc[2 * jp + 1][i];
                 uint32_t x0 = pack_bf2(vx[0], vx[1]), x1 = pack_bf2(vx[2], vx[3]);
                 uint32_t y0 = pack_bf2(vy[0], vy[1]), y1 = pack_bf2(vy[2], vy[3]);
-                sk_swap16(x0, y0);
-                sk_swap16(x1, y1);
+                swap16(x0, y0);
+                swap16(x1, y1);
                 __builtin_amdgcn_raw_buffer_store_b128((u32x4){x0, x1, y0, y1}, d.c, ((row + 16 * i) * p.ldc + col_swp + 32 * jp) * 2, 0, 0);
             }
     }
@@ -162,8 +154,7 @@ __device__ __forceinline__ void sk_epilogue(const GemmParams& p, const SkEpiDesc
 // The partial tile of a workgroup of NTHR threads in accumulator order (4 KiB per wave instruction): slot bytes = 4 MT NTHR 16.
 template <int MT, int NTHR>
 __device__ __forceinline__ void sk_store_partial(const SkEpiDesc& d, const f32x4 (&acc)[4][MT], int slot, int wave) {
-    int lane = sk_lane();
-    asm volatile("" : "+v"(lane));
+    const int lane = lane_id_opaque();
     const int lane_off = (wave * 64 + lane) * 16;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -177,8 +168,7 @@ __device__ __forceinline__ void sk_store_partial(const SkEpiDesc& d, const f32x4
 // conditional and the eight-wave kernel (256 registers per lane) spilled ~90 of them -- into the K loop's fragment addresses.
 template <int MT, int NTHR>
 __device__ __forceinline__ void sk_add_partials(const SkEpiDesc& d, f32x4 (&acc)[4][MT], int first, int last, int wave) {
-    int lane = sk_lane();
-    asm volatile("" : "+v"(lane));
+    const int lane = lane_id_opaque();
     const int lane_off = (wave * 64 + lane) * 16;
     constexpr int CH = MT >= 8 ? 4 : MT;      // row blocks per pass (the eight-wave tile has 256 registers per lane: 16 + 16 temporaries)
 #pragma unroll

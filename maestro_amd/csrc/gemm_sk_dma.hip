@@ -1,8 +1,8 @@
 // Stream-K on the eight-wave 256 x 256 x 32 LDS-DMA tile (mh_gemm_bf16_sk, tile MH_TILE_SK_DMA_256): the main loop of gemm_dma.hip
 // -- a 4-stage ring filled by buffer_load ... lds, two wave groups half a K step out of phase, 128 x 64 wave tiles -- run by
 // PERSISTENT workgroups (one per CU) over an even split of tiles x (K / 32) units, for the long-K, narrow-N problems of the
-// transformer blocks (fc2, out-proj, the fc1 / qkv / out-proj dgrads: the nn.Linear call sites of vit_pytorch's Attention /
-// FeedForward built at /root/reference/maestro/ssl/mae.py:135-174).  Why this tile: it is the structure of this tree that turns a
+// transformer blocks (fc2, out-proj, the fc1 / qkv / out-proj dgrads: the nn.Linears of the reference model's Attention /
+// FeedForward blocks).  Why this tile: it is the structure of this tree that turns a
 // CU-second into the most FLOPs (two waves per SIMD cover each other's LDS / DMA issue; 0.375 fragment reads per MFMA; half the
 // operand bytes per FLOP of a 128 x 128 tile: 1.2-1.35 PFLOP/s on long K), but an N = 768 output has 3 tile columns -- 96 tiles for
 // 256 CUs at M = 8192 -- and its one-tile-per-workgroup launch pays a ring fill and an exposed epilogue per tile.  Here
@@ -49,8 +49,8 @@ __global__ __launch_bounds__(TSK::NT, 1) void gemm_sk_dma_kernel(GemmParams p, S
     };
 
     // ---- DMA stream: per-lane source offsets relative to a tile's origin + a uniform cursor (segment, K step)
-    const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra_src = buffer_rsrc(p.A, (int)p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rb_src = buffer_rsrc(p.B, (int)p.b_bytes);
     int va[PA], vb[PB];
     piece_offsets<false, T::BM, NW, PA>(p.lda, 0, w, l, va);
     piece_offsets<B_KMAJOR, T::BN, NW, PB>(p.ldb, 0, w, l, vb);
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(TSK::NT, 1) void gemm_sk_dma_kernel(GemmParams p, S
         const bool fin = c_ke == nk;
         const int wf = (fin && c_kb > 0) ? sp.first_owner(sk, c_tile) : lw;
         if (wf < lw) {
-            if (w == 0 && sk_lane() == 0) sk_wait_flags(sk, wf, lw);
+            if (w == 0 && lane_id() == 0) sk_wait_flags(sk, wf, lw);
             __builtin_amdgcn_s_barrier();
         }
         sk_add_partials<MT, T::NT>(ed, acc, wf, lw, w);
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(TSK::NT, 1) void gemm_sk_dma_kernel(GemmParams p, S
             sk_store_partial<MT, T::NT>(ed, acc, lw, w);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave: its partial has left the CU
             __builtin_amdgcn_s_barrier();
-            if (w == 0 && sk_lane() == 0) __hip_atomic_store(sk.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (w == 0 && lane_id() == 0) __hip_atomic_store(sk.flags + lw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __builtin_amdgcn_sched_barrier(0);   // the zeros must not be materialised (in 128 NEW registers) above the epilogue's last uses
 #pragma unroll
@@ -199,7 +199,6 @@ __global__ __launch_bounds__(TSK::NT, 1) void gemm_sk_dma_kernel(GemmParams p, S
 
 int gemm_sk_dma_launch(int layout, int epi, GemmParams& p, void* workspace, int grid, void* stream) {
     using T = TSK;
-    const bool b_kmajor = layout == 1;
     if (p.K % BK != 0 || p.K < 4 * BK || p.N % T::BN != 0 || p.lda % 8 || p.ldb % 8) return -2;
     p.tiles_m = ceil_div(p.M, T::BM); p.tiles_n = p.N / T::BN; p.k_per_split = p.K; p.fast = 1;
     if (!sk_in_reach(layout, epi, p, T::BM)) return -2;
@@ -214,12 +213,10 @@ int gemm_sk_dma_launch(int layout, int epi, GemmParams& p, void* workspace, int 
     sk.P = (int)(grid < units ? grid : units);
     dim3 g(sk.P), b(T::NT);
     hipStream_t s = (hipStream_t)stream;
-    if (epi == SK_EPI_F32) {
-        if (b_kmajor) hipLaunchKernelGGL((gemm_sk_dma_kernel<true, SK_EPI_F32>), g, b, 0, s, p, sk);
-        else hipLaunchKernelGGL((gemm_sk_dma_kernel<false, SK_EPI_F32>), g, b, 0, s, p, sk);
-    } else {
-        if (b_kmajor) hipLaunchKernelGGL((gemm_sk_dma_kernel<true, SK_EPI_BF16>), g, b, 0, s, p, sk);
-        else hipLaunchKernelGGL((gemm_sk_dma_kernel<false, SK_EPI_BF16>), g, b, 0, s, p, sk);
-    }
+    for_layout(layout, [&](auto, auto b_kmajor_c) {
+        constexpr bool BKM = decltype(b_kmajor_c)::value;
+        if (epi == SK_EPI_F32) hipLaunchKernelGGL((gemm_sk_dma_kernel<BKM, SK_EPI_F32>), g, b, 0, s, p, sk);
+        else hipLaunchKernelGGL((gemm_sk_dma_kernel<BKM, SK_EPI_BF16>), g, b, 0, s, p, sk);
+    });
     return 0;
 }

@@ -303,11 +303,10 @@ def _pick_tile(layout, M, N, K, flags, args) -> int:  # noqa: N803
         forced = os.environ.get("MH_GEMM_TILE")
         if forced is not None:
             t = int(forced)
-            # the ablation builds of the ping-pong tile (MH_TILE_PP_128_DIAG1..5) leave out parts of the kernel: WRONG outputs.  The
-            # shipped library does not contain them (the C ABI returns -2); a library built with MH_BUILD_FLAGS=-DMH_DIAG_TILES does
-            if TILE_PP_128 < t <= TILE_PP_128 + 5 and os.environ.get("MH_ALLOW_DIAG_TILES") != "1":
-                raise HipExtensionError(f"MH_GEMM_TILE={t} selects a diagnostic build of the ping-pong tile that writes wrong "
-                                        "outputs (present only in a -DMH_DIAG_TILES library); set MH_ALLOW_DIAG_TILES=1 to run it on purpose")
+            # MH_TILE_PP_128_DIAG1..5: retired ids of ablation builds of the ping-pong tile; every library declines them (-2)
+            if TILE_PP_128 < t <= TILE_PP_128 + 5:
+                raise HipExtensionError(f"MH_GEMM_TILE={t} is a retired id (a diagnostic build of the ping-pong tile that wrote wrong "
+                                        "outputs): no library contains that kernel")
             return t
         dma = os.environ.get("MH_GEMM_DMA", "")[:1]
         if os.environ.get("MH_GEMM_PP", "")[:1] == "0" and dma == "":   # A/B: the round-2 rule (no persistent ping-pong tile)

@@ -1,5 +1,5 @@
-"""A/B aid: run a script of this repository against ANOTHER build of libmaestro_hip.so (same ABI, e.g. one compiled with
--DMH_GELU_TERMS=5):  python scripts/ab_lib.py <path/to/lib.so> <script.py> [script args ...]
+"""A/B aid: run a script of this repository against ANOTHER build of libmaestro_hip.so (same ABI, e.g. the parent
+commit's, or one compiled with MH_BUILD_FLAGS=-DMH_GUARD_NT_LOADS=1):  python scripts/ab_lib.py <path/to/lib.so> <script.py> [script args ...]
        python scripts/ab_lib.py <path/to/lib.so> -m pytest tests/test_kernels_gpu.py -k layernorm -q
 The library is loaded lazily by maestro_amd.hip, so pointing its path elsewhere before the first call is enough."""
 import os, runpy, sys

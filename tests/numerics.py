@@ -142,7 +142,7 @@ def gelu_grid():
 
 
 def gelu_cdf_pdf4_emulated(x: torch.Tensor, c1: float = 0.7478556):
-    """fp32 emulation of ``gelu_cdf_pdf4`` (csrc/common.hpp, MH_GELU_TERMS = 3) as written; ``c1`` is its first coefficient."""
+    """fp32 emulation of ``gelu_cdf_pdf4`` (csrc/common.hpp, the three-term form) as written; ``c1`` is its first coefficient."""
     x = x.float()
     f = torch.float32
     e = torch.exp2((x * x) * torch.tensor(-0.5 * 1.4426950408889634, dtype=f))

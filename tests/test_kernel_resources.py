@@ -15,7 +15,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "scripts"))
 
 # forms of the ping-pong GEMM that are built but not dispatched by default because they spill
-KNOWN_SPILLS = {"gemm_pp_kernel<true, 1, 0>", "gemm_pp_kernel<true, 2, 0>", "gemm_pp_kernel<false, 2, 0>"}
+KNOWN_SPILLS = {"gemm_pp_kernel<true, 1>", "gemm_pp_kernel<true, 2>", "gemm_pp_kernel<false, 2>"}
 
 
 @pytest.fixture(scope="module")
@@ -61,6 +61,35 @@ def test_attention_kernels_stay_inside_their_occupancy_step(kernels):
     for form, limit in limits.items():
         k = names.get(form)
         assert k is not None, (form, sorted(n for n in names if n.startswith("attn_")))
+        assert k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
+        assert k["vgpr_count"] <= limit, k
+
+
+def test_dispatched_gemm_kernels_stay_inside_their_occupancy_step(kernels):
+    """The GEMM kernels that the dispatch rule, the grouped weight-gradient launch and the fp8 / MX entry points run, by name,
+    spill-free, and inside the occupancy step their `__launch_bounds__` ask for: 512 registers per SIMD lane divided by the waves per
+    SIMD the bound implies (a workgroup of 256 threads is one wave per SIMD, one of 512 is two; 512 / 3 rounded down to the allocation
+    granule of 8 is 168).  The 256 x 256 fp8 tile's bound names two workgroups but its 128 KiB ring leaves room for one per CU, so its
+    step is the two waves per SIMD of that one workgroup.  profiles/gemm_straightline.md has the counts."""
+    names = {k["kernel"]: k for k in kernels}
+    limits = {}
+    for layout in ("false, false", "false, true"):
+        limits[f"gemm_kernel<{layout}, 2>"] = 168                       # __launch_bounds__(256, 3)
+        limits[f"gemm_kernel<{layout}, 4>"] = 256                       # (256, 2)
+        limits[f"gemm_kernel<{layout}, 6>"] = 256
+        limits[f"gemm_dma_kernel<Tile<2, 4, 4, 8>, {layout}, true>"] = 256   # (512, 1)
+    limits["gemm_kernel<true, true, 4>"] = 256
+    limits["gemm_dma_kernel<Tile<2, 4, 4, 8>, true, true, true>"] = 256
+    limits["gemm_dma_grouped_tn_kernel<Tile<2, 4, 4, 8>, true>"] = 256       # (512)
+    for epi in (0, 1, 3):                                                    # plain bf16, GELU, fp32 + residual; NT
+        limits[f"gemm_pp_kernel<false, {epi}>"] = 256                        # (256, 2)
+    for form in ("false, true", "true, false", "false, false"):             # MX, e5m2 A, e4m3 A
+        limits[f"gemm_fp8_kernel<Tile8<2, 4, 8, 2>, {form}>"] = 256          # (512, 2), one workgroup per CU by its LDS
+        limits[f"gemm_fp8_kernel<Tile8<2, 2, 4, 2>, {form}>"] = 256          # (256, 2)
+        limits[f"gemm_fp8_kernel<Tile8<2, 2, 4, 4>, {form}>"] = 512          # (256, 1)
+    for form, limit in limits.items():
+        k = names.get(form)
+        assert k is not None, (form, sorted(n for n in names if n.startswith(form.split("<")[0])))
         assert k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, k
         assert k["vgpr_count"] <= limit, k
 
