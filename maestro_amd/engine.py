@@ -690,7 +690,14 @@ class EngineBase:
             d = batch[f"{s.src}_dates"]
             if d.dtype != torch.int16 or not d.is_contiguous():     # (mh_date_features reads int16_t)
                 raise ValueError(f"batch['{s.src}_dates'] must be a contiguous int16 tensor [B, D, 3]")
-        batch = self._stable_inputs(batch)
+        batch = self._resize_inputs(self._stable_inputs(batch), sources)
+        self._staged = batch
+        self._cur_key = tuple(batch[k].data_ptr() for k in sorted(batch) if isinstance(batch[k], torch.Tensor))
+        return batch
+
+    def _resize_inputs(self, batch: dict, sources) -> dict:
+        """Rasters that do not arrive at ``image_size`` (or any raster, under an interpolating mode) resized into an engine-owned
+        buffer, which takes the raster's place in ``batch``."""
         for s in sources:
             img = batch[s.src]
             if tuple(img.shape[-2:]) != (s.S, s.S) or self.model.interpolate != "nearest":
@@ -702,8 +709,6 @@ class EngineBase:
                     buf = self.mb[s.name]["resized"] = torch.empty(self.B, s.Dates, s.C_src, s.S, s.S, dtype=F32, device=self.device)
                 hip.resize(img, buf, self.B * s.Dates * s.C_src, img.shape[-2], img.shape[-1], s.S, s.S, mode)
                 batch[s.src] = buf
-        self._staged = batch
-        self._cur_key = tuple(batch[k].data_ptr() for k in sorted(batch) if isinstance(batch[k], torch.Tensor))
         return batch
 
     def returned_batch(self, batch: dict) -> dict:

@@ -13,6 +13,7 @@ on their second run like the pretrain engine's, groups run on parallel HIP strea
 
 from __future__ import annotations
 
+import math
 import os
 from typing import NamedTuple
 
@@ -58,6 +59,58 @@ def parse_views(views) -> tuple:
     if not out or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 7 for v in out) or len(set(out)) != len(out):
         raise ValueError(f"views={views!r}: a non-empty sequence of distinct dihedral flags 0..7 or \"d4\"")
     return out
+
+
+BLENDS = ("flat", "linear")
+
+
+def scene_unit(sizes) -> int:
+    """Side of the prediction window in UNITS: the greatest common divisor of the model's raster sizes -- every input's
+    ``image_size`` and every segment target's ``G * P`` -- so that a raster of size ``S`` has ``S / W`` whole pixels per unit
+    (the reference's ``size_gcd`` / ``crop_gcd`` rule, ``conf/dataset/utils.py:99-109``, stated on the model's own sizes)."""
+    return math.gcd(*[int(s) for s in sizes])
+
+
+def check_scene(scene: dict, rasters: dict, W: int, stride=None, blend: str = "linear", device=None) -> tuple:  # noqa: N803
+    """The argument checks of ``SupervisedEngine.predict_scene``, all before any launch: ``rasters`` is ``{name: (image_size, dates,
+    channels)}``, ``device`` the engine's GPU (None: any GPU).  Returns ``(N, Hu, Wu, stride)``: the number of scenes, their
+    extent in units and the stride in units."""
+    extent = None
+    for src, (S, D, C) in rasters.items():  # noqa: N806
+        img, dates = scene.get(src), scene.get(f"{src}_dates")
+        if not isinstance(img, torch.Tensor) or img.dtype != F32 or not img.is_contiguous():
+            raise ValueError(f"scene[{src!r}] must be a contiguous float32 GPU tensor [N, {D}, {C}, Hu * q, Wu * q]")
+        q = S // W
+        if img.dim() != 5 or tuple(img.shape[1:3]) != (D, C) or img.shape[3] % q or img.shape[4] % q:
+            raise ValueError(f"scene[{src!r}] is {tuple(img.shape)}: expected [N, {D}, {C}, Hu * {q}, Wu * {q}] ({q} pixels per unit)")
+        here = (img.shape[0], img.shape[3] // q, img.shape[4] // q)
+        if extent is not None and here != extent[1]:
+            raise ValueError(f"scene[{src!r}] covers {here[0]} scenes of {here[1]} x {here[2]} units, scene[{extent[0]!r}] "
+                             f"{extent[1][0]} of {extent[1][1]} x {extent[1][2]}: the extents of the modalities disagree")
+        extent = extent or (src, here)
+        if not isinstance(dates, torch.Tensor) or dates.dtype != torch.int16 or not dates.is_contiguous() \
+                or tuple(dates.shape) != (here[0], D, 3):
+            raise ValueError(f"scene['{src}_dates'] must be a contiguous int16 tensor [{here[0]}, {D}, 3]")
+    if extent is None:
+        raise ValueError("the model has no input raster")
+    N, Hu, Wu = extent[1]  # noqa: N806
+    ref = scene.get("ref_date")
+    if not isinstance(ref, torch.Tensor) or ref.dtype != torch.int16 or not ref.is_contiguous() or tuple(ref.shape) != (N, 1, 3):
+        raise ValueError(f"scene['ref_date'] must be a contiguous int16 tensor [{N}, 1, 3]")     # (mh_date_features reads int16_t)
+    if N < 1 or Hu < W or Wu < W:
+        raise ValueError(f"a scene of {Hu} x {Wu} units is below one window of {W} x {W} units")
+    stride = max(1, W // 2) if stride is None else stride
+    if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= W:
+        raise ValueError(f"stride={stride!r}: 1 ... {W} units (a larger stride would leave units uncovered)")
+    if blend not in BLENDS:
+        raise ValueError(f"blend={blend!r}: \"flat\" or \"linear\"")
+    for k in [k for src in rasters for k in (src, f"{src}_dates")] + ["ref_date"]:
+        if not scene[k].is_cuda:
+            raise ValueError(f"scene[{k!r}] must be on the GPU; there is no CPU fallback")
+        index = None if device is None else torch.device(device).index
+        if device is not None and scene[k].device.index != (torch.cuda.current_device() if index is None else index):
+            raise ValueError(f"scene[{k!r}] is on {scene[k].device}, the engine on {device}: the kernels read it by address")
+    return N, Hu, Wu, stride
 
 
 class SupervisedEngine(EngineBase):
@@ -330,13 +383,7 @@ class SupervisedEngine(EngineBase):
         need_prob = probs or len(views) > 1
         for t in self.hb:
             self._predict_buffers(t, need_prob)
-        view = None
-        if not direct:
-            view = getattr(self, "_pv", None)
-            if view is None:
-                sources = [parts[0] for parts in self.model.src_specs.values()]
-                view = self._pv = dict(flags=torch.zeros(self.B, dtype=torch.uint8, device=self.device),
-                                       rasters={s.src: torch.empty_like(batch[s.src]) for s in sources})
+        view = None if direct else self._view_buffers(batch)
         key = (self._cur_key, probs, tuple(sorted(thr.items())))
         for i, v in enumerate(views):
             mode = "one" if len(views) == 1 else ("first" if i == 0 else "acc")
@@ -353,6 +400,159 @@ class SupervisedEngine(EngineBase):
                 hip.predict_finish(pb["prob"], len(views), act, pb["cls"], pb["conf"], self.B, C, pb["prob"].numel() // (self.B * C),
                                    threshold=thr[t], mean=pb["prob"] if probs else None)
             out[t] = Prediction(pb["cls"], pb["conf"], pb["prob"] if probs else None)
+        return out
+
+    def _view_buffers(self, batch: dict) -> dict:
+        """The flag bytes and the transformed rasters of a dihedral view (engine-owned, allocated when first needed)."""
+        view = getattr(self, "_pv", None)
+        if view is None:
+            sources = [parts[0] for parts in self.model.src_specs.values()]
+            view = self._pv = dict(flags=torch.zeros(self.B, dtype=torch.uint8, device=self.device),
+                                   rasters={s.src: torch.empty_like(batch[s.src]) for s in sources})
+        return view
+
+    # ------------------------------------------------------------------------------------------ scene prediction
+    def scene_geometry(self) -> dict:
+        """``W`` (the window side in units, ``scene_unit`` of this model's sizes), ``q`` = pixels per unit of every input raster
+        and ``qt`` = pixels per unit of every segment target."""
+        sources = [parts[0] for parts in self.model.src_specs.values()]
+        seg = {t: self.ref["G"] * hb["P"] for t, hb in self.hb.items() if hb["kind"] == "segment"}
+        W = scene_unit([s.S for s in sources] + list(seg.values()))  # noqa: N806
+        return dict(W=W, q={s.src: s.S // W for s in sources}, qt={t: S // W for t, S in seg.items()})
+
+    def _scene_buffers(self, scene: dict, sources, table, N: int, Hu: int, Wu: int, blend: str) -> dict:  # noqa: N803
+        """Engine-owned state of ``predict_scene``: the window batch the gather writes, the uploaded window table and the fixed
+        rows of the current batch, the blend profiles, the canvases and the window grids.  Whatever depends on the scene's
+        extent is allocated again when that changes."""
+        dev, B, geo = self.device, self.B, self.scene_geometry()  # noqa: N806
+        ps = self.__dict__.setdefault("_ps", dict(win={}, profile={}, canvas={}, grid={}))
+        for k in [k for s in sources for k in (s.src, f"{s.src}_dates")] + ["ref_date"]:
+            shape = (B,) + tuple(scene[k].shape[1:])
+            if k in geo["q"]:                                              # a raster: one window of it per slot
+                shape = shape[:3] + (geo["W"] * geo["q"][k],) * 2
+            if k not in ps["win"] or ps["win"][k].shape != shape or ps["win"][k].dtype != scene[k].dtype:
+                ps["win"][k] = torch.empty(shape, dtype=scene[k].dtype, device=dev)
+        if "cur" not in ps:
+            ps["cur"], ps["cur_n"] = torch.zeros(B, 4, dtype=I32, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)
+        ps["table"] = torch.from_numpy(table).to(dev)                  # the whole plan, uploaded once
+        ps["table_n"] = ps["table"][:, :, 0].to(torch.int64).contiguous()
+        n_rows = table.shape[0] * B
+        for t, hb in self.hb.items():
+            C = hb["C"]  # noqa: N806
+            if hb["kind"] == "segment":
+                S, q = self.ref["G"] * hb["P"], geo["qt"][t]  # noqa: N806
+                if (S, blend) not in ps["profile"]:
+                    ps["profile"][S, blend] = torch.from_numpy(hip.blend_profile(S, blend)).to(dev)
+                cv = ps["canvas"].get(t)
+                if cv is None or cv["acc"].shape != (N, C, Hu * q, Wu * q):
+                    e = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
+                    cv = ps["canvas"][t] = dict(acc=e(N, C, Hu * q, Wu * q), wsum=e(N, Hu * q, Wu * q),
+                                                cls=e(N, Hu * q, Wu * q, dt=torch.uint8), conf=e(N, Hu * q, Wu * q))
+            else:
+                pb = self._pb[t]
+                gr = ps["grid"].get(t)
+                if gr is None or gr["cls"].shape[0] != n_rows:
+                    gr = ps["grid"][t] = {k: torch.empty((n_rows,) + tuple(pb[k].shape[1:]), dtype=pb[k].dtype, device=dev)
+                                          for k in ("cls", "conf", "prob")}
+        return ps
+
+    def predict_scene(self, scene: dict, stride: int | None = None, blend: str = "linear", views=(0,), probs: bool = False,
+                      threshold=0.5) -> dict:
+        """Predictions ``{target: Prediction(cls, conf, probs)}`` for whole SCENES: rasters larger than the model's window, cut
+        into sliding windows on the device, predicted ``B`` windows at a time and blended into one canvas per segment target.
+
+        ``scene`` is a batch without targets whose rasters are ``[N, D, C, Hu * q, Wu * q]`` (float32, contiguous, on the GPU):
+        ``N`` scenes of ``Hu x Wu`` UNITS, a unit being ``1 / W`` of the model's window (``scene_geometry``: ``W`` is the greatest
+        common divisor of every ``image_size`` and every segment target's size, ``q = image_size / W`` the raster's pixels per
+        unit), with ``<m>_dates`` ``[N, D, 3]`` int16 and ``ref_date`` ``[N, 1, 3]``; ``Hu, Wu >= W``.  Rasters are taken at the
+        model's own pixel scale: resampling a scene is the caller's job.
+
+        Windows (``hip.scene_windows``): starts ``0, stride, 2 stride, ...`` along each axis and one last, clamped window that
+        ends at the edge; ``stride`` in units, ``1 .. W``, default ``max(1, W // 2)``; scene-major, row-major; the last batch is
+        padded with slots that blend nothing.  Per batch ONE captured segment: ``mh_window_gather`` per raster into the
+        engine's window batch, the date rows by the slot's scene, the launch list of ``predict`` for every view of ``views``,
+        ``mh_predict_blend`` per segment target with ``scale = 1 / len(views)``.  ``blend``: ``"linear"`` (a separable tent,
+        ``hip.blend_profile``) or ``"flat"``; a canvas pixel is the weighted mean of the windows that cover it, summed in window
+        order whatever ``B`` is (csrc/scene_abi.hpp).  One ``mh_predict_blend_finish`` per segment target after the last batch.
+
+        segment: ``cls`` u8 ``[N, Hc, Wc]``, ``conf`` f32 ``[N, Hc, Wc]``, ``probs`` f32 ``[N, C, Hc, Wc]`` or None, ``Hc = Hu * q_t``
+        -- ``N * C * Hc * Wc * 4`` bytes of canvas per target, resident for the call: cutting a mosaic into scenes that fit is the
+        caller's job.  classif / multilabel targets are not blended: the per-window results of ``predict`` on the window grid,
+        ``[N, ny, nx]`` (``probs`` ``[N, ny, nx, C]``) / ``[N, ny, nx, C]``.
+
+        Nothing is read on the host.  The returned tensors are the engine's own buffers (the next ``predict_scene`` overwrites
+        them); weights, gradients, ``loss_acc``, optimizer and metric state are untouched; ``backward()`` raises until the next
+        ``forward``.  ValueError before any launch: extents that disagree between the rasters, an extent below one window, a
+        stride outside ``1 .. W``, a raster that is not float32 / contiguous / on the GPU, an unknown ``blend``."""
+        views = parse_views(views)
+        sources = [parts[0] for parts in self.model.src_specs.values()]
+        geo = self.scene_geometry()
+        W, B = geo["W"], self.B  # noqa: N806
+        N, Hu, Wu, stride = check_scene(scene, {s.src: (s.S, s.Dates, s.C_src) for s in sources}, W, stride, blend, self.device)  # noqa: N806
+        thr = {t: float(threshold[t] if isinstance(threshold, dict) else threshold) for t in self.hb}
+        ys, xs = hip.scene_axis_starts(Hu, W, stride), hip.scene_axis_starts(Wu, W, stride)
+        table = hip.scene_table(N, [(y, x) for y in ys for x in xs], B)
+        if self.store.refresh_half():
+            self._pack_conv_weights()
+        self._saved_for_backward = False
+        for t in self.hb:
+            self._predict_buffers(t, True)
+        ps = self._scene_buffers(scene, sources, table, N, Hu, Wu, blend)
+        win, cur, cur_n = ps["win"], ps["cur"], ps["cur_n"]
+        view = None if views == (0,) else self._view_buffers(win)
+        seg = {t: (ps["canvas"][t], ps["profile"][self.ref["G"] * hb["P"], blend]) for t, hb in self.hb.items()
+               if hb["kind"] == "segment"}
+        for cv, _ in seg.values():
+            cv["acc"].zero_()
+            cv["wsum"].zero_()
+
+        def launches(rows):
+            for s in sources:
+                img = scene[s.src]
+                hip.window_gather(img, win[s.src], cur, rows, B, N, s.Dates * s.C_src, img.shape[3], img.shape[4], s.S, geo["q"][s.src])
+                torch.index_select(scene[f"{s.src}_dates"], 0, cur_n, out=win[f"{s.src}_dates"])
+            torch.index_select(scene["ref_date"], 0, cur_n, out=win["ref_date"])
+            batch = self._staged = self._resize_inputs(dict(win), sources)
+            for i, v in enumerate(views):
+                if view is not None:
+                    view["flags"].fill_(v)
+                mode = "one" if len(views) == 1 else ("first" if i == 0 else "acc")
+                self._predict_view_launches(batch, view, mode, True, thr)
+            for t, hb in self.hb.items():
+                pb = self._pb[t]
+                if t in seg:
+                    cv, profile = seg[t]
+                    S = self.ref["G"] * hb["P"]  # noqa: N806
+                    hip.predict_blend(pb["prob"], 1.0 / len(views), profile, cur, rows, cv["acc"], cv["wsum"], B, N, hb["C"], S,
+                                      geo["qt"][t], cv["acc"].shape[2], cv["acc"].shape[3])
+                elif len(views) > 1:
+                    hip.predict_finish(pb["prob"], len(views), self._head_geometry(hb)[0], pb["cls"], pb["conf"], B, hb["C"], 1,
+                                       threshold=thr[t], mean=pb["prob"])
+
+        # the addresses the captured segment bakes in, and everything that shapes its launch list
+        key = (tuple((scene[k].data_ptr(), win[k].data_ptr()) for k in sorted(win)), tuple(cv["acc"].data_ptr() for cv, _ in seg.values()),
+               tuple(p.data_ptr() for _, p in seg.values()), N, Hu, Wu, views, tuple(sorted(thr.items())))
+        for i in range(table.shape[0]):
+            cur.copy_(ps["table"][i])         # in front of the segment: a replayed graph reads the rows of THIS batch
+            cur_n.copy_(ps["table_n"][i])
+            self._segment("sup_predict_scene", key, lambda i=i: launches(table[i]))
+            for t, gr in ps["grid"].items():  # per-window results onto the window grid (pad slots land behind its end)
+                for k in ("cls", "conf") + (("prob",) if probs else ()):
+                    gr[k][i * B: (i + 1) * B].copy_(self._pb[t][k])
+        out = {}
+        ny, nx = len(ys), len(xs)
+        for t, hb in self.hb.items():
+            C = hb["C"]  # noqa: N806
+            if t in seg:
+                cv = seg[t][0]
+                hip.predict_blend_finish(cv["acc"], cv["wsum"], cv["cls"], cv["conf"], cv["acc"] if probs else None, N, C,
+                                         cv["wsum"][0].numel())
+                out[t] = Prediction(cv["cls"], cv["conf"], cv["acc"] if probs else None)
+                continue
+            gr = ps["grid"][t]
+            per = (C,) if hb["kind"] == "multilabel_classif" else ()
+            out[t] = Prediction(gr["cls"][: N * ny * nx].view(N, ny, nx, *per), gr["conf"][: N * ny * nx].view(N, ny, nx, *per),
+                                gr["prob"][: N * ny * nx].view(N, ny, nx, C) if probs else None)
         return out
 
     # ------------------------------------------------------------------------------------------ backward

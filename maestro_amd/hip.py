@@ -49,6 +49,10 @@ def lib() -> ctypes.CDLL:
         _lib.mh_predict_view.argtypes = [vp, vp, ci, ctypes.c_float, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]     # csrc/predict_abi.hpp
         _lib.mh_predict_finish.argtypes = [vp, ctypes.c_float, ci, ctypes.c_float, vp, vp, vp, ci, ci, ctypes.c_long, vp]
         _lib.mh_predict_view.restype = _lib.mh_predict_finish.restype = ci
+        _lib.mh_window_gather.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]                          # csrc/scene_abi.hpp
+        _lib.mh_predict_blend.argtypes = [vp, ctypes.c_float, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+        _lib.mh_predict_blend_finish.argtypes = [vp, vp, vp, vp, vp, ci, ci, ctypes.c_long, vp]
+        _lib.mh_window_gather.restype = _lib.mh_predict_blend.restype = _lib.mh_predict_blend_finish.restype = ci
         _lib.mh_reduce_ordered.argtypes = [vp, vp, ci, vp, ci, vp]          # deterministic forms
         _lib.mh_colsum_partial_rows.argtypes = [ci]
         _lib.mh_masked_loss_partial_size.argtypes = _lib.mh_embed_bwd_partial_rows.argtypes = [ci, ci]
@@ -1191,6 +1195,155 @@ def predict_reference(logits, flags, act, *, g=1, P=1, C=None, threshold=0.5, pr
         p = (e * (1 / s)[:, None]).astype(dtype) if dtype == np.float32 else e / s[:, None]
         conf = (1 / s).astype(dtype)
     return (p if prob is None else (prob + p).astype(dtype)), cls, conf
+
+
+# ---- scene prediction (csrc/scene.hip, declarations in csrc/scene_abi.hpp)
+SCENE_MAX_SLOTS, SCENE_MAX_S, SCENE_UNCOVERED = 1024, 4096, 255      # MH_SCENE_MAX_SLOTS, MH_SCENE_MAX_S, MH_SCENE_UNCOVERED
+
+
+def scene_axis_starts(U: int, W: int, stride: int | None = None) -> list:  # noqa: N803
+    """Window starts along one axis of ``U`` units for windows of ``W`` units: ``0, stride, 2 stride, ...`` while
+    ``start + W < U``, then one last start at ``U - W`` (the clamped window: it reaches the edge whatever the stride)."""
+    stride = max(1, W // 2) if stride is None else stride
+    if W < 1 or U < W:
+        raise ValueError(f"scene_windows: an extent of {U} units is below one window of {W}")
+    if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= W:
+        raise ValueError(f"scene_windows: stride={stride!r} (1 ... W = {W} units: a larger stride would leave units uncovered)")
+    starts = list(range(0, U - W, stride))
+    return starts + [U - W]
+
+
+def scene_windows(Hu: int, Wu: int, W: int, stride: int | None = None) -> list:  # noqa: N803
+    """The windows ``(y0, x0)`` of one ``Hu x Wu``-unit scene in row-major order (a pure host function): ``scene_axis_starts`` on
+    both axes.  ``stride`` in ``1 .. W``, default ``max(1, W // 2)``."""
+    ys, xs = scene_axis_starts(Hu, W, stride), scene_axis_starts(Wu, W, stride)
+    return [(y, x) for y in ys for x in xs]
+
+
+def scene_table(N: int, windows, B: int):  # noqa: N803
+    """The window table of ``N`` equally sized scenes as int32 ``[n_batches, B, 4]`` rows ``(n, y0, x0, on)``: scene-major, then the
+    order of ``windows``; batches are ``B`` consecutive windows and the last batch is padded with slots that repeat ITS first
+    window with ``on = 0`` (gathered like any other, so the model sees finite data; blended nowhere)."""
+    import numpy as np
+    if N < 1 or B < 1 or not windows:
+        raise ValueError(f"scene_table: N = {N}, B = {B}, {len(windows)} windows")
+    rows = [(n, y, x, 1) for n in range(N) for (y, x) in windows]
+    n_batches = -(-len(rows) // B)
+    first = rows[(n_batches - 1) * B]
+    rows += [(first[0], first[1], first[2], 0)] * (n_batches * B - len(rows))
+    return np.asarray(rows, dtype=np.int32).reshape(n_batches, B, 4)
+
+
+def blend_profile(S: int, kind: str = "linear"):  # noqa: N803
+    """The separable window weight as numpy f32 ``[S]`` (a pixel weighs ``profile[y] * profile[x]``): ``"flat"`` all ones,
+    ``"linear"`` the tent ``min(i + 1, S - i) / ceil(S / 2)`` -- 1 in the middle, never zero at the rim."""
+    import numpy as np
+    if S < 1:
+        raise ValueError(f"blend_profile: S = {S}")
+    if kind == "flat":
+        return np.ones(S, dtype=np.float32)
+    if kind == "linear":
+        i = np.arange(S)
+        return np.minimum(i + 1, S - i).astype(np.float32) / np.float32(-(-S // 2))
+    raise ValueError(f"blend={kind!r}: \"flat\" or \"linear\"")
+
+
+def _scene_host_table(what, table_host, B):  # noqa: N803
+    import numpy as np
+    t = np.ascontiguousarray(table_host, dtype=np.int32)
+    if t.size != 4 * B:
+        raise HipExtensionError(f"{what}: the host window table must hold {B} rows (n, y0, x0, on)")
+    return t
+
+
+def scene_blend_bytes(table, C, S, q) -> float:  # noqa: N803
+    """Algorithmic bytes of one ``predict_blend`` launch: every ``on`` window's probabilities read once (``4 C`` per window pixel),
+    every canvas pixel under at least one of them read and written once (``8 (C + 1)``: the classes and the weight sum)."""
+    import numpy as np
+    rows = np.asarray(table).reshape(-1, 4)
+    rows = rows[rows[:, 3] != 0]
+    W = -(-S // q)  # noqa: N806
+    units = {(n, y, x) for n, y0, x0, _ in rows.tolist() for y in range(y0, y0 + W) for x in range(x0, x0 + W)}
+    return 4.0 * C * len(rows) * S * S + 8.0 * (C + 1) * min(len(units) * q * q, len(rows) * S * S)
+
+
+def window_gather(scene, out, table_dev, table_host, B, N, planes, Hs, Ws, S, q):  # noqa: N803
+    """``out[b, p, y, x] = scene[n_b, p, y0_b * q + y, x0_b * q + x]`` for the ``B`` rows ``(n, y0, x0, on)`` of the window table
+    (``table_dev`` int32 ``[B, 4]`` on the device, ``table_host`` the same rows on the host: checked before the launch).  ``scene``
+    f32 ``[N, planes, Hs, Ws]``, ``out`` f32 ``[B, planes, S, S]``; bit-exact data movement, pad slots (``on = 0``) included."""
+    _predict_out("window_gather", "scene", scene, torch.float32, N * planes * Hs * Ws)
+    _predict_out("window_gather", "out", out, torch.float32, B * planes * S * S)
+    _predict_out("window_gather", "table_dev", table_dev, torch.int32, 4 * B)
+    host = _scene_host_table("window_gather", table_host, B)
+    _hbm_call("window_gather", 8.0 * B * planes * S * S, "mh_window_gather", scene, out, table_dev, ctypes.c_void_p(host.ctypes.data),
+              _I(B), _I(N), _I(planes), _I(Hs), _I(Ws), _I(S), _I(q))
+
+
+def predict_blend(prob, scale, profile, table_dev, table_host, acc, wsum, B, N, C, S, q, Hc, Wc):  # noqa: N803
+    """The ``B`` windows of one batch onto the canvas: ``prob`` f32 ``[B, C, S, S]`` (the sum over views ``predict_view`` leaves) times
+    ``scale`` times the window weight ``profile[y] * profile[x]`` is added into ``acc`` f32 ``[N, C, Hc, Wc]`` and the weight into
+    ``wsum`` f32 ``[N, Hc, Wc]`` at the window's place, slot after slot in ascending order, every product and sum rounded on its own
+    (``scene_blend_reference`` states it).  Pad slots add nothing; pixels that no window of the batch covers are not touched."""
+    _predict_out("predict_blend", "prob", prob, torch.float32, B * C * S * S)
+    _predict_out("predict_blend", "profile", profile, torch.float32, S)
+    _predict_out("predict_blend", "table_dev", table_dev, torch.int32, 4 * B)
+    _predict_out("predict_blend", "acc", acc, torch.float32, N * C * Hc * Wc)
+    _predict_out("predict_blend", "wsum", wsum, torch.float32, N * Hc * Wc)
+    host = _scene_host_table("predict_blend", table_host, B)
+    nbytes = scene_blend_bytes(host, C, S, q) if _timer is not None else 0.0      # (only a KernelTimer reads them)
+    _hbm_call("predict_blend", nbytes, "mh_predict_blend", prob, _F(float(scale)), profile, table_dev,
+              ctypes.c_void_p(host.ctypes.data), acc, wsum, _I(B), _I(N), _I(C), _I(S), _I(q), _I(Hc), _I(Wc))
+
+
+def predict_blend_finish(acc, wsum, cls, conf, mean, N, C, n_pix):  # noqa: N803
+    """After the last batch: ``cls`` u8 ``[N, n_pix]`` = the arg-max over the classes of ``acc`` f32 ``[N, C, n_pix]`` (the rule of
+    ``predict_view``), ``conf`` = that maximum / ``wsum``, ``mean`` (the shape of ``acc``, or ``acc`` itself) = ``acc / wsum``,
+    correctly rounded; where ``wsum == 0``: ``SCENE_UNCOVERED``, 0, 0.  Any of ``cls``, ``conf``, ``mean`` may be ``None``, not all."""
+    _predict_out("predict_blend_finish", "acc", acc, torch.float32, N * C * n_pix)
+    _predict_out("predict_blend_finish", "wsum", wsum, torch.float32, N * n_pix)
+    _predict_out("predict_blend_finish", "cls", cls, torch.uint8, N * n_pix)
+    _predict_out("predict_blend_finish", "conf", conf, torch.float32, N * n_pix)
+    _predict_out("predict_blend_finish", "mean", mean, torch.float32, N * C * n_pix)
+    nbytes = N * n_pix * (4.0 * (C + 1) + (1 if cls is not None else 0) + (4 if conf is not None else 0) + (4 * C if mean is not None else 0))
+    _hbm_call("predict_blend_finish", nbytes, "mh_predict_blend_finish", acc, wsum, cls, conf, mean, _I(N), _I(C), _L(n_pix))
+
+
+def scene_finish_reference(acc, wsum):
+    """``predict_blend_finish`` restated in numpy f32: ``(cls, conf, mean)`` of ``acc [N, C, ...]`` and ``wsum [N, ...]``."""
+    import numpy as np
+    acc, wsum = np.asarray(acc, dtype=np.float32), np.asarray(wsum, dtype=np.float32)
+    covered = wsum != 0
+    w = np.where(covered, wsum, np.float32(1))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        mean = np.where(covered[:, None], acc / w[:, None], np.float32(0)).astype(np.float32)
+        arg = argmax_reference(acc, 1)
+        best = np.take_along_axis(acc, arg[:, None].astype(np.int64), axis=1)[:, 0]
+        conf = np.where(covered, best / w, np.float32(0)).astype(np.float32)
+    cls = np.where(covered, arg, SCENE_UNCOVERED).astype(np.uint8)
+    return cls, conf, mean
+
+
+def scene_blend_reference(prob, scale, profile, table, q, acc, wsum, finish=False):
+    """``predict_blend`` restated in numpy f32 (no GPU).  ``prob [B, C, S, S]``, ``profile [S]``, ``table`` the ``B`` rows
+    ``(n, y0, x0, on)``, ``acc [N, C, Hc, Wc]`` and ``wsum [N, Hc, Wc]`` the canvas so far (not modified).  The ``on`` slots are added
+    one after the other in ascending order -- for a pixel, ``wsum = ((wsum + w_b1) + w_b2) ...`` and per class ``acc = ((acc +
+    (prob_b1 * scale) * w_b1) + ...)``, ``w_b = profile[Y - y0_b q] * profile[X - x0_b q]``, each product and sum one fp32 operation.
+    Returns the new ``(acc, wsum)``, or with ``finish`` the ``(cls, conf, mean)`` of ``scene_finish_reference`` on them."""
+    import numpy as np
+    prob, profile = np.asarray(prob, dtype=np.float32), np.asarray(profile, dtype=np.float32)
+    acc, wsum = np.array(acc, dtype=np.float32), np.array(wsum, dtype=np.float32)
+    S = prob.shape[-1]  # noqa: N806
+    w = profile[:, None] * profile[None, :]
+    scale = np.float32(scale)
+    for b, (n, y0, x0, on) in enumerate(np.asarray(table).reshape(-1, 4).tolist()):
+        if not on:
+            continue
+        ys, xs = slice(y0 * q, y0 * q + S), slice(x0 * q, x0 * q + S)
+        if not 0 <= n < acc.shape[0] or y0 < 0 or x0 < 0 or ys.stop > acc.shape[2] or xs.stop > acc.shape[3]:
+            raise ValueError(f"scene_blend_reference: slot {b} = ({n}, {y0}, {x0}) leaves the canvas {acc.shape}")
+        wsum[n, ys, xs] = wsum[n, ys, xs] + w
+        acc[n, :, ys, xs] = acc[n, :, ys, xs] + (prob[b] * scale) * w[None]
+    return scene_finish_reference(acc, wsum) if finish else (acc, wsum)
 
 
 def zero_spans(base, spans, n_spans, max_len):

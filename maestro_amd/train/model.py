@@ -498,6 +498,27 @@ class SSLModule(_Base):
                 return engine.predict(batch, views=self.predict_views, threshold=thr)
         return engine.predict(batch, views=self.predict_views, threshold=thr)
 
+    def predict_scene(self, scene: dict, stride: int | None = None, blend: str = "linear", probs: bool = False,
+                      batch_size: int | None = None) -> dict:
+        """``SupervisedEngine.predict_scene`` for whole scenes (rasters larger than the model's window, cut into sliding windows
+        and blended on the device) under ``self.predict_views``, with the thresholds and the weights of ``predict_step``: every
+        multilabel target at its test metric's ``threshold_detect``, the EMA weights swapped in when finetuning with ``use_ema``.
+        ``batch_size``: windows per forward (default: the supervised engine's, 32 when none exists yet)."""
+        phase = self._ssl_phase()
+        if phase not in ("probe", "finetune"):
+            raise ValueError(f"predict_scene needs ssl phase 'probe' or 'finetune' (got {phase!r}): a pretrained model has no heads")
+        first = next(iter(self.dataset.inputs))
+        if batch_size is None:
+            cached = getattr(self.model, "_sup_engine", None)
+            batch_size = cached.B if cached is not None else 32
+        engine = self.model.sup_engine(batch_size, scene[first].device, phase)
+        thr = {t: getattr(self.metrics[f"{t}_test"], "threshold_detect", 0.5) if f"{t}_test" in self.metrics else 0.5 for t in engine.hb}
+        kw = dict(stride=stride, blend=blend, views=self.predict_views, probs=probs, threshold=thr)
+        if phase == "finetune" and self.ema_model is not None:
+            with engine.store.swapped(self._ema_flat(engine), engine._pack_conv_weights):
+                return engine.predict_scene(scene, **kw)
+        return engine.predict_scene(scene, **kw)
+
     def on_train_epoch_end(self) -> None:
         if self.ema_model is not None:
             self.update_ema()

@@ -319,6 +319,11 @@ class SupervisedLoop(_GuardSurface):
         """``SupervisedEngine.predict`` with the loop's current weights (a batch without labels; no optimizer state moves)."""
         return self.engine.predict(batch, views=views, probs=probs, threshold=threshold)
 
+    def predict_scene(self, scene: dict, stride: int | None = None, blend: str = "linear", views=(0,), probs: bool = False,
+                      threshold=0.5) -> dict:
+        """``SupervisedEngine.predict_scene`` with the loop's current weights (whole scenes, sliding windows blended on the device)."""
+        return self.engine.predict_scene(scene, stride=stride, blend=blend, views=views, probs=probs, threshold=threshold)
+
     def step(self, batch: dict) -> torch.Tensor:
         eng = self.engine
         loss = eng.forward(batch)
