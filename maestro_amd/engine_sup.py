@@ -45,6 +45,24 @@ class Prediction(NamedTuple):
     probs: torch.Tensor | None
 
 
+class Features(NamedTuple):
+    """Encoder features (``SupervisedEngine.encode``): device tensors, engine-owned -- valid until the next ``encode``.  ``bf16`` is
+    the round-to-nearest-even copy of ``f32``, the operand of ``hip.knn_topk``."""
+    f32: torch.Tensor
+    bf16: torch.Tensor
+
+
+FEATURE_LEVELS = ("sample", "grid")
+
+
+def check_encode_args(level, normalize) -> None:
+    """The argument checks of ``SupervisedEngine.encode``, before any launch."""
+    if level not in FEATURE_LEVELS:
+        raise ValueError(f"level={level!r}: \"sample\" (one feature per batch element) or \"grid\" (one per cell of the reference grid)")
+    if not isinstance(normalize, bool):
+        raise ValueError(f"normalize={normalize!r}: True or False")
+
+
 def parse_views(views) -> tuple:
     """``views`` of ``SupervisedEngine.predict`` as a tuple of dihedral flag bytes: a non-empty sequence of distinct values 0..7
     (bit 0 flips the rows, bit 1 the columns, bit 2 then swaps the axes: ``dataset.py:224-257``), or ``"d4"`` for all eight."""
@@ -115,7 +133,7 @@ def check_scene(scene: dict, rasters: dict, W: int, stride=None, blend: str = "l
 
 class SupervisedEngine(EngineBase):
     def __init__(self, model, batch_size: int, device, phase: str = "finetune", deterministic: bool = False) -> None:
-        if phase not in ("probe", "finetune"):
+        if phase not in ("probe", "finetune", "encode"):
             raise ValueError(f"Invalid ssl phase {phase}. Expected 'probe' or 'finetune'")
         if deterministic:
             raise ValueError("deterministic=True is not available for the probe / finetune step: the loss accumulators and the "
@@ -129,7 +147,7 @@ class SupervisedEngine(EngineBase):
         if fold and m.encoder_inter is not None:
             raise NotImplementedError(
                 f"Simultaneous encoding of all mods not yet compatible with fusion mode: {m.fusion_mode}.")  # model.py:65-67
-        if not len(m.heads):
+        if not len(m.heads) and phase != "encode":     # ("encode" runs the encoders alone: no head is needed, none is built)
             raise ValueError("the dataset config selects no target (filter_targets): nothing to probe / finetune")
         self.B, self.phase, self.E = batch_size, phase, m.embed_dim
         self._init_runtime(device, len(m.group_specs) - 1)
@@ -148,8 +166,11 @@ class SupervisedEngine(EngineBase):
         # ---- flat parameter store: encoder side first, heads last (probe trains the contiguous tail only)
         ordered, head_params = ordered_parameters(m)
         self.store = ParamStore(ordered, device)
-        lo, _ = self.store.span([p for _, p in head_params])
-        self.trainable_span = (lo, self.store.total) if phase == "probe" else (0, self.store.total)
+        if phase == "encode":
+            self.trainable_span = (self.store.total, self.store.total)      # nothing is trained
+        else:
+            lo, _ = self.store.span([p for _, p in head_params])
+            self.trainable_span = (lo, self.store.total) if phase == "probe" else (0, self.store.total)
         m.enc_pos_encoding = m.enc_pos_encoding.to(device)
         self._alloc()
         self.store.refresh_half(force=True)
@@ -175,13 +196,14 @@ class SupervisedEngine(EngineBase):
         ds = m.dataset
         self.hb = {}
         self.ref = None
-        seg = [t for t, c in ds.targets.items() if c.type_target == "segment"]
+        targets = {} if self.phase == "encode" else ds.targets      # "encode": encoders only, no head buffers
+        seg = [t for t, c in targets.items() if c.type_target == "segment"]
         if seg:
             G = m.out_grid_size[ds.ref_input]  # noqa: N806
             TD = sum(s.Dates for s in self.mods.values())  # noqa: N806
             self.ref = dict(G=G, Lr=G * G, TD=TD, x=e(B, TD * G * G, E), dx=e(B, TD * G * G, E))
             ws_rows = max(ws_rows, B * TD * G * G)
-        for t, c in ds.targets.items():
+        for t, c in targets.items():
             head = m.heads[t]
             attentive = hasattr(head, "reduce")
             if c.type_target == "segment":
@@ -209,8 +231,14 @@ class SupervisedEngine(EngineBase):
         self.scratch = e(ws_rows, E)      # LayerNorm-backward dx sink when the features are detached (probe)
 
     # ------------------------------------------------------------------------------------------ forward
+    def _refuse_encode_phase(self, what: str) -> None:
+        if self.phase == "encode":
+            raise ValueError(f"{what}() needs a 'probe' or 'finetune' engine: phase 'encode' runs the encoders alone and has no heads "
+                             "(use encode())")
+
     def forward(self, batch: dict) -> torch.Tensor:
         """Forward + ``loss_pred``; returns the loss as a 1-element device tensor (no host sync)."""
+        self._refuse_encode_phase("forward")
         if self.store.refresh_half():
             self._pack_conv_weights()
 
@@ -256,11 +284,14 @@ class SupervisedEngine(EngineBase):
             jn, R = self.joint.t.norm, B * self.JL  # noqa: N806
             hip.layernorm_fwd(self.joint.x_last, R, 0, jn.weight, jn.bias, self.xenc, R, 0, self.mean_j, self.rstd_j, 1, R, E)
         if self.ref is not None:          # compute_logits: every modality's token grid on the reference grid (mim.py:351-373)
-            r, d0 = self.ref, 0
-            for s in self.mods.values():
-                hip.token_resize(self.xenc, self.JL, self.goff[s.group] + s.tok_off, r["x"], r["TD"] * r["Lr"], d0 * r["Lr"], B,
-                                 s.Dates, s.g, r["G"], E)
-                d0 += s.Dates
+            self._tokens_on_ref_grid(self.ref)
+
+    def _tokens_on_ref_grid(self, r: dict) -> None:
+        d0 = 0
+        for s in self.mods.values():
+            hip.token_resize(self.xenc, self.JL, self.goff[s.group] + s.tok_off, r["x"], r["TD"] * r["Lr"], d0 * r["Lr"], self.B,
+                             s.Dates, s.g, r["G"], self.E)
+            d0 += s.Dates
 
     def _head_logits(self, t: str) -> None:
         """Head ``t`` from the encoded tokens up to and including its logits buffer."""
@@ -372,6 +403,7 @@ class SupervisedEngine(EngineBase):
         The returned tensors are the engine's own buffers: the next ``predict`` overwrites them.  Weights, gradients,
         ``loss_acc``, optimizer and metric state are untouched; the saved activations and ``logits()`` are those of the LAST
         view, in that view's orientation, so ``backward()`` raises until the next ``forward``."""
+        self._refuse_encode_phase("predict")
         views = parse_views(views)
         ds = self.model.dataset
         thr = {t: float(threshold[t] if isinstance(threshold, dict) else threshold) for t in self.hb}
@@ -401,6 +433,72 @@ class SupervisedEngine(EngineBase):
                                    threshold=thr[t], mean=pb["prob"] if probs else None)
             out[t] = Prediction(pb["cls"], pb["conf"], pb["prob"] if probs else None)
         return out
+
+    # ------------------------------------------------------------------------------------------ features
+    def _feature_buffers(self, level: str) -> dict:
+        """Engine-owned outputs of ``encode`` (stable addresses for the captured segments), allocated when first needed; for
+        ``"grid"`` on a model without a segment target also the token grids on the reference grid (``self.ref`` stays None: the
+        forward's launch list does not change)."""
+        if not hasattr(self, "_fb"):
+            self._fb = {}
+        fb = self._fb.get(level)
+        if fb is not None:
+            return fb
+        B, E, dev = self.B, self.E, self.device  # noqa: N806
+        if level == "sample":
+            fb = dict(rows=B, f32=torch.empty(B, E, dtype=F32, device=dev), bf16=torch.empty(B, E, dtype=BF16, device=dev), ref=None)
+        else:
+            ref = self.ref
+            if ref is None:
+                ds = self.model.dataset
+                if ds.ref_input is None:
+                    raise ValueError("encode(level='grid'): the dataset names no ref_input, so there is no reference grid")
+                G = self.model.out_grid_size[ds.ref_input]  # noqa: N806
+                TD = sum(s.Dates for s in self.mods.values())  # noqa: N806
+                ref = dict(G=G, Lr=G * G, TD=TD, x=torch.empty(B, TD * G * G, E, dtype=F32, device=dev))
+            fb = dict(rows=B * ref["Lr"], f32=torch.empty(B, ref["Lr"], E, dtype=F32, device=dev),
+                      bf16=torch.empty(B, ref["Lr"], E, dtype=BF16, device=dev), ref=ref)
+        self._fb[level] = fb
+        return fb
+
+    def _feature_launches(self, batch: dict, level: str, normalize: bool, fb: dict) -> None:
+        B, E = self.B, self.E  # noqa: N806
+        self._encode_launches(batch)
+        if level == "sample":
+            hip.mean_reduce_fwd(self.xenc, fb["f32"], B, self.JL, 1, E)
+        else:
+            r = fb["ref"]
+            if r is not self.ref:
+                self._tokens_on_ref_grid(r)
+            hip.mean_reduce_fwd(r["x"], fb["f32"], B, r["TD"], r["Lr"], E)
+        f32, b16 = fb["f32"].view(fb["rows"], E), fb["bf16"].view(fb["rows"], E)
+        if normalize:
+            hip.l2_normalize(f32, y=f32, y16=b16, eps=1e-12)
+        else:
+            hip.cast_bf16(f32, b16, fb["rows"] * E)
+
+    def encode(self, batch: dict, level: str = "sample", normalize: bool = True) -> Features:
+        """Encoder features ``Features(f32, bf16)`` of a batch WITHOUT labels (target keys are ignored), in every phase: embed,
+        encoders and the joint encoder as the forward runs them, nothing after.
+
+        ``level="sample"``: the mean over all ``JL`` encoded tokens, ``[B, E]`` (``mh_mean_reduce_fwd`` with ``T = JL, Lr = 1``);
+        ``level="grid"``: every modality's token grid on the reference grid ``G = out_grid_size[ref_input]`` (``mh_token_resize``),
+        mean over the ``TD`` date slices, ``[B, G * G, E]``.  ``normalize``: rows divided by ``max(||row||_2, 1e-12)``
+        (``mh_l2_normalize``, the rule of ``F.normalize``) with the bf16 copy rounded from the normalised fp32 row; off: the means
+        themselves and their ``mh_cast_bf16`` copy.  One captured segment per ``(level, normalize)``.
+
+        The returned tensors are the engine's own buffers: the next ``encode`` of the same level overwrites them.  Weights,
+        gradients, ``loss_acc``, optimizer and metric state are untouched; like ``predict`` it overwrites the encoders' saved
+        activations, so ``backward()`` raises until the next ``forward``."""
+        check_encode_args(level, normalize)
+        ds = self.model.dataset
+        fb = self._feature_buffers(level)
+        if self.store.refresh_half():
+            self._pack_conv_weights()
+        batch = self._stage_inputs({k: v for k, v in batch.items() if k not in ds.targets})
+        self._saved_for_backward = False
+        self._segment(f"sup_encode:{level}:{int(normalize)}", self._cur_key, lambda: self._feature_launches(batch, level, normalize, fb))
+        return Features(fb["f32"], fb["bf16"])
 
     def _view_buffers(self, batch: dict) -> dict:
         """The flag bytes and the transformed rasters of a dihedral view (engine-owned, allocated when first needed)."""
@@ -484,6 +582,7 @@ class SupervisedEngine(EngineBase):
         them); weights, gradients, ``loss_acc``, optimizer and metric state are untouched; ``backward()`` raises until the next
         ``forward``.  ValueError before any launch: extents that disagree between the rasters, an extent below one window, a
         stride outside ``1 .. W``, a raster that is not float32 / contiguous / on the GPU, an unknown ``blend``."""
+        self._refuse_encode_phase("predict_scene")
         views = parse_views(views)
         sources = [parts[0] for parts in self.model.src_specs.values()]
         geo = self.scene_geometry()
@@ -561,6 +660,7 @@ class SupervisedEngine(EngineBase):
 
     def backward(self, grad_scale: float = 1.0) -> None:
         """Backward of the last ``forward`` (d loss = 1) into the flat grad buffer (zero it first).  probe: heads only."""
+        self._refuse_encode_phase("backward")
         if grad_scale != 1.0:
             raise NotImplementedError("loss scaling is not needed for bf16")
         if not getattr(self, "_saved_for_backward", True):

@@ -53,6 +53,13 @@ def lib() -> ctypes.CDLL:
         _lib.mh_predict_blend.argtypes = [vp, ctypes.c_float, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
         _lib.mh_predict_blend_finish.argtypes = [vp, vp, vp, vp, vp, ci, ci, ctypes.c_long, vp]
         _lib.mh_window_gather.restype = _lib.mh_predict_blend.restype = _lib.mh_predict_blend_finish.restype = ci
+        _lib.mh_knn_splits.argtypes = [ci, ci, ci, ci]                                                                # csrc/knn_abi.hpp
+        _lib.mh_knn_workspace_bytes.argtypes = [ci, ci, ci]
+        _lib.mh_knn_workspace_bytes.restype = ctypes.c_long
+        _lib.mh_l2_normalize.argtypes = [vp, ctypes.c_long, ctypes.c_float, vp, ctypes.c_long, vp, ctypes.c_long, ctypes.c_long, ci, vp]
+        _lib.mh_knn_topk.argtypes = [vp, ctypes.c_long, vp, ctypes.c_long, ctypes.c_long, vp, vp, ci, vp, ctypes.c_long, ci, ci, ci, ci, ci, vp]
+        _lib.mh_knn_vote.argtypes = [vp, vp, vp, ctypes.c_long, ci, ctypes.c_float, ci, ci, vp, ctypes.c_long, vp, ci, ci, vp]
+        _lib.mh_knn_splits.restype = _lib.mh_l2_normalize.restype = _lib.mh_knn_topk.restype = _lib.mh_knn_vote.restype = ci
         _lib.mh_reduce_ordered.argtypes = [vp, vp, ci, vp, ci, vp]          # deterministic forms
         _lib.mh_colsum_partial_rows.argtypes = [ci]
         _lib.mh_masked_loss_partial_size.argtypes = _lib.mh_embed_bwd_partial_rows.argtypes = [ci, ci]
@@ -1344,6 +1351,220 @@ def scene_blend_reference(prob, scale, profile, table, q, acc, wsum, finish=Fals
         wsum[n, ys, xs] = wsum[n, ys, xs] + w
         acc[n, :, ys, xs] = acc[n, :, ys, xs] + (prob[b] * scale) * w[None]
     return scene_finish_reference(acc, wsum) if finish else (acc, wsum)
+
+
+# ---- nearest neighbours of encoder features (csrc/knn.hip, declarations in csrc/knn_abi.hpp)
+KNN_MAX_K = 128      # MH_KNN_MAX_K
+_knn_ws = {}         # (device index, Nq, k, splits) -> workspace of knn_topk
+
+
+def _knn_check(what, name, t, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "" if shape is None else f" of shape {list(shape)}"
+        raise HipExtensionError(f"{what}: {name} must be a {str(dtype).split('.')[-1]} tensor{want}")
+    if t.dim() and t.stride(-1) != 1:
+        raise HipExtensionError(f"{what}: {name} must have unit column stride")
+
+
+def _knn_rows(what, name, t, dtype):
+    """A ``[rows, E]`` operand with unit column stride: ``(rows, E, ld)``."""
+    _knn_check(what, name, t, dtype)
+    if t.dim() != 2:
+        raise HipExtensionError(f"{what}: {name} must be 2-dimensional [rows, E]")
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def _knn_gpu(what, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise HipExtensionError(f"{what}: maestro_amd kernels need GPU tensors (no CPU fallback)")
+
+
+def knn_splits(Nq: int, Nb: int, E: int, k: int) -> int:  # noqa: N803
+    """The bank-split rule of ``knn_topk`` (``mh_knn_splits``): a pure function of the shape."""
+    s = int(lib().mh_knn_splits(Nq, Nb, E, k))
+    if s < 1:
+        raise HipExtensionError(f"knn_splits: refused shape Nq = {Nq}, Nb = {Nb}, E = {E}, k = {k}")
+    return s
+
+
+def knn_workspace_bytes(Nq: int, k: int, splits: int) -> int:  # noqa: N803
+    n = int(lib().mh_knn_workspace_bytes(Nq, k, splits))
+    if n < 0:
+        raise HipExtensionError(f"knn_workspace_bytes: refused arguments Nq = {Nq}, k = {k}, splits = {splits}")
+    return n
+
+
+def l2_normalize(x, y=None, y16=None, eps: float = 1e-12):
+    """``y = x / max(||x||_2, eps)`` per row of ``x`` f32 ``[rows, E]`` (``F.normalize``); ``y`` f32 (may be ``x``) and / or ``y16``
+    bf16, the round-to-nearest-even copy of the fp32 result.  Row pitches are taken from the tensors."""
+    rows, E, ldx = _knn_rows("l2_normalize", "x", x, torch.float32)  # noqa: N806
+    if y is None and y16 is None:
+        raise HipExtensionError("l2_normalize: no output (y and y16 are both None)")
+    ldy = ldy16 = 0
+    if y is not None:
+        r, e, ldy = _knn_rows("l2_normalize", "y", y, torch.float32)
+        if (r, e) != (rows, E):
+            raise HipExtensionError(f"l2_normalize: y must be [{rows}, {E}]")
+    if y16 is not None:
+        r, e, ldy16 = _knn_rows("l2_normalize", "y16", y16, torch.bfloat16)
+        if (r, e) != (rows, E):
+            raise HipExtensionError(f"l2_normalize: y16 must be [{rows}, {E}]")
+    _knn_gpu("l2_normalize", x, y, y16)
+    call("mh_l2_normalize", x, _L(ldx), _F(float(eps)), y, _L(ldy), y16, _L(ldy16), _L(rows), _I(E))
+
+
+def knn_topk(q, bank, k: int, sims=None, idx=None, index_base: int = 0, accumulate: bool = False, splits: int | None = None):
+    """The ``k`` nearest rows of ``bank`` bf16 ``[Nb, E]`` for every row of ``q`` bf16 ``[Nq, E]`` under the order rule of
+    csrc/knn_abi.hpp (``knn_reference`` states it): ``(sims f32 [Nq, k], idx i32 [Nq, k])``, sorted, global indices
+    ``index_base + row``, unfilled slots ``(-inf, -1)``.  ``sims`` / ``idx`` are allocated when not given; with ``accumulate`` the
+    given ones are merged as further candidates (a bank streamed in chunks).  ``splits=None`` takes ``knn_splits``.  The workspace is
+    allocated once per ``(Nq, k, splits)`` and cached: call once eagerly before capturing a graph."""
+    Nq, E, ldq = _knn_rows("knn_topk", "q", q, torch.bfloat16)  # noqa: N806
+    Nb, Eb, ldb = _knn_rows("knn_topk", "bank", bank, torch.bfloat16)  # noqa: N806
+    if Eb != E:
+        raise HipExtensionError(f"knn_topk: q has {E} columns, bank {Eb}")
+    if accumulate and (sims is None or idx is None):
+        raise HipExtensionError("knn_topk: accumulate needs the sims and idx of the earlier calls")
+    if sims is not None or idx is not None:
+        _knn_check("knn_topk", "sims", sims, torch.float32, (Nq, k))
+        _knn_check("knn_topk", "idx", idx, torch.int32, (Nq, k))
+        if not sims.is_contiguous() or not idx.is_contiguous():
+            raise HipExtensionError("knn_topk: sims and idx must be contiguous")
+    _knn_gpu("knn_topk", q, bank, sims, idx)
+    if sims is None:
+        sims = torch.empty(Nq, k, dtype=torch.float32, device=q.device)
+        idx = torch.empty(Nq, k, dtype=torch.int32, device=q.device)
+    splits = knn_splits(Nq, Nb, E, k) if splits is None else int(splits)
+    nbytes = knn_workspace_bytes(Nq, k, splits)
+    key = (q.device.index, Nq, k, splits)
+    ws = _knn_ws.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise HipExtensionError(f"knn_topk: workspace for {key[1:]} first needed inside a hipGraph capture")
+        ws = _knn_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    _flop_call("knn_topk", 2.0 * Nq * Nb * E, (Nq, Nb, E), "mh_knn_topk", q, _L(ldq), bank, _L(ldb), _L(int(index_base)), sims, idx,
+               _I(1 if accumulate else 0), ws, _L(nbytes), _I(splits), _I(Nq), _I(Nb), _I(E), _I(k))
+    return sims, idx
+
+
+def knn_vote(sims, idx, labels, num_classes: int, T: float = 0.07, k_eval: int | None = None, missing_val: int = -1, scores=None,  # noqa: N803
+             cls=None, want_scores: bool = True, want_cls: bool = True):
+    """The weighted vote of csrc/knn_abi.hpp over the first ``k_eval`` entries of the sorted lists ``sims`` / ``idx`` ``[Nq, k]``:
+    ``(scores f32 [Nq, C], cls i32 [Nq])``; ``labels`` i32 ``[n_labels]``.  ``knn_vote_reference`` states it.  ``scores`` / ``cls`` are
+    allocated when not given, unless ``want_scores`` / ``want_cls`` is off (that output is then None; not both)."""
+    _knn_check("knn_vote", "sims", sims, torch.float32)
+    if sims.dim() != 2 or not sims.is_contiguous():
+        raise HipExtensionError("knn_vote: sims must be a contiguous [Nq, k] tensor")
+    Nq, k = sims.shape  # noqa: N806
+    _knn_check("knn_vote", "idx", idx, torch.int32, (Nq, k))
+    _knn_check("knn_vote", "labels", labels, torch.int32)
+    if not idx.is_contiguous() or labels.dim() != 1 or not labels.is_contiguous():
+        raise HipExtensionError("knn_vote: idx must be contiguous and labels a contiguous 1-dimensional tensor")
+    if not T > 0:
+        raise ValueError(f"knn_vote: temperature T = {T} (must be positive)")
+    C = int(num_classes)  # noqa: N806
+    k_eval = k if k_eval is None else int(k_eval)
+    lds = C
+    if scores is not None:
+        r, c, lds = _knn_rows("knn_vote", "scores", scores, torch.float32)
+        if (r, c) != (Nq, C):
+            raise HipExtensionError(f"knn_vote: scores must be [{Nq}, {C}]")
+    if cls is not None:
+        _knn_check("knn_vote", "cls", cls, torch.int32, (Nq,))
+    _knn_gpu("knn_vote", sims, idx, labels, scores, cls)
+    if scores is None and want_scores:
+        scores = torch.empty(Nq, C, dtype=torch.float32, device=sims.device)
+    if cls is None and want_cls:
+        cls = torch.empty(Nq, dtype=torch.int32, device=sims.device)
+    call("mh_knn_vote", sims, idx, labels, _L(labels.numel()), _I(int(missing_val)), _F(1.0 / float(T)), _I(k), _I(k_eval), scores, _L(lds),
+         cls, _I(Nq), _I(C))
+    return scores, cls
+
+
+def bf16_values(x):
+    """The values of bf16 operands as numpy f64: a ``torch.bfloat16`` tensor, or an array of raw bf16 bit patterns (uint16)."""
+    import numpy as np
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().to(torch.float64).numpy()
+    x = np.asarray(x)
+    if x.dtype == np.uint16:
+        return (x.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    return x.astype(np.float64)
+
+
+def knn_order(sims, idx):
+    """The order rule of csrc/knn_abi.hpp as a permutation of candidates (numpy arrays): larger similarity first, then the smaller
+    index; the caller has removed NaN similarities and negative indices."""
+    import numpy as np
+    return np.lexsort((np.asarray(idx), -np.asarray(sims)))
+
+
+def knn_reference(q, bank, k: int, index_base: int = 0, init=None, sims=None):
+    """``knn_topk`` restated in numpy (no GPU).  ``q`` ``[Nq, E]`` and ``bank`` ``[Nb, E]`` hold bf16 VALUES (``bf16_values`` takes
+    what the kernel takes); the similarity of a pair is their dot product in fp64 (exact wherever the kernel's fp32 sum is, e.g. for
+    small integers), or the given ``sims`` ``[Nq, Nb]`` (the tests pass measured or emulated similarities to state the rule alone).
+    Per query the candidates are the pairs ``(similarity, index_base + row)`` with a non-NaN similarity and, with ``init = (sims,
+    idx)`` of earlier calls, its entries with ``idx >= 0`` and a non-NaN similarity.  They are ordered by larger similarity first,
+    then smaller index; the first ``k`` are returned, sorted, as ``(f32 [Nq, k], i32 [Nq, k])``, unfilled slots ``(-inf, -1)``."""
+    import numpy as np
+    if sims is None:
+        q, bank = bf16_values(q), bf16_values(bank)
+        s_all = q @ bank.T if bank.shape[0] else np.zeros((q.shape[0], 0))
+    else:
+        s_all = np.asarray(sims, dtype=np.float64)
+    Nq, Nb = s_all.shape  # noqa: N806
+    out_s, out_i = np.full((Nq, k), -np.inf, dtype=np.float32), np.full((Nq, k), -1, dtype=np.int32)
+    gidx = index_base + np.arange(Nb, dtype=np.int64)
+    for n in range(Nq):
+        s, i = s_all[n], gidx
+        if init is not None:
+            s0, i0 = np.asarray(init[0][n], dtype=np.float64), np.asarray(init[1][n], dtype=np.int64)
+            s, i = np.concatenate([s0[i0 >= 0], s]), np.concatenate([i0[i0 >= 0], i])
+        keep = ~np.isnan(s)
+        s, i = s[keep], i[keep]
+        order = knn_order(s, i)[:k]
+        out_s[n, : len(order)], out_i[n, : len(order)] = s[order], i[order]
+    return out_s, out_i
+
+
+def knn_vote_reference(sims, idx, labels, num_classes: int, T: float = 0.07, k_eval: int | None = None, missing_val: int = -1,  # noqa: N803
+                       dtype=None):
+    """``knn_vote`` restated in numpy (no GPU): ``(scores [Nq, C], cls i32 [Nq])``.  In fp32 (the default) the kernel's operation
+    order: ``inv_T = fl(1 / T)``; per entry ``j < k_eval`` ``w_j = 1`` where ``sims[j] == sims[0]``, else ``exp(fl(fl(sims[j] -
+    sims[0]) * inv_T))`` (the exponential taken in fp64 and rounded to fp32: the one place the device differs, by its own
+    exponential's error); per class the
+    weights of the entries that vote for it are added one by one in ascending ``j`` from 0.  An entry votes when ``0 <= idx <
+    len(labels)``, its label is not ``missing_val`` and lies in ``[0, C)``.  ``cls`` = the lowest class among equal maxima of the
+    scores, -1 when no entry voted.  ``dtype=np.float64``: the same sums in fp64 from the fp32 similarities."""
+    import numpy as np
+    dtype = np.float32 if dtype is None else dtype
+    sims, idx, labels = np.asarray(sims, dtype=np.float32), np.asarray(idx, dtype=np.int64), np.asarray(labels, dtype=np.int64)
+    Nq, k = sims.shape  # noqa: N806
+    k_eval = k if k_eval is None else k_eval
+    if not 1 <= k_eval <= k:
+        raise ValueError(f"knn_vote_reference: k_eval = {k_eval} outside 1 ... k = {k}")
+    C = int(num_classes)  # noqa: N806
+    inv_t = dtype(np.float32(1.0 / float(T)))
+    scores, cls = np.zeros((Nq, C), dtype=dtype), np.full(Nq, -1, dtype=np.int32)
+    for n in range(Nq):
+        voted = False
+        s0 = sims[n, 0].astype(dtype)
+        for j in range(k_eval):
+            i = idx[n, j]
+            if not 0 <= i < len(labels):
+                continue
+            lab = labels[i]
+            if lab == missing_val or not 0 <= lab < C:
+                continue
+            s = sims[n, j].astype(dtype)
+            with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+                w = dtype(1) if s == s0 else dtype(np.exp(np.float64(dtype(dtype(s - s0) * inv_t))))
+            scores[n, lab] = dtype(scores[n, lab] + w)
+            voted = True
+        if voted:
+            cls[n] = int(np.argmax(scores[n]))          # (numpy: the first of equal maxima; no NaN can arise)
+    return scores, cls
 
 
 def zero_spans(base, spans, n_spans, max_len):

@@ -498,6 +498,21 @@ class SSLModule(_Base):
                 return engine.predict(batch, views=self.predict_views, threshold=thr)
         return engine.predict(batch, views=self.predict_views, threshold=thr)
 
+    def encode_step(self, batch: dict, batch_idx: int, level: str = "sample"):  # noqa: ARG002
+        """Encoder features ``Features(f32, bf16)`` of ``SupervisedEngine.encode`` (L2-normalised rows; ``level``: ``"sample"`` or
+        ``"grid"``) for a batch without labels -- what ``maestro_amd/train/knn.py`` scores.  Valid in every ssl phase: pretrain uses
+        an encoders-only engine (phase ``"encode"``: no head is needed), probe / finetune their own.  Finetune with ``use_ema``
+        encodes with the EMA weights, swapped in exactly as ``predict_step`` does."""
+        phase = self._ssl_phase()
+        if phase not in ("pretrain", "probe", "finetune"):
+            raise ValueError(f"Invalid ssl phase {phase}. Expected 'pretrain' or 'probe' or 'finetune'")
+        first = next(iter(self.dataset.inputs))
+        engine = self.model.sup_engine(batch[first].shape[0], batch[first].device, "encode" if phase == "pretrain" else phase)
+        if phase == "finetune" and self.ema_model is not None:
+            with engine.store.swapped(self._ema_flat(engine), engine._pack_conv_weights):
+                return engine.encode(batch, level=level)
+        return engine.encode(batch, level=level)
+
     def predict_scene(self, scene: dict, stride: int | None = None, blend: str = "linear", probs: bool = False,
                       batch_size: int | None = None) -> dict:
         """``SupervisedEngine.predict_scene`` for whole scenes (rasters larger than the model's window, cut into sliding windows
