@@ -177,7 +177,15 @@ int mh_gemm_fp8(int M, int N, int K, const void* A8, int lda, int a_format, cons
  * copy dst_t [cols, rows] of a [rows, cols] tensor when dst_t != NULL, cols %% 4 == 0);  2: cast AND fold max |src| into amax
  * (delayed scaling of activations: this step casts with the previous step's scale).  Values saturate at the format's largest
  * finite number.  mh_fp8_update_scales: scale = 2^(floor(log2(format_max / amax)) - margin_log2) (1 while amax is 0),
- * descale = 1 / scale, amax reset to 0 -- all on the device, capturable.
+ * descale = 1 / scale, amax reset to 0 -- all on the device, capturable.  The floor is the exact one, the largest e with
+ * amax 2^e <= format_max, for every finite amax > 0 -- held bit for bit where a float32 evaluation could slip: amax =
+ * format_max 2^-k and its fp32 neighbours, fp32 subnormals, the largest fp32 numbers; the exponent after the margin is clamped
+ * to [-100, 100]; an inf / NaN amax gives a NaN scale and descale.
+ * The cast at EVERY site of this header that writes fp8 bytes (the quantisers, the LayerNorm and GEMM output copies, the AdamW
+ * shadow): code = fp8(clamp(x * scale, -max, max)) with the product rounded once to fp32 (subnormal products are kept, not
+ * flushed), then round to nearest even; a result that rounds to zero keeps the sign of x; x is the fp32 value the site
+ * computed, never its bf16 rounding (the MX copies, which quantise the bf16 output by definition, excepted); the absmax is
+ * taken on |x| before the scale (tests/test_fp8_codes_gpu.py holds all of it bit for bit).
  * amax tables: ONE ROW of MH_FP8_AMAX_PITCH floats per slot, not one float -- same-cache-line atomics retire at about one per
  * 10 ns on MI355X (scripts/micro_amax.hip: 18432 LayerNorm rows folding into one word took 217 us instead of 19), so every
  * workgroup folds into sub-slot (its index %% MH_FP8_AMAX_SUBSLOTS) of the row, MH_FP8_AMAX_STRIDE floats (256 bytes) apart; a

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void update_scales_kernel(float* __restrict__ 
     if (l < MH_FP8_AMAX_SUBSLOTS) *row = 0.f;
     if (l != 0) return;
     float s = 1.f;
-    if (a > 0.f && a < 3.0e38f) {
+    if (a > 0.f && __float_as_uint(a) < 0x7f800000u) {   // every finite amax, the largest fp32 numbers included (exponent clamped below)
         int e = (int)floorf(log2f(fmax8 / a)) - margin;
         e = max(-100, min(100, e));
         s = exp2f((float)e);

@@ -25,26 +25,7 @@ def dev():
 
 
 # ---------------------------------------------------------------------------------------------------- host emulation
-def mx_ref(x: torch.Tensor):
-    """The MX rule in exact float64 arithmetic: bf16 [rows, cols] -> (e4m3 bytes [rows, cols], E8M0 bytes [rows, cols / 32],
-    finite-block mask [rows, cols / 32])."""
-    rows, cols = x.shape
-    v = x.cpu().double().view(rows, cols // 32, 32)
-    amax = v.abs().amax(-1)
-    finite = torch.isfinite(v).all(-1)
-    m, E = torch.frexp(torch.where(finite, amax, torch.ones_like(amax)))   # amax = m 2^E, m in [0.5, 1)  # noqa: N806
-    e = torch.where(m <= 0.875, E - 9, E - 8)                               # smallest e with amax <= 448 2^e = 0.875 2^(e + 9)
-    byte = torch.where(amax == 0, torch.full_like(e, 127), (127 + e).clamp(0, 254))
-    byte = torch.where(finite, byte, torch.full_like(byte, 255))
-    scaled = torch.ldexp(v, (127 - byte.clamp(max=254)).double()[..., None].expand_as(v))
-    q = scaled.float().to(torch.float8_e4m3fn).view(torch.uint8).view(rows, cols)
-    return q, byte.to(torch.uint8), finite
-
-
-def mx_dequant(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    rows, cols = q.shape
-    v = q.cpu().view(torch.float8_e4m3fn).double().view(rows, cols // 32, 32)
-    return torch.ldexp(v, (s.cpu().long() - 127).double()[..., None].expand_as(v)).view(rows, cols)
+from tests.fp8_codes import mx_dequant, mx_ref  # noqa: E402  (the MX rule in exact float64 arithmetic, and its inverse)
 
 
 def _scales(rows, cols, dev):
@@ -99,7 +80,8 @@ def test_quant_mx_matches_the_rule_bit_for_bit(dev):
 
 
 @pytest.mark.parametrize("tile", ["128", "128d", "256"])
-@pytest.mark.parametrize("M,N,K", [(256, 256, 128), (300, 520, 384), (1000, 136, 256), (64, 768, 768), (130, 264, 1152)])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 128), (300, 520, 384), (1000, 136, 256), (64, 768, 768), (130, 264, 1152),
+                                   (64, 256, 3072)])      # (the last: fc2's depth, 24 K steps; sum |terms| = 3.6e4 at most, in units of 2^-5: far below 2^24 units)
 def test_gemm_mx_exact_data(dev, M, N, K, tile, monkeypatch):
     """Small integers times independent random power-of-two block scales: every product and partial sum is exact in fp32, so
     any mistake in the per-lane scale map (row, K block), the A/B scale swap or the scale staging changes bits."""
