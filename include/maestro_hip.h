@@ -662,6 +662,135 @@ int mh_confusion_ce(const float* logits, const void* target, int target_bytes, l
 int mh_confusion_bce(const float* logits, const float* target, float missing_val, float logit_threshold, long long* cm, int B,
                      int C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- predictions (predict.hip)
+ * The reference has no prediction path; a user of it takes the head's logits [B, 1, C, S, S]
+ * (maestro/layers/head.py:116-130), torch.argmax over the class axis (maestro/layers/overlay.py:11-23) and, for a confidence,
+ * torch.softmax.  Test-time augmentation undoes the transforms the models are trained under (maestro/dataset/dataset.py:224-257:
+ * per sample, flip the rows, flip the columns, swap the two axes, in this order; the flag byte of mh_dihedral).
+ *
+ * Operands as for mh_ce_loss / mh_confusion_ce: `logits` is f32 in patch layout [B * g * g, ld >= P * P * C], column
+ * (p1 * P + p2) * C + c of token row (b * g + ty) * g + tx is class c of pixel (ty * P + p1, tx * P + p2) of the S x S raster,
+ * S = g * P; classification heads are g = P = 1.  Any ld and a 4-byte aligned base are accepted, 16-byte loads are used where
+ * ld % 4 == 0 and the base is 16-byte aligned, pad columns are never read, every logit is read once. */
+#define MH_PREDICT_SOFTMAX 0
+#define MH_PREDICT_SIGMOID 1
+/* One view of the batch.  `flags` (u8 [B], or NULL = identity) is the mh_dihedral flag byte that produced sample b's view: bit 0
+ * flipped the rows, bit 1 the columns, bit 2 then swapped the axes.  Pixel (y, x) of the view is written at its place (y0, x0) of
+ * the UNTRANSFORMED raster:  (y0, x0) = bit 2 ? (x, y) : (y, x);  bit 1: x0 = S - 1 - x0;  bit 0: y0 = S - 1 - y0.
+ *
+ * act = MH_PREDICT_SOFTMAX (2 <= C <= 128), in fp32 with m = max_j l_j:
+ *   prob  f32 raster [B, C, S, S] (the layout of the logits a reference user holds):
+ *         prob[b, c, y0, x0] = (accumulate ? old : 0) + exp(l_c - m) / sum_j exp(l_j - m) -- a plain read-modify-write by the one
+ *         thread that owns the pixel; no atomics
+ *   cls   u8 [B, S, S]: torch.argmax of the logits -- the lowest index among equal maxima, a NaN is the maximum and the first NaN
+ *         wins (the rule of mh_confusion_ce, one device function)
+ *   conf  f32 [B, S, S]: 1 / sum_j exp(l_j - m), the largest class probability
+ * act = MH_PREDICT_SIGMOID (1 <= C <= 1024, g = P = 1, flags ignored), `threshold` a LOGIT threshold (the decision of
+ * mh_confusion_bce):
+ *   prob  f32 [B, C] (+)= 1 / (1 + exp(-l));  cls u8 [B, C] = l > threshold;  conf f32 [B, C] = 1 / (1 + exp(-l))
+ * Each of prob, cls and conf may be NULL, not all three.  `threshold` is ignored for the softmax. */
+int mh_predict_view(const float* logits, const uint8_t* flags, int act, float threshold, float* prob, int accumulate, uint8_t* cls,
+                    float* conf, int B, int g, int P, int C, int ld, void* stream);
+/* After 1 / inv_views accumulated views.  `prob` is [B, C, n_pix] (n_pix = S * S, or 1 for classification heads).
+ *   softmax: cls[b, pix] = arg-max over c of prob[b, c, pix] under the same rule, conf[b, pix] = max * inv_views
+ *   sigmoid: cls[b, c] = prob * inv_views > threshold (`threshold` a PROBABILITY here), conf[b, c] = prob * inv_views (n_pix = 1)
+ *   mean (f32, the shape of prob; may be prob itself) = prob * inv_views, the mean probabilities: conf is their largest, bit for bit
+ * Each of cls, conf and mean may be NULL, not all three. */
+int mh_predict_finish(const float* prob, float inv_views, int act, float threshold, uint8_t* cls, float* conf, float* mean, int B, int C,
+                      long n_pix, void* stream);
+
+/* ---------------------------------------------------------------------------------------------- scene prediction (scene.hip)
+ * The window cut in front of the prediction path, the weighted accumulation of overlapping windows into a scene canvas behind
+ * it, and the canvas finish.  The reference cuts its training crops on the host, every modality at its own pixel scale on one
+ * common grid of UNITS (maestro/dataset/dataset.py:86-105, the size_gcd / crop_gcd rule of maestro/conf/dataset/utils.py:99-109),
+ * and has no scene inference.  Here a window is W x W units, W the greatest common divisor of the model's raster sizes, and a
+ * raster with q pixels per unit shows the window (y0, x0) at pixels [y0 * q, y0 * q + S) x [x0 * q, x0 * q + S), S = W * q.
+ *
+ * The window table: int32 rows (n, y0, x0, on) -- scene index, window origin in units, 1 for a real window and 0 for a pad slot
+ * (pad slots are gathered, so the model sees finite data, and blend nothing).  Every entry point takes the table of the B slots
+ * twice, as mh_reduce_ordered takes its job table: `table_host` is checked before the launch, `table_dev` is what the kernel
+ * reads.  A row of `table_dev` that names no scene or leaves the raster is skipped on the device, never followed. */
+#define MH_SCENE_MAX_SLOTS 1024      /* B of one launch */
+#define MH_SCENE_MAX_S 4096          /* window side in pixels of mh_predict_blend (its profile sits in LDS) */
+#define MH_SCENE_UNCOVERED 255       /* cls of a canvas pixel no window has reached */
+/* out[b, p, y, x] = scene[n_b, p, y0_b * q + y, x0_b * q + x]: `scene` f32 [N, planes, Hs, Ws], `out` f32 [B, planes, S, S],
+ * planes = dates * channels.  Pure data movement, bit-exact.  16-byte loads and stores where both bases are 16-byte aligned and
+ * Ws, S and every x0 * q are multiples of 4, one float at a time otherwise (4-byte aligned bases).  Refused: a row of
+ * `table_host` with n outside 0 .. N - 1 or a window that leaves the scene. */
+int mh_window_gather(const float* scene, float* out, const int32_t* table_dev, const int32_t* table_host, int B, int N, int planes,
+                     int Hs, int Ws, int S, int q, void* stream);
+/* The B windows of one batch onto the canvas.  `prob` f32 [B, C, S, S] (the sum over views mh_predict_view leaves), `profile`
+ * f32 [S], `acc` f32 [N, C, Hc, Wc], `wsum` f32 [N, Hc, Wc].  For every canvas pixel (n, Y, X) that at least one `on` slot covers,
+ * with b1 < b2 < ... the covering slots and w_b = profile[Y - y0_b * q] * profile[X - x0_b * q]:
+ *   wsum[n, Y, X]   = ((wsum + w_b1) + w_b2) ...
+ *   acc[n, c, Y, X] = ((acc + (prob[b1, c, ..] * scale) * w_b1) + (prob[b2, c, ..] * scale) * w_b2) ...
+ * every product and every sum a separately rounded fp32 operation (nothing is contracted into an FMA).  Pixels that no `on` slot
+ * covers are neither read nor written.  No atomics: the thread of the LOWEST covering slot owns the pixel and walks the slots in
+ * order, so the canvas bits depend on the order of the windows alone, not on how they are cut into launches.
+ * 2 <= C <= 128, B <= MH_SCENE_MAX_SLOTS, S <= MH_SCENE_MAX_S.  Refused: a row of `table_host` as for mh_window_gather. */
+int mh_predict_blend(const float* prob, float scale, const float* profile, const int32_t* table_dev, const int32_t* table_host,
+                     float* acc, float* wsum, int B, int N, int C, int S, int q, int Hc, int Wc, void* stream);
+/* After the last batch.  `acc` f32 [N, C, n_pix], `wsum` f32 [N, n_pix], n_pix = Hc * Wc.
+ *   cls  u8  [N, n_pix]: the arg-max over c of acc under the rule of mh_predict_view (one device function: the lowest index among
+ *        equal maxima, a NaN is the maximum and the first NaN wins)
+ *   conf f32 [N, n_pix]: that maximum / wsum;  mean f32 [N, C, n_pix] (may be `acc` itself) = acc / wsum
+ * with correctly rounded divisions; wsum == 0 (no window reached the pixel): cls = MH_SCENE_UNCOVERED, conf = 0, mean = 0.
+ * Each of cls, conf and mean may be NULL, not all three.  2 <= C <= 128. */
+int mh_predict_blend_finish(const float* acc, const float* wsum, uint8_t* cls, float* conf, float* mean, int N, int C, long n_pix,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------- nearest neighbours (knn.hip)
+ * Row normalisation of exported encoder features, the top-k cosine neighbours of bf16 queries in a bf16 feature bank, and the
+ * weighted vote over their labels.  The reference trains and scores its models through heads only
+ * (maestro/layers/head.py:116-130 gives the logits, maestro/train/metric.py the scores) and has no label-free evaluation of a
+ * pretrained encoder.  The protocol stated here is the weighted k-NN classifier of DINO (Caron et al., "Emerging Properties in
+ * Self-Supervised Vision Transformers", ICCV 2021, section 4.1, after Wu et al., CVPR 2018): features are L2-normalised with the
+ * rule of torch.nn.functional.normalize (x / max(||x||_2, eps)), the k bank rows of largest cosine similarity vote for their
+ * labels with weight exp(sim / T).
+ *
+ * The order rule.  Pairs (similarity, global index) are totally ordered: the larger similarity first, then the smaller index; an
+ * index below zero (an unfilled slot) comes after every real index, and a NaN similarity is no candidate at all.  Every list
+ * below is the head of its candidate set under this order, so it does not depend on how the work was cut. */
+#define MH_KNN_MAX_K 128
+/* The bank-split rule of mh_knn_topk: how many ways the bank is cut across workgroups so that few queries still fill the chip.
+ * A function of its arguments alone (no device query); 1 <= splits <= the number of 128-row bank tiles.  0 for arguments
+ * mh_knn_topk would refuse. */
+int mh_knn_splits(int Nq, int Nb, int E, int k);
+/* Bytes of the workspace of mh_knn_topk for `splits` splits: splits * Nq * k pairs of (f32, i32).  -1 for refused arguments. */
+long mh_knn_workspace_bytes(int Nq, int k, int splits);
+/* y[r, c] = x[r, c] / max(||x[r, :]||_2, eps) for `rows` rows of E columns; x f32 with row pitch ldx, y f32 with pitch ldy (may
+ * be NULL, may be x itself with ldy == ldx), y16 bf16 with pitch ldy16 (may be NULL; not both): the round-to-nearest-even bf16 of
+ * the fp32 quotient, bit for bit.  The sum of squares: lane l of a 64-lane wave takes s_l = fma(x_c, x_c, s_l) over its columns
+ * c = l, l + 64, ... in ascending order, the 64 partial sums are folded by the xor butterfly 32, 16, ... 1, all in fp32: an
+ * order that depends on E alone.  Then one correctly rounded sqrt, max with eps, and one correctly rounded division per element.
+ * A zero row gives zeros.  4-byte aligned x and y, 2-byte aligned y16, any pitch >= E.  1 <= E <= 65536, eps >= 0. */
+int mh_l2_normalize(const float* x, long ldx, float eps, float* y, long ldy, uint16_t* y16, long ldy16, long rows, int E,
+                    void* stream);
+/* The k nearest bank rows of every query.  q bf16 [Nq, E] with pitch ldq, bank bf16 [Nb, E] with pitch ldb; 16-byte aligned
+ * bases, pitches that are multiples of 8 and at most 2^20, E % 32 == 0, 32 <= E <= 1024, 1 <= k <= MH_KNN_MAX_K.
+ * The similarity of a pair is the fp32 accumulator of v_mfma_f32_16x16x32_bf16 over the E / 32 blocks of 32 columns in ascending
+ * order, started from zero: exact bf16 products, one order that depends on E alone -- not on the tile, split, chunk or row the
+ * pair falls in.
+ * sims f32 [Nq, k], idx i32 [Nq, k] (4-byte aligned, dense): per query the k first pairs (similarity, index_base + bank row)
+ * under the order rule, sorted by it; unfilled slots hold (-inf, -1).  accumulate = 1: the incoming sims / idx rows are further
+ * candidates (entries with idx < 0 or a NaN are none), so that a bank streamed in chunks gives the bits of one call;
+ * accumulate = 0: they are not read.  Nb = 0 (bank may then be NULL) is accepted with accumulate = 1 only.  index_base >= 0,
+ * index_base + Nb <= 2^31 - 1.
+ * `splits` >= 1 cuts the bank's 128-row tiles evenly over that many workgroups per 64-query tile (mh_knn_splits gives the rule's
+ * value; any value gives the same bits); the partial lists go to `ws` (16-byte aligned, at least
+ * mh_knn_workspace_bytes(Nq, k, splits) bytes) and a second launch on the same stream merges them.  No [Nq, Nb] buffer exists. */
+int mh_knn_topk(const uint16_t* q, long ldq, const uint16_t* bank, long ldb, long index_base, float* sims, int* idx, int accumulate,
+                void* ws, long ws_bytes, int splits, int Nq, int Nb, int E, int k, void* stream);
+/* The weighted vote over the first k_eval <= k entries of every sorted list (sims, idx: [Nq, k] as mh_knn_topk leaves them).
+ *   w_j = sims[j] == sims[0] ? 1 : exp((sims[j] - sims[0]) * inv_T)      (fp32: one subtraction, one product, expf)
+ *   scores[n, c] = sum over j in ascending order of w_j [labels[idx_j] == c], each sum one fp32 addition, from 0
+ * An entry with idx < 0, idx >= n_labels, a label equal to missing_val or a label outside [0, C) adds nothing.  labels i32
+ * [n_labels].  scores f32 [Nq, lds >= C] (pad columns untouched), cls i32 [Nq]: the lowest class among equal maxima of the
+ * scores just written (the arg-max rule of mh_confusion_ce), -1 when no entry voted.  Either may be NULL, not both.
+ * 2 <= C <= 1024, inv_T > 0 and finite, 1 <= k_eval <= k <= MH_KNN_MAX_K. */
+int mh_knn_vote(const float* sims, const int* idx, const int* labels, long n_labels, int missing_val, float inv_T, int k, int k_eval,
+                float* scores, long lds, int* cls, int Nq, int C, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- misc
  * column sums: out[n] += sum_m x[m, n]  (bias gradients); x bf16 or f32; atomically accumulated. */
 int mh_colsum(const void* x, int x_is_f32, float* out, int M, int N, int ld, void* stream);

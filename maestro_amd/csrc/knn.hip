@@ -1,5 +1,5 @@
 // Nearest neighbours of exported encoder features: row normalisation, the top-k cosine neighbours of bf16 queries in a bf16
-// bank, and the weighted vote over their labels.  C declarations and the full contract: knn_abi.hpp.
+// bank, and the weighted vote over their labels.  C declarations and the full contract: include/maestro_hip.h.
 //
 // mh_knn_topk is the project's bf16 NT tile loop (gemm_reg.hpp: buffer loads -> registers -> swizzled LDS -> ds_read_b128
 // fragments -> v_mfma_f32_16x16x32_bf16) with a selection for an epilogue, so the [Nq, Nb] similarities never leave the
@@ -10,7 +10,7 @@
 // entries t and t + 64; the position is a ballot count, the shift one shuffle.  Nothing here is a global atomic; the partial
 // lists of the splits are merged by a second kernel under the same order.
 #include "gemm_reg.hpp"
-#include "knn_abi.hpp"
+#include "../../include/maestro_hip.h"
 
 namespace {
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
     return a - b;
 }
 
-// The order rule of knn_abi.hpp: (s, i) comes before (ts, ti).  Indices compare as unsigned, so the -1 of an unfilled slot comes
+// The order rule of include/maestro_hip.h: (s, i) comes before (ts, ti).  Indices compare as unsigned, so the -1 of an unfilled slot comes
 // after every real index; a NaN s comes before nothing.
 __device__ __forceinline__ bool before(float s, int i, float ts, int ti) {
     return s > ts || (s == ts && (unsigned)i < (unsigned)ti);
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(const float* __restrict__
     if (l == 0) cls[qi] = voters > 0 ? arg : -1;
 }
 
-// One row per wave, four per workgroup; the order of the sum of squares is the one knn_abi.hpp states.
+// One row per wave, four per workgroup; the order of the sum of squares is the one include/maestro_hip.h states.
 __global__ __launch_bounds__(256) void l2_normalize_kernel(const float* x, long ldx, float eps, float* y, long ldy, bf16_t* __restrict__ y16,
                                                            long ldy16, long rows, int E) {
     const int l = threadIdx.x & 63;

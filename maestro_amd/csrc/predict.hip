@@ -1,12 +1,12 @@
 // Predictions from the resident head logits: class maps, confidences and class probabilities, one dihedral view at a time, and the
-// finish after several accumulated views (test-time augmentation).  C declarations and the full contract: predict_abi.hpp.
+// finish after several accumulated views (test-time augmentation).  C declarations and the full contract: include/maestro_hip.h.
 //
 // The softmax kernel is the walk of confusion_ce_kernel (logits_walk.hpp) writing a prediction instead of a histogram: tiles of
 // whole pixels staged in LDS by 16-byte loads in memory order, the next tile's loads in flight, one thread per pixel scanning its C
 // floats in LDS (no per-thread class array).  Nothing here is atomic: every output element has one writer.
 #include "common.hpp"
 #include "logits_walk.hpp"
-#include "predict_abi.hpp"
+#include "../../include/maestro_hip.h"
 
 namespace {
 

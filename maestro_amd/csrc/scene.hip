@@ -1,5 +1,5 @@
 // Scene prediction around the resident prediction path (predict.hip): the window cut in front of it, the weighted accumulation of
-// overlapping windows into a scene canvas behind it, and the canvas finish.  C declarations and the full contract: scene_abi.hpp.
+// overlapping windows into a scene canvas behind it, and the canvas finish.  C declarations and the full contract: include/maestro_hip.h.
 //
 // Nothing here is atomic.  The blend is a gather through an inverted index: a canvas pixel is owned by the thread of the LOWEST
 // slot whose window covers it, and that thread walks the covering slots in ascending order, so every pixel has one writer and
@@ -7,7 +7,7 @@
 // whose windows overlap the workgroup's own window: the O(B) test is paid once per workgroup, not per pixel.
 #include "common.hpp"
 #include "logits_walk.hpp"
-#include "scene_abi.hpp"
+#include "../../include/maestro_hip.h"
 
 namespace {
 
@@ -16,7 +16,7 @@ constexpr int SC_PASSES = 4;               // pixels of a window per blend workg
 constexpr int SC_MAX_CHUNKS = 64;          // workgroups along one plane of the gather (they stride over the plane)
 
 // Rounded one by one: a * b and a + b as separate fp32 operations, never contracted into an FMA (the build's default contracts
-// a + b * c, and under it __fmul_rn / __fadd_rn are the plain operators), so that the canvas holds the sums scene_abi.hpp states.
+// a + b * c, and under it __fmul_rn / __fadd_rn are the plain operators), so that the canvas holds the sums include/maestro_hip.h states.
 __device__ __forceinline__ float mul_rn(float a, float b) {
 #pragma clang fp contract(off)
     return a * b;

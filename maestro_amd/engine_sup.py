@@ -571,7 +571,7 @@ class SupervisedEngine(EngineBase):
         engine's window batch, the date rows by the slot's scene, the launch list of ``predict`` for every view of ``views``,
         ``mh_predict_blend`` per segment target with ``scale = 1 / len(views)``.  ``blend``: ``"linear"`` (a separable tent,
         ``hip.blend_profile``) or ``"flat"``; a canvas pixel is the weighted mean of the windows that cover it, summed in window
-        order whatever ``B`` is (csrc/scene_abi.hpp).  One ``mh_predict_blend_finish`` per segment target after the last batch.
+        order whatever ``B`` is (include/maestro_hip.h).  One ``mh_predict_blend_finish`` per segment target after the last batch.
 
         segment: ``cls`` u8 ``[N, Hc, Wc]``, ``conf`` f32 ``[N, Hc, Wc]``, ``probs`` f32 ``[N, C, Hc, Wc]`` or None, ``Hc = Hu * q_t``
         -- ``N * C * Hc * Wc * 4`` bytes of canvas per target, resident for the call: cutting a mosaic into scenes that fit is the

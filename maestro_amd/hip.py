@@ -46,14 +46,14 @@ def lib() -> ctypes.CDLL:
         _lib.mh_confusion_ce.argtypes = [vp, vp, ci, ctypes.c_long, vp, ci, ci, ci, ci, ci, vp]
         _lib.mh_confusion_bce.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp, ci, ci, vp]
         _lib.mh_confusion_ce.restype = _lib.mh_confusion_bce.restype = ci
-        _lib.mh_predict_view.argtypes = [vp, vp, ci, ctypes.c_float, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]     # csrc/predict_abi.hpp
+        _lib.mh_predict_view.argtypes = [vp, vp, ci, ctypes.c_float, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]     # predictions
         _lib.mh_predict_finish.argtypes = [vp, ctypes.c_float, ci, ctypes.c_float, vp, vp, vp, ci, ci, ctypes.c_long, vp]
         _lib.mh_predict_view.restype = _lib.mh_predict_finish.restype = ci
-        _lib.mh_window_gather.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]                          # csrc/scene_abi.hpp
+        _lib.mh_window_gather.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]                          # scene prediction
         _lib.mh_predict_blend.argtypes = [vp, ctypes.c_float, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
         _lib.mh_predict_blend_finish.argtypes = [vp, vp, vp, vp, vp, ci, ci, ctypes.c_long, vp]
         _lib.mh_window_gather.restype = _lib.mh_predict_blend.restype = _lib.mh_predict_blend_finish.restype = ci
-        _lib.mh_knn_splits.argtypes = [ci, ci, ci, ci]                                                                # csrc/knn_abi.hpp
+        _lib.mh_knn_splits.argtypes = [ci, ci, ci, ci]                                                                # nearest neighbours
         _lib.mh_knn_workspace_bytes.argtypes = [ci, ci, ci]
         _lib.mh_knn_workspace_bytes.restype = ctypes.c_long
         _lib.mh_l2_normalize.argtypes = [vp, ctypes.c_long, ctypes.c_float, vp, ctypes.c_long, vp, ctypes.c_long, ctypes.c_long, ci, vp]
@@ -1099,7 +1099,7 @@ def confusion_bce(logits, target, missing_val, threshold, cm, B, C):  # noqa: N8
     call("mh_confusion_bce", logits, target, _F(float(missing_val)), _F(logit_threshold(threshold)), cm, _I(B), _I(C))
 
 
-# ---- predictions (csrc/predict.hip, declarations in csrc/predict_abi.hpp)
+# ---- predictions (csrc/predict.hip, include/maestro_hip.h)
 PREDICT_SOFTMAX, PREDICT_SIGMOID = 0, 1
 
 
@@ -1204,7 +1204,7 @@ def predict_reference(logits, flags, act, *, g=1, P=1, C=None, threshold=0.5, pr
     return (p if prob is None else (prob + p).astype(dtype)), cls, conf
 
 
-# ---- scene prediction (csrc/scene.hip, declarations in csrc/scene_abi.hpp)
+# ---- scene prediction (csrc/scene.hip, include/maestro_hip.h)
 SCENE_MAX_SLOTS, SCENE_MAX_S, SCENE_UNCOVERED = 1024, 4096, 255      # MH_SCENE_MAX_SLOTS, MH_SCENE_MAX_S, MH_SCENE_UNCOVERED
 
 
@@ -1353,7 +1353,7 @@ def scene_blend_reference(prob, scale, profile, table, q, acc, wsum, finish=Fals
     return scene_finish_reference(acc, wsum) if finish else (acc, wsum)
 
 
-# ---- nearest neighbours of encoder features (csrc/knn.hip, declarations in csrc/knn_abi.hpp)
+# ---- nearest neighbours of encoder features (csrc/knn.hip, include/maestro_hip.h)
 KNN_MAX_K = 128      # MH_KNN_MAX_K
 _knn_ws = {}         # (device index, Nq, k, splits) -> workspace of knn_topk
 
@@ -1416,7 +1416,7 @@ def l2_normalize(x, y=None, y16=None, eps: float = 1e-12):
 
 def knn_topk(q, bank, k: int, sims=None, idx=None, index_base: int = 0, accumulate: bool = False, splits: int | None = None):
     """The ``k`` nearest rows of ``bank`` bf16 ``[Nb, E]`` for every row of ``q`` bf16 ``[Nq, E]`` under the order rule of
-    csrc/knn_abi.hpp (``knn_reference`` states it): ``(sims f32 [Nq, k], idx i32 [Nq, k])``, sorted, global indices
+    include/maestro_hip.h (``knn_reference`` states it): ``(sims f32 [Nq, k], idx i32 [Nq, k])``, sorted, global indices
     ``index_base + row``, unfilled slots ``(-inf, -1)``.  ``sims`` / ``idx`` are allocated when not given; with ``accumulate`` the
     given ones are merged as further candidates (a bank streamed in chunks).  ``splits=None`` takes ``knn_splits``.  The workspace is
     allocated once per ``(Nq, k, splits)`` and cached: call once eagerly before capturing a graph."""
@@ -1450,7 +1450,7 @@ def knn_topk(q, bank, k: int, sims=None, idx=None, index_base: int = 0, accumula
 
 def knn_vote(sims, idx, labels, num_classes: int, T: float = 0.07, k_eval: int | None = None, missing_val: int = -1, scores=None,  # noqa: N803
              cls=None, want_scores: bool = True, want_cls: bool = True):
-    """The weighted vote of csrc/knn_abi.hpp over the first ``k_eval`` entries of the sorted lists ``sims`` / ``idx`` ``[Nq, k]``:
+    """The weighted vote of include/maestro_hip.h over the first ``k_eval`` entries of the sorted lists ``sims`` / ``idx`` ``[Nq, k]``:
     ``(scores f32 [Nq, C], cls i32 [Nq])``; ``labels`` i32 ``[n_labels]``.  ``knn_vote_reference`` states it.  ``scores`` / ``cls`` are
     allocated when not given, unless ``want_scores`` / ``want_cls`` is off (that output is then None; not both)."""
     _knn_check("knn_vote", "sims", sims, torch.float32)
@@ -1494,7 +1494,7 @@ def bf16_values(x):
 
 
 def knn_order(sims, idx):
-    """The order rule of csrc/knn_abi.hpp as a permutation of candidates (numpy arrays): larger similarity first, then the smaller
+    """The order rule of include/maestro_hip.h as a permutation of candidates (numpy arrays): larger similarity first, then the smaller
     index; the caller has removed NaN similarities and negative indices."""
     import numpy as np
     return np.lexsort((np.asarray(idx), -np.asarray(sims)))

@@ -1,6 +1,6 @@
 """Label-cheap evaluation of an encoder: a device-resident bank of labelled features and the weighted k-nearest-neighbour
 classifier over it (the DINO protocol: cosine similarity of L2-normalised features, ``k`` neighbours, votes weighted by
-``exp(sim / T)``).  The reference has no such path; csrc/knn_abi.hpp states what the three kernels compute, ``hip.knn_reference``
+``exp(sim / T)``).  The reference has no such path; include/maestro_hip.h states what the three kernels compute, ``hip.knn_reference``
 and ``hip.knn_vote_reference`` restate it in numpy.
 
     engine = model.sup_engine(B, device, "encode")

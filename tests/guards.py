@@ -214,7 +214,8 @@ def bits_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
 # files listed here) and EXEMPT; tests/test_abi.py enforces it, so a new entry point cannot arrive without a decision.
 GUARD_TEST_FILES = ("test_guard_bands_gpu.py", "test_fp8_gpu.py", "test_mx_gpu.py", "test_det_kernels_gpu.py",
                     "test_step_ends_gpu.py", "test_metrics_gpu.py", "test_date_select_gpu.py", "test_mask_rng_gpu.py",
-                    "test_grad_guard_gpu.py", "test_adamw_groups_gpu.py", "test_adamw_moments_gpu.py")
+                    "test_grad_guard_gpu.py", "test_adamw_groups_gpu.py", "test_adamw_moments_gpu.py", "test_predict_gpu.py",
+                    "test_scene_gpu.py", "test_knn_gpu.py")
 
 # name -> how a guard test reaches it when not by its own name or the hip.py wrapper of the same name (hip.<name without mh_>)
 VIA = {
@@ -250,6 +251,8 @@ GUARDED = {
     "mh_unmask_token_grad_per_sample_det", "mh_embed_finish_bwd_det",
     "mh_masked_loss_cs", "mh_masked_loss_bands_cs", "mh_gather_rows_bf16_cs", "mh_embed_finish_bwd_ends",
     "mh_confusion_ce", "mh_confusion_bce", "mh_select_dates",
+    "mh_predict_view", "mh_predict_finish", "mh_window_gather", "mh_predict_blend", "mh_predict_blend_finish",
+    "mh_l2_normalize", "mh_knn_topk", "mh_knn_vote",
 }
 
 # The calls that touch no device buffer (sizes, version, error text) are exempt as such; at most MAX_OTHER_EXEMPT further names
@@ -271,5 +274,7 @@ EXEMPT = {
     "mh_gather_rows_cs_rows": NO_DEVICE_BUFFER,
     "mh_embed_bwd_cs_rows": NO_DEVICE_BUFFER,
     "mh_grad_sumsq_partial_rows": NO_DEVICE_BUFFER,
+    "mh_knn_splits": NO_DEVICE_BUFFER,
+    "mh_knn_workspace_bytes": NO_DEVICE_BUFFER,
 }
 MAX_OTHER_EXEMPT = 6

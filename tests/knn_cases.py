@@ -1,4 +1,4 @@
-"""Cases, wrong forms and derived error bounds for the nearest-neighbour kernels (csrc/knn_abi.hpp), shared by
+"""Cases, wrong forms and derived error bounds for the nearest-neighbour kernels (include/maestro_hip.h), shared by
 tests/test_knn_host.py (no GPU: the references' own teeth) and tests/test_knn_gpu.py (the kernels on the same cases).
 
 Bounds (u = 2^-24, the unit roundoff of fp32; derived, not fitted):

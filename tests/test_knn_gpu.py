@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-# ----------------------------------------------------------------------------------------------------- guarded callers
+# ----------------------------------------------------------------------------------- guarded callers: guard bands (tests/guards.py)
 def topk_call(q, bank, k, index_base=0, init=None, splits=None, pad=8):
     """``hip.knn_topk`` on guarded operands (``pad`` NaN columns behind every row; sims / idx dense at a 4-byte aligned base).
     ``init``: CPU ``(sims, idx)`` of earlier chunks (accumulate).  Returns CPU numpy ``(sims, idx)``."""

@@ -1,4 +1,4 @@
-"""The prediction path without a GPU: the two entry points of csrc/predict_abi.hpp (declared, exported, bound, bad arguments
+"""The prediction path without a GPU: its two entry points of include/maestro_hip.h (declared, exported, bound, bad arguments
 refused before any launch), ``hip.predict_reference`` against torch on the CPU, and the argument checks of the Python surfaces."""
 
 import ctypes
@@ -22,9 +22,9 @@ NULL = ctypes.c_void_p(0)
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
 def test_predict_names_are_declared_exported_and_bound():
-    header = (ROOT / "maestro_amd" / "csrc" / "predict_abi.hpp").read_text()
-    declared = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", re.sub(r"//[^\n]*", "", header)))
-    assert declared == set(NAMES)
+    header = (ROOT / "include" / "maestro_hip.h").read_text()
+    declared = set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", header))
+    assert set(NAMES) <= declared
     assert 'extern "C"' in header
     for ref in ("maestro/layers/head.py:116-130", "maestro/layers/overlay.py:11-23", "maestro/dataset/dataset.py:224-257"):
         assert ref in header
